@@ -22,6 +22,11 @@ Prints ONE JSON line (rank 0) with the driver's contract plus
                   forward -> metrics): what a user sees, bounded by JPEG decoding on the host cores;
   serving       - SelfMaskInference.predict_tensors at batch 1 (app.py's call pattern): p50 / p99 latency.
 --quick skips everything but the timed steps and the roofline (profiling runs).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32), for comparing two builds output for
+output: `rows` - the per-image result rows of that step, every rank's (B*N, 16: 7 metrics of the picked mask, 7 of the upper
+bound, the two query ids); `mask_pred`, `objectness`, `features` - rank 0's MaskFormer.forward outputs for that batch.  The
+inputs are seeded, so the same arguments give the same inputs on every run.  At most 64 MB in all: an array over its share is
+replaced by a fixed, seeded sample of its flattened elements (listed under "dump_outputs" in the JSON line).
 """
 import argparse
 import json
@@ -41,6 +46,7 @@ F32_MFMA_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, 64 
 F16_MFMA_PEAK_TFLOPS = 2500.0  # dense f16/bf16 MFMA (v_mfma_f32_32x32x16_f16); the split GEMM issues 3 MFMA flops per
                                # algorithmic flop, so its fp32-equivalent roof is 833 TFLOP/s
 HBM_PEAK_GBS = 8000.0
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: all .npy files together, headers included
 
 
 def forward_flops_per_image(P, S, L=6, nq=20):
@@ -345,11 +351,14 @@ class Workload:
         self.x_host = self.x.cpu().pin_memory() if host_input else None
         self.fwd = GraphedForward(self.model, enabled=graph)
         self.ring = StreamRing(dev, max(1, streams))
+        self.keep_last, self.last_out = False, None  # --dump-outputs: hold the latest step's forward outputs
 
     def step(self):
         # one evaluator iteration over a batch (evaluator.pyc@L193-228, batched mode): forward, last decoder
         # layer, up-sample to each GT's size, upper-bound + arg-max-objectness query, 7 metrics x 2 -> 16 floats/image
         out = self.fwd(self.x_host.to(self.dev, non_blocking=True) if self.x_host is not None else self.x)
+        if self.keep_last:
+            self.last_out = out
         if self.forward_only:
             return out["objectness"][:, -1, :16, 0]
         return self.ops.evaluate_masks(out["mask_pred"][:, -1], out["objectness"][:, -1, :, 0], self.gt_batch, scale=0.0)
@@ -696,6 +705,27 @@ def max_over_ranks(values, dev) -> list:
     return t.tolist()
 
 
+def dump_outputs(arrays: dict, out_dir: str, budget: int = DUMP_BUDGET_BYTES) -> dict:
+    """--dump-outputs: every array as out_dir/<name>.npy in float32, all files together at most `budget` bytes.  If the arrays
+    are larger, each keeps its share of the budget as a fixed sample of its flattened elements (seeded, sorted indices: the
+    same shape gives the same sample on every run).  Returns {name: {"shape", "saved_elements", "sampled"}}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    room = budget - 1024 * len(arrays)  # .npy headers
+    total = sum(v.nbytes for v in arrays.values())
+    info = {}
+    for name, v in arrays.items():
+        flat = v.reshape(-1)
+        keep = v.size if total <= room else v.size * room // total
+        if keep < v.size:
+            idx = np.sort(np.random.Generator(np.random.PCG64(0)).choice(v.size, keep, replace=False))
+            flat = flat[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), flat if keep < v.size else v)
+        info[name] = {"shape": list(v.shape), "saved_elements": int(keep), "sampled": bool(keep < v.size)}
+    return info
+
+
 def spawn_ranks(n: int, argv) -> int:
     """Start `n` ranks of this script under torch.distributed.run (one process per GPU, rendezvous on 127.0.0.1) and
     wait for them.  The parent never touches the GPU: ranks are fresh processes, nothing is exec'ed after HIP init."""
@@ -787,7 +817,12 @@ def main():
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="CPU rehearsal of the N-rank launch path (gloo, no GPU): same spawn, barrier, gather and "
                          "max-over-ranks timing around a trivial step; used by tests/test_bench_launcher_cpu.py")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy (float32, at most "
+                         "64 MB in all): the per-image result rows and rank 0's forward outputs")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error(f"--steps must be >= 1 and --warmup >= 0 (got {a.steps}, {a.warmup})")
 
     # ---- N ranks: one process per GPU ------------------------------------------------------------------------------
     # `python bench.py --gpus N` with no WORLD_SIZE in the environment starts the N ranks itself, as FRESH child
@@ -834,6 +869,7 @@ def main():
     run_steps((fwd.policy.admit_after + 1) * len(ring.streams))
     run_steps(a.warmup)
     rows = torch.zeros((a.steps * B, 16), device=dev)  # per-image result rows (14 metrics + the two query ids)
+    wl.keep_last = a.dump_outputs is not None
 
     def sync():
         torch.cuda.synchronize()
@@ -851,6 +887,17 @@ def main():
     dt = time.perf_counter() - t0
     if world > 1:
         dt = max_over_ranks([dt], dev)[0]
+
+    # --dump-outputs: the last timed step's results, copied to the host before any later leg runs the model again
+    dumped = None
+    if a.dump_outputs is not None:
+        last = slice((a.steps - 1) * B, a.steps * B)
+        last_rows = gathered.view(world, a.steps * B, 16)[:, last].reshape(world * B, 16) if world > 1 else rows[last]
+        if rank == 0:
+            arrays = {"rows": last_rows.cpu().numpy()}
+            arrays.update({k: v.cpu().numpy() for k, v in wl.last_out.items() if isinstance(v, torch.Tensor)})
+            dumped = dump_outputs(arrays, a.dump_outputs)
+        wl.keep_last, wl.last_out = False, None
 
     # per-kernel taps right behind the timed steps (same clocks / cache state as the K steps; agreement with rocprofv3's
     # kernel-trace averages of the same command is checked in profiles/)
@@ -927,6 +974,8 @@ def main():
         }
         res["sustained"] = sustained
         res["end_to_end"] = e2e
+        if dumped is not None:
+            res["dump_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
         if world == 1 and not a.quick:
             res["serving"] = serving_latency(model, dev)
             if model.gemm_mode == "w16" and not a.zero_data:

@@ -17,6 +17,7 @@ generation is destroyed before the next call.
 
 The outputs of a replay live in the graph's memory pool and are overwritten by the next replay on the same key;
 consume them on the same stream before calling again (the Evaluator and bench.py do)."""
+import gc
 from collections import OrderedDict
 from typing import Callable, Dict, Hashable, Optional
 
@@ -121,10 +122,20 @@ class GraphedForward:
             # all graphs the same scratch: each graph owns its workspace instead
             ws = self.model.new_workspace(static_x)
             graph = torch.cuda.CUDAGraph()
-            # thread_local: the capture only polices this thread - an RCCL watchdog thread polling its events while we
-            # capture (torch.distributed is initialised in multi-GPU runs) must not invalidate it
-            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                out = self.model(static_x, workspace=ws)
+            # no cyclic garbage collection inside the capture: a dead cycle that still holds HIP objects (streams, events,
+            # pinned or device memory) would be freed in the middle of it, and a free / destroy there aborts the process.
+            # torch's graph context stopped collecting before capture_begin, so collect here while it is still safe
+            gc_was_on = gc.isenabled()
+            gc.collect()
+            gc.disable()
+            try:
+                # thread_local: the capture only polices this thread - an RCCL watchdog thread polling its events while we
+                # capture (torch.distributed is initialised in multi-GPU runs) must not invalidate it
+                with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                    out = self.model(static_x, workspace=ws)
+            finally:
+                if gc_was_on:
+                    gc.enable()
         except Exception as e:  # capture unsupported here: keep the eager HIP path, say why once
             self.failed = f"{type(e).__name__}: {e}"
             return None
