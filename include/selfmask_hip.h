@@ -122,8 +122,8 @@ int sm_gemm_f16x2_pick_tile(const sm_gemm_args* args, int* bm, int* bn, int* nst
  * transformer_decoder.py:271-293; maskformer.py:265-268); W must be a weight (batch 1). */
 int sm_split_w16(const float* src, int64_t ld_src, float* dst, int64_t ld_dst, int64_t rows, int32_t K, float scale,
                  void* stream);
-/* variant: 0 = 256x128 (8 waves, 16-k stages x3), 1 = 256x128 (16 waves, 32-k x2), 2 = 128x128 (8 waves), 3 = 128x128
- * (4 waves, 16-k x3), 4 = 64x64, 6 = 256x128 (8 waves, 32-k x2), 7 = 128x64 */
+/* variant (v_mfma_f32_16x16x32_f16, 32-k stages): 40 = 256x256 (16 waves), 42 = 128x128 (8 waves), 43 = 256x192 (16 waves),
+ * 44 = 64x64 (4 waves, ring of three), 45 = 128x64 (4 waves), 47 = 256x128 (16 waves, ring of three) */
 int sm_gemm_w16_tile(const sm_gemm_args* args, int out_f16x2, int variant, void* stream);
 int sm_gemm_w16(const sm_gemm_args* args, int out_f16x2, void* stream);
 int sm_gemm_w16_pick(const sm_gemm_args* args); /* the variant sm_gemm_w16 launches for this shape */

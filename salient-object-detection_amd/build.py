@@ -1,9 +1,9 @@
 """Build libselfmask_hip.so in-tree with hipcc for gfx950 (no torch headers: the library is a plain C ABI).
 
 Each ``csrc/*.hip`` becomes an object under ``build/`` (recompiled only when it or a header changed, several in
-parallel), then one link.  ``SM_TUNING=1`` (or ``build(tuning=True)``) defines ``SM_TUNING``: the timing-only ablation
-switches of the GEMM / attention kernels exist only in that build (``lib/libselfmask_hip_tuning.so``), never in the
-product library.
+parallel), then one link.  ``SM_TUNING=1`` (or ``build(tuning=True)``) defines ``SM_TUNING``: that build
+(``lib/libselfmask_hip_tuning.so``) adds environment switches that force a choice between the product's own code paths
+(tile, walk, plan; tests compare the paths through it) and in-kernel stamps, never anything the product library lacks.
 """
 import os
 import shutil

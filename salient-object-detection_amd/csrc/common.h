@@ -33,15 +33,10 @@ inline int check_launch(const char* what) {
         }                              \
     } while (0)
 
-// 64-lane butterfly reductions (wavefront shuffles; every lane ends with the total)
+// 64-lane butterfly reduction (wavefront shuffles; every lane ends with the total)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
 
@@ -95,16 +90,10 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// The hi conversion goes through inline asm so that the value stored and the value subtracted are ONE conversion
-// result: left to itself hipcc emitted a packed round-toward-zero convert for a stored vector and a round-to-nearest
-// one for the subtraction (lo then had the wrong sign whenever the two roundings differed).
-__device__ __forceinline__ void split1(float x, _Float16& hi, _Float16& lo) {
-    float hf;
-    asm("v_cvt_f16_f32 %0, %1" : "=v"(hi) : "v"(x));
-    asm("v_cvt_f32_f16 %0, %1" : "=v"(hf) : "v"(hi));
-    lo = (_Float16)((x - hf) * 2048.0f);
-}
-// Two elements in 5 VALU instructions instead of 12, same bits as split1: one packed round-to-nearest convert (gfx950
+// hi = f16(x), lo = f16((x - hi) * 2^11).  The hi conversion goes through inline asm so that the value stored and the value
+// subtracted are ONE conversion result: left to itself hipcc emitted a packed round-toward-zero convert for a stored vector and a
+// round-to-nearest one for the subtraction (lo then had the wrong sign whenever the two roundings differed).
+// Two elements in 5 VALU instructions instead of 12 for the element-wise form: one packed round-to-nearest convert (gfx950
 // v_cvt_pk_f16_f32) for the hi pair, then lo = f16(fma(f32(hi), -2048, 2048 x)) by v_fma_mixlo/mixhi_f16, which read the
 // f16 halves of the hi register directly and write the halves of the lo register (2048 (x - hi) is exact in f32, so the
 // single fma rounds like the subtract-multiply-convert chain).
@@ -162,14 +151,6 @@ __device__ __forceinline__ void store_f16x2_4(void* row, int64_t k, const float 
     char* p = reinterpret_cast<char*>(row) + f16x2_off(k);
     *reinterpret_cast<f16x4*>(p) = hi;
     *reinterpret_cast<f16x4*>(p + 16) = lo;
-}
-// store 2 consecutive elements k, k+1 (k even)
-__device__ __forceinline__ void store_f16x2_2(void* row, int64_t k, float x0, float x1) {
-    f16x2 hi, lo;
-    split2(x0, x1, hi, lo);
-    char* p = reinterpret_cast<char*>(row) + f16x2_off(k);
-    *reinterpret_cast<f16x2*>(p) = hi;
-    *reinterpret_cast<f16x2*>(p + 16) = lo;
 }
 
 // Lanes l and l^32 each hold elements 4h..4h+3 (h = l >> 5) of two consecutive 8-element groups: x of group G, y of
@@ -274,15 +255,10 @@ __device__ __forceinline__ void gelu4(float (&t)[4]) {
 //     (kg, x), bank row 128 B for stores: the eight slots must differ.  The round-2/3 image (a rotation by row bit 3, an XOR by row
 //     bit 1) served the reads but put those eight lanes on TWO slots - a 4-way conflict on every K / V^T store, the
 //     SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.17 of profiles/r03_pmc_sq_counters.txt.
-#ifdef SM_M16_SLOT_R3  // the previous image, for A/B builds only (build.py --variant=slot_r3 -DSM_M16_SLOT_R3)
-__device__ __forceinline__ int m16_slot(int row, int kg, int x) { return 2 * ((kg + 2 * ((row >> 3) & 1)) & 3) + (x ^ ((row >> 1) & 1)); }
-__device__ __forceinline__ int m16_chunk_of_slot(int row, int p) { return 2 * (((p >> 1) + 2 * ((row >> 3) & 1)) & 3) + ((p & 1) ^ ((row >> 1) & 1)); }
-#else
 __device__ __forceinline__ int m16_swz(int row) { return (row & 7) ^ ((row >> 3) & 1); }
 __device__ __forceinline__ int m16_slot(int row, int kg, int x) { return (2 * kg + x) ^ m16_swz(row); }
 // inverse, for the LDS-DMA source address: the chunk (2 kg + x) that lives in slot p of `row` (an XOR is its own inverse)
 __device__ __forceinline__ int m16_chunk_of_slot(int row, int p) { return p ^ m16_swz(row); }
-#endif
 
 // row of a 32x32 MFMA accumulator held in register v by lane-half h  (cdna_hip_programming.md section 3)
 __device__ __forceinline__ int acc_row(int v, int h) { return (v & 3) + 8 * (v >> 2) + 4 * h; }

@@ -183,17 +183,6 @@ static int gemm(const Ctx& c, const sm_gemm_args& g, bool out_s) {
     }
     return c.S ? sm_gemm_f16x2(&g, out_s ? 1 : 0, c.st) : sm_gemm_f32(&g, c.st);
 }
-// split mode, N = 384: C = R + (A W^T + b) in place on the residual stream AND the next pre-norm of it (F16X2) in one
-// launch on the 64 x 384 full-row tile (SM_EPI_RESIDUAL_LN)
-static int linear_residual_ln(const Ctx& c, const float* A, int lda, const float* W, const float* b, float* X, int64_t M, int K,
-                              const float* ln_w, const float* ln_b, float eps, float* Xn) {
-    sm_gemm_args g = {};
-    g.A = A; g.W = W; g.bias = b; g.C = X; g.R = X; g.C2 = Xn;
-    g.M = (int)M; g.N = SM_EMBED; g.K = K; g.lda = lda; g.ldw = K; g.ldc = SM_EMBED; g.ldr = SM_EMBED;
-    g.batch = 1; g.epilogue = SM_EPI_RESIDUAL_LN; g.ln_gamma = ln_w; g.ln_beta = ln_b; g.ln_eps = eps;
-    TapScope tap(c.st, "gemm_f16x2_kernel<64, 384, 2, 2, 4, 1, 0>", 2.0 * g.M * g.N * g.K, 0.0);
-    return sm_gemm_f16x2_tile(&g, 0, 64, 384, c.st);
-}
 // in split mode Q, K and V are F16X2 (written so by the projection GEMMs) and the f16 matrix cores do the work
 static int attn(const Ctx& c, sm_attn_args& a) {
     TapScope tap(c.st, c.S ? "attention_f16x2_kernel<4, false>" : "attention_f32_kernel", 4.0 * a.batch * a.heads * a.n_q * (double)a.n_k * SM_HEAD_DIM,
@@ -289,17 +278,14 @@ static int forward(const sm_weights* w, const sm_forward_io* io, float* wsbase, 
     }
 
     // ---- 12 pre-norm blocks (vision_transformer.py:164-170) -----------------------------------------------------
-    // Optional (split mode): the two pre-norms of a block ride on the GEMM that produces their input (proj -> norm2,
-    // fc2 -> the next block's norm1); only the first norm1 is then a launch of its own.
-    // SM_FUSED_LN (tuning build only, default 0): 1 = proj and fc2, 2 = proj only.  Measured with three batches in flight:
-    // 17.3k images/s against 18.0k unfused - the full-row tile needs 112 KiB of LDS (one workgroup per CU, 197 of them).
+    // (Split mode could carry the two pre-norms of a block on the GEMM that produces their input, on the 64 x 384 full-row tile
+    // of SM_EPI_RESIDUAL_LN.  Measured with three batches in flight: 17.3k images/s against 18.0k unfused - the full-row tile
+    // needs 112 KiB of LDS (one workgroup per CU, 197 of them).)
 #ifdef SM_TUNING
-    static const int fused_ln_env = getenv("SM_FUSED_LN") ? atoi(getenv("SM_FUSED_LN")) : 0;
     static const int fused_qkv_env = getenv("SM_FUSED_QKV") ? atoi(getenv("SM_FUSED_QKV")) : 1;
 #else
-    constexpr int fused_ln_env = 0, fused_qkv_env = 1;
+    constexpr int fused_qkv_env = 1;
 #endif
-    const bool fuse_proj = S && !c.W16 && fused_ln_env >= 1, fuse_fc2 = S && !c.W16 && fused_ln_env == 1;
     // W16 mode, token grids of <= 208 (ViT-S/16 at 224^2): the qkv projection and the attention are ONE launch
     // (qkv_attention.hip); SM_FUSED_QKV=0 (tuning build only) keeps the two-launch path (same results to rounding)
     // ... and at least 96 (image, head) workgroups: the fused kernel is one workgroup per pair with a ~30 us life, so a small batch
@@ -309,11 +295,6 @@ static int forward(const sm_weights* w, const sm_forward_io* io, float* wsbase, 
                            (io->attn_path == 1 || s.B * SM_HEADS >= 96);
     LnOpt xs;
     xs.ys = S ? ws.Xn : nullptr;  // LN output only feeds a GEMM: F16X2 in split mode
-#ifdef SM_TUNING  // timing-only ablation (tuning build): what the 24 encoder LayerNorm launches cost the pipeline (results are garbage)
-    static const int ablate_ln = getenv("SM_ABLATE_LN") ? atoi(getenv("SM_ABLATE_LN")) : 0;
-#else
-    constexpr int ablate_ln = 0;
-#endif
     // sm_weights.ln_fold: norm2 rides on proj -> fc1 and the next block's norm1 on fc2 -> qkv: the residual epilogues also write the
     // raw stream as F16X2 (into Xn) with its row statistics, the consuming GEMM carries the gain in its weights and applies
     // r (x W'^T - mu c) + b' in its epilogue.  Block 0's norm1 (its input comes from the patch embedding) stays a launch.
@@ -322,13 +303,12 @@ static int forward(const sm_weights* w, const sm_forward_io* io, float* wsbase, 
     // epilogues and the statistics cost more than 23 co-resident LayerNorm launches) - so it follows the same batch rule and the same
     // pin as the attention path (sm_forward_io.attn_path: 2 = the small-batch kernels, 1 = the large-batch ones).
     const bool lnf = c.W16 && w->ln_fold != 0 && io->attn_path != 1 && (io->attn_path == 2 || s.B * SM_HEADS < 96);
-    if (fuse_fc2) TRY(ln(c, ws.X, w->enc[0].norm1_w, w->enc[0].norm1_b, nullptr, s.M, 1e-6f, xs));
-    const bool split_fc2 = c.W16 && S && io->attn_path == 0 && s.M <= SM_SPLIT_FC2_ROWS && !fuse_fc2 && !ablate_ln;
+    const bool split_fc2 = c.W16 && S && io->attn_path == 0 && s.M <= SM_SPLIT_FC2_ROWS;
     for (int i = 0; i < SM_ENC_DEPTH; ++i) {
         const sm_enc_layer& e = w->enc[i];
         const bool n1_done = split_fc2 && i > 0;  // the previous block's split fc2 ended in this block's norm1
         const bool f1 = lnf && i > 0 && !n1_done;  // this block's norm1 is folded into its qkv projection
-        if (!fuse_fc2 && !f1 && !n1_done && !(ablate_ln && i > 0)) TRY(ln(c, ws.X, e.norm1_w, e.norm1_b, S ? nullptr : ws.Xn, s.M, 1e-6f, xs));
+        if (!f1 && !n1_done) TRY(ln(c, ws.X, e.norm1_w, e.norm1_b, S ? nullptr : ws.Xn, s.M, 1e-6f, xs));
         Fold fq;
         if (f1) { fq.stats = ws.ST; fq.cvec = e.qkv_c; fq.eps = 1e-6f; }
         const float* qkv_w = f1 ? e.qkv_fw : e.qkv_w;
@@ -352,22 +332,15 @@ static int forward(const sm_weights* w, const sm_forward_io* io, float* wsbase, 
             a.batch = s.B; a.heads = SM_HEADS; a.n_q = s.N; a.n_k = s.N; a.scale = 0.125f;
             TRY(attn(c, a));
         }
-        if (fuse_proj) {
-            TRY(linear_residual_ln(c, ws.AO, D, e.proj_w, e.proj_b, ws.X, s.M, D, e.norm2_w, e.norm2_b, 1e-6f, ws.Xn));
-        } else {
-            Fold fp;
-            if (lnf) { fp.xs = ws.Xn; fp.stats_out = ws.ST; }
-            TRY(linear(c, ws.AO, D, e.proj_w, e.proj_s, e.proj_b, ws.X, D, s.M, D, D, SM_EPI_RESIDUAL, ws.X, D, false, fp));
-            if (!lnf && !ablate_ln) TRY(ln(c, ws.X, e.norm2_w, e.norm2_b, S ? nullptr : ws.Xn, s.M, 1e-6f, xs));
-        }
+        Fold fp;
+        if (lnf) { fp.xs = ws.Xn; fp.stats_out = ws.ST; }
+        TRY(linear(c, ws.AO, D, e.proj_w, e.proj_s, e.proj_b, ws.X, D, s.M, D, D, SM_EPI_RESIDUAL, ws.X, D, false, fp));
+        if (!lnf) TRY(ln(c, ws.X, e.norm2_w, e.norm2_b, S ? nullptr : ws.Xn, s.M, 1e-6f, xs));
         Fold f2;
         if (lnf) { f2.stats = ws.ST; f2.cvec = e.fc1_c; f2.eps = 1e-6f; }
         TRY(linear(c, ws.Xn, D, lnf ? e.fc1_fw : e.fc1_w, lnf ? e.fc1_fs : e.fc1_s, lnf ? e.fc1_fb : e.fc1_b, ws.HID, SM_MLP, s.M, SM_MLP, D,
                    SM_EPI_GELU, nullptr, 0, S, f2));
-        if (fuse_fc2 && i + 1 < SM_ENC_DEPTH) {
-            const sm_enc_layer& nx = w->enc[i + 1];
-            TRY(linear_residual_ln(c, ws.HID, SM_MLP, e.fc2_w, e.fc2_b, ws.X, s.M, SM_MLP, nx.norm1_w, nx.norm1_b, 1e-6f, ws.Xn));
-        } else if (split_fc2 && i + 1 < SM_ENC_DEPTH) {
+        if (split_fc2 && i + 1 < SM_ENC_DEPTH) {
             const sm_enc_layer& nx = w->enc[i + 1];
             sm_gemm_args g = {};
             g.A = ws.HID; g.W = e.fc2_w; g.C = ws.PART; g.M = (int)s.M; g.N = D; g.K = SM_MLP; g.lda = SM_MLP;

@@ -25,7 +25,6 @@
 #include <type_traits>
 #include <mutex>
 #include <stdlib.h>
-#include <string.h>
 
 namespace sm {
 
@@ -44,7 +43,7 @@ __device__ __forceinline__ void wait_vmcnt_h() {
 // L2; activation panels come from HBM / the Infinity Cache with several times the latency, so the LDS that two
 // workgroups per CU leave free (2 x 80 of 160 KiB with the 128x128 tile) can buy the A stream one more K-tile of
 // run-ahead.  Measured with three batches in flight: 1 % SLOWER than AX = 0 (a CU whose LDS is full takes no workgroup
-// of another stream's kernel), so the shipped shapes use AX = 0; SM_F16X2_VARIANT=a3 selects the AX = 1 variant.
+// of another stream's kernel), so the shipped shapes use AX = 0.
 template <int BM, int BN, int NST, int NWM, int NWN, int MINB, int AX>
 __global__ __launch_bounds__(NWM * NWN * 64, MINB) void gemm_f16x2_kernel(sm_gemm_args g) {
     constexpr int NW = NWM * NWN, WTM = BM / NWM, WTN = BN / NWN;
@@ -141,21 +140,13 @@ __global__ __launch_bounds__(NWM * NWN * 64, MINB) void gemm_f16x2_kernel(sm_gem
 #pragma unroll
     for (int v = -(NSTA - 1); v < 0; ++v) issue_step(v);  // prologue = the virtual steps before kt = 0
 
-#ifdef SM_TUNING  // timing-only ablations exist only in the tuning build (build.py --tuning), never in the product library
-    const int ablate = g.patch_n <= -2 ? -g.patch_n : 0;  // 2 = no MFMA, 3 = no DMA in the loop, 4 = no epilogue, 5 = 3 + 4, 6 = 5 without the barrier
-#else
-    constexpr int ablate = 0;
-#endif
     for (int kt = 0; kt < nk; ++kt) {
-        if (ablate != 6) {
-            // tiles kt of both rings have landed; what may still fly was issued after the later of the two: AX = 0 the
-            // NST-2 steps since; AX = 1 the A tile issued right behind W(kt) plus those steps
-            wait_vmcnt_h<(NST - 2) * NI + AX * A_INST>();
-            __builtin_amdgcn_s_barrier();
-        }
+        // tiles kt of both rings have landed; what may still fly was issued after the later of the two: AX = 0 the
+        // NST-2 steps since; AX = 1 the A tile issued right behind W(kt) plus those steps
+        wait_vmcnt_h<(NST - 2) * NI + AX * A_INST>();
+        __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        if (ablate != 3 && ablate < 5) issue_step(kt);
-        if (ablate == 2) continue;
+        issue_step(kt);
         const char* sta = smemh + (kt % NSTA) * A_STAGE;
         const char* stw = smemh + W_RING + (kt % NST) * W_STAGE;
         // all fragment reads of the stage are issued up front: the second 16-k step's reads land under the first
@@ -189,7 +180,6 @@ __global__ __launch_bounds__(NWM * NWN * 64, MINB) void gemm_f16x2_kernel(sm_gem
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
     wait_vmcnt_h<0>();
-    if (ablate >= 4) return;  // timing-only: no epilogue
 
     float* C = g.C + (split > 1 ? (int64_t)blockIdx.z : bz) * g.strideC;
     const bool out_split = g.patch_n < 0;  // out-format flag travels in the sign of patch_n for non-PATCH epilogues
@@ -457,34 +447,20 @@ extern "C" int sm_gemm_f16x2_tile(const sm_gemm_args* g, int out_f16x2, int bm, 
                    "sm_gemm_f16x2: bad split_k");
     sm_gemm_args a = *g;
     if (out_f16x2) a.patch_n = -1;
-#ifdef SM_TUNING
-    if (const char* ab = getenv("SM_F16X2_ABLATE")) a.patch_n = -atoi(ab);  // timing-only (wrong results): tuning build only
-#endif
     hipStream_t st = (hipStream_t)stream;
-    // Occupancy is what this kernel lives on (scripts/gemm_f16x2_ablate.py): the DMA stream, the MFMA stream and the
-    // epilogue of one workgroup only overlap with those of OTHER workgroups on the CU, so the default shapes are the
-    // ones that fit three workgroups per CU - 48 KiB of LDS and, via __launch_bounds__(256, 3), <= 168 registers
-    // (left alone hipcc spends 109 VGPR + 64 AGPR on the 128x64 tile = two per CU, and the kernel is 25 % slower).
-    // tuning knobs (tuning build only): SM_F16X2_NST = ring depth (2..5 where instantiated), SM_F16X2_VARIANT = "a3" (128x128, four waves,
-    // the A ring one tile deeper), "w4" (128x128 as four waves of 64x64), "w16" (256x128 as sixteen waves of 64x32)
-#ifdef SM_TUNING
-    const char* env = getenv("SM_F16X2_NST");
-    const int nst = env ? atoi(env) : 0;
-    const char* var = getenv("SM_F16X2_VARIANT");
-#else
-    constexpr int nst = 0;
-    const char* var = nullptr;
-#endif
-    const bool var_a3 = var && !strcmp(var, "a3"), var_w4 = var && !strcmp(var, "w4");
+    // Occupancy is what this kernel lives on (round 1: timing runs with the MFMAs, the in-loop DMA or the epilogue removed in
+    // turn): the DMA stream, the MFMA stream and the epilogue of one workgroup only overlap with those of OTHER workgroups on
+    // the CU, so the default shapes are the ones that fit three workgroups per CU - 48 KiB of LDS and, via
+    // __launch_bounds__(256, 3), <= 168 registers (left alone hipcc spends 109 VGPR + 64 AGPR on the 128x64 tile = two per
+    // CU, and the kernel is 25 % slower).
+    // (Deeper rings, the 128x128 tile as four waves of 64x64 (-2.7 % end to end) or with the A ring one tile deeper (AX = 1:
+    // -1 %) and 256x128 as sixteen waves were measured and not kept.)
     if (bm == 64 && bn == 384) return sm::launch_gemm_h<64, 384, 2, 2, 4, 1, 0>(a, st);  // full-row tile (LayerNorm epilogue)
-    if (bm == 256 && bn == 128 && var && !strcmp(var, "w16")) return sm::launch_gemm_h<256, 128, 2, 4, 4, 1, 0>(a, st);  // 16 waves of 64x32
-    if (bm == 256 && bn == 128) return nst == 2 ? sm::launch_gemm_h<256, 128, 2, 4, 2>(a, st) : sm::launch_gemm_h<256, 128, 3, 4, 2>(a, st);
-    if (bm == 256 && bn == 64) return nst == 3 ? sm::launch_gemm_h<256, 64, 3, 4, 1>(a, st) : sm::launch_gemm_h<256, 64, 2, 4, 1>(a, st);
-    if (bm == 128 && bn == 128 && var_a3) return sm::launch_gemm_h<128, 128, 2, 2, 2, 2, 1>(a, st);  // 80 KiB: -1 % end to end
-    if (bm == 128 && bn == 128 && var_w4) return sm::launch_gemm_h<128, 128, 2, 2, 2, 2, 0>(a, st);  // -2.7 % end to end
-    if (bm == 128 && bn == 128) return nst == 3 ? sm::launch_gemm_h<128, 128, 3>(a, st) : nst == 4 ? sm::launch_gemm_h<128, 128, 4>(a, st) : sm::launch_gemm_h<128, 128, 2, 2, 4, 2, 0>(a, st);
-    if (bm == 128 && bn == 64) return nst == 3 ? sm::launch_gemm_h<128, 64, 3>(a, st) : nst == 4 ? sm::launch_gemm_h<128, 64, 4>(a, st) : sm::launch_gemm_h<128, 64, 2, 2, 2, 3>(a, st);
-    if (bm == 64 && bn == 64) return nst == 4 ? sm::launch_gemm_h<64, 64, 4>(a, st) : nst == 5 ? sm::launch_gemm_h<64, 64, 5>(a, st) : nst == 2 ? sm::launch_gemm_h<64, 64, 2, 2, 2, 5>(a, st) : sm::launch_gemm_h<64, 64, 3, 2, 2, 3>(a, st);
+    if (bm == 256 && bn == 128) return sm::launch_gemm_h<256, 128, 3, 4, 2>(a, st);
+    if (bm == 256 && bn == 64) return sm::launch_gemm_h<256, 64, 2, 4, 1>(a, st);
+    if (bm == 128 && bn == 128) return sm::launch_gemm_h<128, 128, 2, 2, 4, 2, 0>(a, st);
+    if (bm == 128 && bn == 64) return sm::launch_gemm_h<128, 64, 2, 2, 2, 3>(a, st);
+    if (bm == 64 && bn == 64) return sm::launch_gemm_h<64, 64, 3, 2, 2, 3>(a, st);
     sm::set_error("sm_gemm_f16x2_tile: unsupported tile %dx%d", bm, bn);
     return SM_EINVAL;
 }

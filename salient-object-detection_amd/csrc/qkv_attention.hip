@@ -22,322 +22,19 @@
 // LDS: one workgroup per CU owns all 160 KiB.  During phase 1 it is the ring (2 x 52 KiB); after the last stage (one barrier)
 // the same memory becomes K (224 x 256 B) + V^T (64 x 896 B).  N <= 208 tokens: the ViT-S/16 224^2 headline shape (197);
 // larger grids take the unfused path (K and V of one head no longer fit: 785 tokens x 256 B x 2 = 392 KiB).
-// The 32x32x16 form of round 2 (qkv_attention_kernel<KT, NST>), the all-waves-load form and the three-slot ring live in the
-// tuning build only (measured: DESIGN.md section 5).
+// The 32x32x16 form of round 2, the all-waves-load form and the three-slot ring were measured and rejected.
 #include "common.h"
 #include <type_traits>
 #include <math.h>
 #include <mutex>
 #include <stdlib.h>
-#include <string.h>
 
 namespace sm {
 
 constexpr int QA_WAVES = 7;
 constexpr int QA_TOK = QA_WAVES * 32;        // 224 token rows staged per K-stage (rows past N repeat the last token)
-constexpr int QA_KROWS = 208;                // keys kept in LDS (13 MFMA steps of 16 keys)
-constexpr int QA_K_BYTES = QA_KROWS * 256;   // 53248
-constexpr int QA_VLD = 208 * 4 + 16;         // bytes per head-dim row of V^T (+16: b128 reads of 16 rows hit 16 slots)
-constexpr int QA_V_BYTES = 64 * QA_VLD;      // 54272
+constexpr int QA_KROWS = 208;                // most tokens (keys) a launch takes: 13 MFMA steps of 16 keys
 constexpr int QA_LDS = 160 * 1024;           // the whole LDS of a CU (one workgroup per CU)
-static_assert(QA_K_BYTES + QA_V_BYTES <= QA_LDS, "K and V^T overlay the ring");
-
-#ifdef SM_TUNING  // the v_mfma_f32_32x32x16_f16 form (round 2, first half): 77-78 us against 65 us for what ships
-// KT = k per ring stage: 32 -> a stage row is one full 128-B line (8 rows per 1-KiB LDS-DMA piece), 16 -> 64-B half lines
-// (16 rows per piece).  NST = ring stages.  Stage = [224 Xn rows | 192 weight rows] x KT * 4 bytes.
-template <int KT, int NST>
-__global__ __launch_bounds__(QA_WAVES * 64, 2) void qkv_attention_kernel(sm_qkv_attn_args a) {
-    constexpr int ROWB = KT * 4, CH = KT / 4, RPP = 1024 / ROWB, KS = KT / 16;
-    constexpr int XT = QA_TOK * ROWB, WT = 192 * ROWB, STAGE = XT + WT;
-    constexpr int XP = XT / 1024, NP = STAGE / 1024;                  // Xn pieces / all pieces per stage
-    constexpr int PPW = (NP + QA_WAVES - 1) / QA_WAVES;               // pieces per wave, the same immediate in every wave: the
-    constexpr int DUMP = NST * STAGE;                                 // surplus ("filler") pieces land in a dump zone behind the ring
-    static_assert(DUMP + (PPW * QA_WAVES - NP) * 1024 <= QA_LDS, "ring + dump zone must fit in LDS");
-    extern __shared__ __attribute__((aligned(16))) char smq[];
-    const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)smq;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = lane & 31, h = lane >> 5;
-    // (image, head) of this workgroup: ids 8 apart share an XCD (round-robin dispatch), so the six heads of an image run
-    // on one XCD back to back and five of them find the image's Xn rows in that L2
-    int head, b;
-    {
-        const int id = blockIdx.x, pairs = a.B * SM_HEADS;
-        int lin = id;
-        if ((pairs & 7) == 0) lin = (id & 7) * (pairs >> 3) + (id >> 3);
-        b = lin / SM_HEADS;
-        head = lin - b * SM_HEADS;
-    }
-    const int N = a.N;
-    const char* X = reinterpret_cast<const char*>(a.Xn + (int64_t)b * N * a.ldx);
-    const char* W = reinterpret_cast<const char*>(a.Wqkv);
-    auto swz = [](int row) { return KT == 32 ? (row >> 1) & 7 : (row >> 2) & 3; };
-
-    // ---- ring fill: piece p of a stage = RPP rows; p < XP: Xn rows, else weight rows; dealt round-robin over the waves.
-    // Lane l fetches chunk (l % CH) ^ swz(row) of row l / CH.
-    const char* src[PPW];
-#pragma unroll
-    for (int j = 0; j < PPW; ++j) {
-        const int p = wave + QA_WAVES * j;
-        const int prow = lane / CH;
-        if (p < XP) {
-            const int row = p * RPP + prow;
-            const int c = (lane % CH) ^ swz(row);
-            const int tok = row < N ? row : N - 1;
-            src[j] = X + (int64_t)tok * a.ldx * 4 + c * 16;
-        } else {
-            const int row = ((p < NP ? p : XP) - XP) * RPP + prow;  // 0..191: [Q dims | K dims | V dims] of this head
-            const int c = (lane % CH) ^ swz(row);
-            const int wrow = (row >> 6) * SM_EMBED + head * SM_HEAD_DIM + (row & 63);
-            src[j] = W + (int64_t)wrow * SM_EMBED * 4 + c * 16;
-        }
-    }
-    auto issue = [&](int kt, int slot) {
-#pragma unroll
-        for (int j = 0; j < PPW; ++j) {
-            const int p = wave + QA_WAVES * j;
-            const unsigned d = p < NP ? lds0 + slot * STAGE + p * 1024 : lds0 + DUMP + (p - NP) * 1024;  // fillers: dump zone
-            lds_dma16(src[j] + kt * ROWB, __builtin_amdgcn_readfirstlane(d));
-        }
-    };
-
-    // fragment offsets inside a stage row: k16 step s, lane half h -> k-group 2s+h -> chunks 2(2s+h) (hi), +1 (lo)
-    const int xrow = wave * 32 + r;
-    int x_hi[KS], x_lo[KS], w_hi[KS], w_lo[KS];
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-        x_hi[s] = xrow * ROWB + (((2 * (2 * s + h)) ^ swz(xrow)) * 16);
-        x_lo[s] = xrow * ROWB + (((2 * (2 * s + h) + 1) ^ swz(xrow)) * 16);
-        w_hi[s] = XT + r * ROWB + (((2 * (2 * s + h)) ^ swz(r)) * 16);   // weight rows 32 blk + r: swz does not depend on blk
-        w_lo[s] = XT + r * ROWB + (((2 * (2 * s + h) + 1) ^ swz(r)) * 16);
-    }
-
-    f32x16 acc[6];  // [Q d0-31, Q d32-63, K d0-31, K d32-63, V d0-31, V d32-63]
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int v = 0; v < 16; ++v) acc[i][v] = 0.f;
-    const f16x8 down = {(_Float16)0.00048828125f, (_Float16)0.00048828125f, (_Float16)0.00048828125f, (_Float16)0.00048828125f,
-                        (_Float16)0.00048828125f, (_Float16)0.00048828125f, (_Float16)0.00048828125f, (_Float16)0.00048828125f};  // 2^-11
-
-    constexpr int NKT = SM_EMBED / KT;
-#pragma unroll
-    for (int t = 0; t < NST - 1; ++t) issue(t, t);
-    for (int kt = 0; kt < NKT; ++kt) {
-        // stage kt has landed (this wave's pieces): all but the NST - 2 younger stages' pieces are done
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NST - 2) * PPW) : "memory");
-        __builtin_amdgcn_s_barrier();  // ... for every wave; every wave is done with stage kt-1, whose slot is refilled now
-        __builtin_amdgcn_sched_barrier(0);
-        {   // stages past the end re-fetch the last one, so that every iteration issues the same number of pieces
-            const int t = kt + NST - 1;
-            issue(t < NKT ? t : NKT - 1, t % NST);
-        }
-        const char* st = smq + (kt % NST) * STAGE;
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-            const f16x8 ah = *reinterpret_cast<const f16x8*>(st + x_hi[s]);
-            const f16x8 al = *reinterpret_cast<const f16x8*>(st + x_lo[s]);
-            f16x8 wh[6], wl[6];
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                wh[i] = *reinterpret_cast<const f16x8*>(st + w_hi[s] + i * 32 * ROWB);
-                wl[i] = *reinterpret_cast<const f16x8*>(st + w_lo[s] + i * 32 * ROWB);
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {  // Q^T, K^T: D[dim][token]
-                const f16x8 whs = wh[i] * down;
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[i], ah, acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[i], ah, acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(whs, al, acc[i], 0, 0, 0);
-            }
-#pragma unroll
-            for (int i = 4; i < 6; ++i) {  // V: D[token][dim]
-                const f16x8 whs = wh[i] * down;
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wh[i], acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wl[i], acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, whs, acc[i], 0, 0, 0);
-            }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
-
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();  // every DMA has landed and every wave has read its last stage: the ring becomes K / V^T
-
-    // ---- accumulators -> Q fragments (registers), K and V^T (LDS) ---------------------------------------------------------
-    const float ws = a.w_scale;
-    const float* bq = a.bias + head * SM_HEAD_DIM;
-    const float* bk = bq + SM_EMBED;
-    const float* bv = bk + SM_EMBED;
-    const int key = wave * 32 + r;  // the token this lane holds as a key (Q^T / K^T blocks) ...
-    f16x8 qh[4], ql[4];             // step t = 2 db + s: dims 32 db + 16 s + 8 (j >> 2) + 4 h + (j & 3)
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            f16x8 kh8, kl8;
-            float qf[8], kf[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int d = db * 32 + acc_row(8 * s + j, h);
-                qf[j] = acc[db][8 * s + j] * ws + bq[d];
-                kf[j] = acc[2 + db][8 * s + j] * ws + bk[d];
-            }
-            split8(qf, qh[2 * db + s], ql[2 * db + s]);
-            split8(kf, kh8, kl8);
-            if (key < QA_KROWS) {  // K row of this key: chunk 2 (4 db + 2 s + h) (+1 = lo), XOR-ed with key & 15
-                const int c = 2 * (4 * db + 2 * s + h);
-                *reinterpret_cast<f16x8*>(smq + key * 256 + ((c ^ (key & 15)) * 16)) = kh8;
-                *reinterpret_cast<f16x8*>(smq + key * 256 + (((c + 1) ^ (key & 15)) * 16)) = kl8;
-            }
-        }
-#pragma unroll
-    for (int db = 0; db < 2; ++db) {  // ... and the head-dim it holds in the V blocks: rows = this wave's 32 tokens
-        const int d = db * 32 + r;
-        const float bias = bv[d];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            if (wave * 32 + 16 * u < QA_KROWS) {
-                f16x8 vh8, vl8;
-                float vf[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) vf[j] = acc[4 + db][8 * u + j] * ws + bias;
-                split8(vf, vh8, vl8);
-                char* p = smq + QA_K_BYTES + d * QA_VLD + wave * 128 + u * 64 + h * 32;
-                *reinterpret_cast<f16x8*>(p) = vh8;
-                *reinterpret_cast<f16x8*>(p + 16) = vl8;
-            }
-        }
-    }
-    __syncthreads();  // K and V^T of the head are complete
-
-    // ---- attention: this wave's 32 queries against all keys --------------------------------------------------------------
-    const int q0 = wave * 32;
-    if (q0 >= N) return;
-    const float cs = a.scale * 1.44269504088896340736f;  // scores in log2 units
-    const int nsteps16 = (N + 15) >> 4;                  // 16-key MFMA steps that hold at least one real key
-    f32x16 om[2], oc[2];
-#pragma unroll
-    for (int v = 0; v < 16; ++v) { om[0][v] = 0.f; om[1][v] = 0.f; oc[0][v] = 0.f; oc[1][v] = 0.f; }
-    float m_run = -INFINITY, l_run = 0.f;
-    const int ksw = r & 15;
-    int k_hi[4], k_lo[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        k_hi[t] = ((2 * (2 * t + h)) ^ ksw) * 16;
-        k_lo[t] = ((2 * (2 * t + h) + 1) ^ ksw) * 16;
-    }
-    const char* Vt = smq + QA_K_BYTES + r * QA_VLD + h * 32;  // + db * 32 rows, + kb * 128 + u * 64
-    const int nch = (N + 63) >> 6;
-    for (int c = 0; c < nch; ++c) {
-        const int ck = min(64, N - c * 64);
-        const int nb2 = (ck + 31) >> 5;
-        f32x16 s[2];
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-            for (int v = 0; v < 16; ++v) s[kb][v] = -INFINITY;
-            if (kb < nb2) {
-                f32x16 mn, cr;
-#pragma unroll
-                for (int v = 0; v < 16; ++v) { mn[v] = 0.f; cr[v] = 0.f; }
-                const char* kr = smq + (c * 64 + kb * 32 + r) * 256;
-                f16x8 kh[4], kl[4];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    kh[t] = *reinterpret_cast<const f16x8*>(kr + k_hi[t]);
-                    kl[t] = *reinterpret_cast<const f16x8*>(kr + k_lo[t]);
-                }
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    mn = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh[t], qh[t], mn, 0, 0, 0);
-                    cr = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh[t], ql[t], cr, 0, 0, 0);
-                    cr = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl[t], qh[t], cr, 0, 0, 0);
-                }
-#pragma unroll
-                for (int v = 0; v < 16; ++v) s[kb][v] = fmaf(cr[v], 1.0f / 2048.0f, mn[v]);
-                if ((kb + 1) * 32 > ck) {  // keys past N: rows >= 208 alias other LDS data, rows 197..207 repeat a token
-#pragma unroll
-                    for (int v = 0; v < 16; ++v)
-                        if (kb * 32 + acc_row(v, h) >= ck) s[kb][v] = -INFINITY;
-                }
-            }
-        }
-        float cmax = -INFINITY;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) cmax = fmaxf(cmax, s[kb][v]);
-        cmax = halves_max(cmax);
-        const float lim = 8.0f / cs;  // lazy running maximum (attention_f16x2.hip): p <= 2^8 between moves
-        if (__builtin_amdgcn_ballot_w64(cmax > m_run + lim) != 0) {
-            const float m_new = fmaxf(m_run, cmax);
-            const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * cs);
-            m_run = m_new;
-            l_run *= alpha;
-#pragma unroll
-            for (int v = 0; v < 16; ++v) { om[0][v] *= alpha; om[1][v] *= alpha; oc[0][v] *= alpha; oc[1][v] *= alpha; }
-        }
-        const float moff = -m_run * cs;
-        float psum = 0.f;
-        f16x8 ph[2][2], pl[2][2];
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                float pf[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    pf[j] = __builtin_amdgcn_exp2f(fmaf(s[kb][8 * u + j], cs, moff));
-                    psum += pf[j];
-                }
-                split8(pf, ph[kb][u], pl[kb][u]);
-            }
-        l_run += psum;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                if ((c * 2 + kb) * 2 + u < nsteps16) {  // wave-uniform: steps past the last real key hold no V data
-                    const char* vp = Vt + (c * 2 + kb) * 128 + u * 64;
-#pragma unroll
-                    for (int db = 0; db < 2; ++db) {
-                        const f16x8 vh = *reinterpret_cast<const f16x8*>(vp + db * 32 * QA_VLD);
-                        const f16x8 vl = *reinterpret_cast<const f16x8*>(vp + db * 32 * QA_VLD + 16);
-                        om[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, ph[kb][u], om[db], 0, 0, 0);
-                        oc[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, pl[kb][u], oc[db], 0, 0, 0);
-                        oc[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, ph[kb][u], oc[db], 0, 0, 0);
-                    }
-                }
-            }
-    }
-
-    const float l = halves_sum(l_run);
-    const float inv = 1.0f / l;
-    if (q0 + r < N) {
-        float* Orow = a.O + ((int64_t)b * N + q0 + r) * a.ldo;
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int g = 0; g < 4; g += 2) {
-                float x[4], y[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    x[e] = (om[db][4 * g + e] + oc[db][4 * g + e] * (1.0f / 2048.0f)) * inv;
-                    y[e] = (om[db][4 * g + 4 + e] + oc[db][4 * g + 4 + e] * (1.0f / 2048.0f)) * inv;
-                }
-                if (a.out_f16x2) {
-                    pair_groups(x, y);
-                    store_f16x2_8(Orow, head * SM_HEAD_DIM + db * 32 + 8 * (g + h), x, y);
-                } else {
-                    const int d = head * SM_HEAD_DIM + db * 32 + 8 * g + 4 * h;
-                    *reinterpret_cast<float4*>(Orow + d) = make_float4(x[0], x[1], x[2], x[3]);
-                    *reinterpret_cast<float4*>(Orow + d + 8) = make_float4(y[0], y[1], y[2], y[3]);
-                }
-            }
-    }
-}
-#endif  // SM_TUNING
 
 // ---- the kernel on v_mfma_f32_16x16x32_f16 ----------------------------------------------------------------------------------
 // Less energy per FLOP at the chip's power limit (gemm_w16.hip, 16x16x32 variant) and 16-row granularity.  The operand
@@ -757,25 +454,9 @@ __global__ __launch_bounds__(QA_WAVES * 64, 2) void qkv_attention_m16_kernel(sm_
 
 }  // namespace sm
 
-// kernel selection.  Product: qkv_attention_m16_kernel<2, 3, 4> (or <2, 1, 4>: the throughput-mode diagnostic).  Tuning build:
-// SM_QKV_RING = "m16x2L4" (default) | "m16x2" (every wave feeds the ring: round 2) | "m16x3L4" | "m16x3" | "32x2" | "32x3" |
-// "16x2" | "16x6" (the 32x32x16-MFMA kernel, "<k per stage>x<stages>") - same results up to summation order.
-static int qkv_mode() {
-#ifdef SM_TUNING
-    static const char* ring = getenv("SM_QKV_RING");
-    return !ring ? 6 : !strcmp(ring, "32x3") ? 1 : !strcmp(ring, "16x2") ? 2 : !strcmp(ring, "16x6") ? 3 : !strcmp(ring, "32x2") ? 0 :
-           !strcmp(ring, "m16x3") ? 5 : !strcmp(ring, "m16x2") ? 4 : !strcmp(ring, "m16x3L4") ? 7 : 6;
-#else
-    return 6;
-#endif
-}
 // name rocprofv3 reports for the selected kernel (labels the in-situ taps of forward.hip)
 const char* sm_qkv_attention_kernel_name(int mfma_terms) {
-    if (mfma_terms == 1) return "qkv_attention_m16_kernel<2, 1, 4>";  // the one-MFMA diagnostic launches this instantiation whatever the mode
-    static const char* names[] = {"qkv_attention_kernel<32, 2>", "qkv_attention_kernel<32, 3>", "qkv_attention_kernel<16, 2>",
-                                  "qkv_attention_kernel<16, 6>", "qkv_attention_m16_kernel<2>", "qkv_attention_m16_kernel<3>",
-                                  "qkv_attention_m16_kernel<2, 3, 4>", "qkv_attention_m16_kernel<3, 3, 4>"};
-    return names[qkv_mode()];
+    return mfma_terms == 1 ? "qkv_attention_m16_kernel<2, 1, 4>" : "qkv_attention_m16_kernel<2, 3, 4>";
 }
 
 extern "C" int sm_qkv_attention_max_tokens(void) { return sm::QA_KROWS; }
@@ -796,18 +477,10 @@ extern "C" int sm_qkv_attention_w16(const sm_qkv_attn_args* a, void* stream) {
                "sm_qkv_attention_w16: row strides must be multiples of 8 elements, pointers 32-B aligned");
     static std::once_flag attr_once;
     std::call_once(attr_once, [] {
-        const void* ks[] = {reinterpret_cast<const void*>(&sm::qkv_attention_m16_kernel<2, 3, 4>), reinterpret_cast<const void*>(&sm::qkv_attention_m16_kernel<2, 1, 4>),
-#ifdef SM_TUNING
-                            reinterpret_cast<const void*>(&sm::qkv_attention_kernel<32, 2>), reinterpret_cast<const void*>(&sm::qkv_attention_kernel<32, 3>),
-                            reinterpret_cast<const void*>(&sm::qkv_attention_kernel<16, 2>), reinterpret_cast<const void*>(&sm::qkv_attention_kernel<16, 6>),
-                            reinterpret_cast<const void*>(&sm::qkv_attention_m16_kernel<2>),
-                            reinterpret_cast<const void*>(&sm::qkv_attention_m16_kernel<3, 3, 4>),
-#endif
-        };
+        const void* ks[] = {reinterpret_cast<const void*>(&sm::qkv_attention_m16_kernel<2, 3, 4>), reinterpret_cast<const void*>(&sm::qkv_attention_m16_kernel<2, 1, 4>)};
         for (const void* k : ks) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, sm::QA_LDS);
         (void)hipGetLastError();
     });
-    const int mode = qkv_mode();
     const dim3 grid(a->B * SM_HEADS), block(sm::QA_WAVES * 64);
     hipStream_t st = (hipStream_t)stream;
     sm_qkv_attn_args args = *a;
@@ -818,16 +491,7 @@ extern "C" int sm_qkv_attention_w16(const sm_qkv_attn_args* a, void* stream) {
 #endif
     a = &args;
     if (a->mfma_terms == 1) hipLaunchKernelGGL((sm::qkv_attention_m16_kernel<2, 1, 4>), grid, block, sm::QA_LDS, st, *a);
-    else if (mode == 6) hipLaunchKernelGGL((sm::qkv_attention_m16_kernel<2, 3, 4>), grid, block, sm::QA_LDS, st, *a);
-#ifdef SM_TUNING
-    else if (mode == 4) hipLaunchKernelGGL((sm::qkv_attention_m16_kernel<2>), grid, block, sm::QA_LDS, st, *a);
-    else if (mode == 5) { sm::set_error("sm_qkv_attention_w16: SM_QKV_RING=m16x3 was retired (use m16x3L4)"); return SM_EINVAL; }
-    else if (mode == 7) hipLaunchKernelGGL((sm::qkv_attention_m16_kernel<3, 3, 4>), grid, block, sm::QA_LDS, st, *a);
-    else if (mode == 1) hipLaunchKernelGGL((sm::qkv_attention_kernel<32, 3>), grid, block, sm::QA_LDS, st, *a);
-    else if (mode == 2) hipLaunchKernelGGL((sm::qkv_attention_kernel<16, 2>), grid, block, sm::QA_LDS, st, *a);
-    else if (mode == 3) hipLaunchKernelGGL((sm::qkv_attention_kernel<16, 6>), grid, block, sm::QA_LDS, st, *a);
-    else hipLaunchKernelGGL((sm::qkv_attention_kernel<32, 2>), grid, block, sm::QA_LDS, st, *a);
-#endif
+    else hipLaunchKernelGGL((sm::qkv_attention_m16_kernel<2, 3, 4>), grid, block, sm::QA_LDS, st, *a);
     return sm::check_launch("sm_qkv_attention_w16");
 }
 

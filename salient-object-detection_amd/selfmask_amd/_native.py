@@ -6,8 +6,8 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# SM_HIP_LIB points the binding at another build of the same ABI - the tuning build with the timing-only ablation
-# switches (build.py --tuning -> lib/libselfmask_hip_tuning.so), used by scripts/*_ablate.py only
+# SM_HIP_LIB points the binding at another build of the same ABI - the tuning build (build.py --tuning ->
+# lib/libselfmask_hip_tuning.so: path forcings and in-kernel stamps) or an experiment build (build.py --variant=NAME)
 LIB_PATH = os.environ.get("SM_HIP_LIB") or os.path.normpath(os.path.join(_HERE, "..", "lib", "libselfmask_hip.so"))
 
 EMBED, HEADS, HEAD_DIM, MLP, ENC_DEPTH, MAX_DEC_LAYERS = 384, 6, 64, 1536, 12, 8

@@ -50,7 +50,7 @@ xn = torch.randn(64 * 197, 384, device=dev)
 wq = torch.randn(1152, 384, device=dev) * 0.05
 bq = torch.zeros(1152, device=dev)
 probe(lambda: None if torch.cuda._sleep(100000) else None, "idle (a sleep kernel on the main stream)")
-probe(lambda: ops.gemm_w16(a, w16, ws, b, variant=2, out=c, out_f16x2=True), "W16 qkv GEMM 128x128, random operands")
-probe(lambda: ops.gemm_w16(az, w16z, wsz, bz, variant=2, out=cz, out_f16x2=True), "W16 qkv GEMM 128x128, zero operands")
-probe(lambda: ops.gemm_w16(a, w16, ws, b, variant=31, out=c, out_f16x2=True), "W16 qkv GEMM 256x128 deep ring, random")
+probe(lambda: ops.gemm_w16(a, w16, ws, b, variant=42, out=c, out_f16x2=True), "W16 qkv GEMM 128x128, random operands")
+probe(lambda: ops.gemm_w16(az, w16z, wsz, bz, variant=42, out=cz, out_f16x2=True), "W16 qkv GEMM 128x128, zero operands")
+probe(lambda: ops.gemm_w16(a, w16, ws, b, variant=47, out=c, out_f16x2=True), "W16 qkv GEMM 256x128 ring of three, random")
 probe(lambda: ops.qkv_attention(xn, wq, bq, 64), "fused QKV+attention (incl. its split kernels)")

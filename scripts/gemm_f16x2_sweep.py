@@ -17,7 +17,6 @@ def t(fn, it=20):
 B = 64; M = B * 197
 shapes = [("qkv", M, 1152, 384, N.EPI_BIAS), ("proj", M, 384, 384, N.EPI_RESIDUAL), ("fc1", M, 1536, 384, N.EPI_GELU),
           ("fc2", M, 384, 1536, N.EPI_RESIDUAL), ("dec_small", B * 20, 384, 384, N.EPI_BIAS)]
-print("SM_F16X2_NST =", os.environ.get("SM_F16X2_NST"))
 torch.manual_seed(0)
 for name, m, n, k, epi in shapes:
     a = torch.randn(m, k, device="cuda"); w = torch.randn(n, k, device="cuda") * 0.05; b = torch.randn(n, device="cuda")

@@ -3,7 +3,6 @@
 interleaved rounds in one process (median of rounds).  Prints us per launch and issued-MFMA TFLOP/s."""
 import os, sys, statistics
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-os.environ.setdefault("SM_HIP_LIB", os.path.join(REPO, "salient-object-detection_amd", "lib", "libselfmask_hip_tuning.so"))  # the variant knobs live in the tuning build
 sys.path[:0] = [os.path.join(REPO, "salient-object-detection_amd"), REPO]
 import torch
 from selfmask_amd import ops, _native as N
@@ -13,7 +12,7 @@ M = int(os.environ.get("M", 12608))
 SHAPES = [("qkv", 1152, 384, N.EPI_BIAS, True, False), ("proj", 384, 384, N.EPI_RESIDUAL, False, True),
           ("fc1", 1536, 384, N.EPI_GELU, True, False), ("fc2", 384, 1536, N.EPI_RESIDUAL, False, True),
           ("kv", 4608, 384, N.EPI_BIAS, True, False)]
-VARIANTS = [int(v) for v in os.environ.get("VARIANTS", "2,7,30,31,32,33,34,35").split(",")]
+VARIANTS = [int(v) for v in os.environ.get("VARIANTS", "40,42,43,44,45,47").split(",")]
 ROUNDS, ITERS = 7, 20
 
 

@@ -1,9 +1,8 @@
 #!/usr/bin/env python3
 """Fused QKV+attention kernel vs the two launches it replaces (W16 qkv GEMM + F16X2 attention), B = 64, N = 197, one stream,
-median of interleaved rounds.  Run once per SM_QKV_RING value (2, 3, 6): the ring depth is read once per process."""
+median of interleaved rounds."""
 import os, sys, statistics
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-os.environ.setdefault("SM_HIP_LIB", os.path.join(REPO, "salient-object-detection_amd", "lib", "libselfmask_hip_tuning.so"))  # the variant knobs live in the tuning build
 sys.path[:0] = [os.path.join(REPO, "salient-object-detection_amd"), REPO]
 import torch
 from selfmask_amd import ops, _native as N
@@ -51,4 +50,4 @@ for _ in range(9):
 flops = B * (2.0 * n * 384 * 1152 + 4.0 * n * n * 384)
 for k, v in t.items():
     m = statistics.median(v)
-    print(f"SM_QKV_RING={os.environ.get('SM_QKV_RING', '2')} {k:28s} {m:7.1f} us (min {min(v):6.1f})  {flops / m / 1e6:6.1f} TFLOP/s alg, {3 * flops / m / 1e6:6.1f} issued")
+    print(f"{k:28s} {m:7.1f} us (min {min(v):6.1f})  {flops / m / 1e6:6.1f} TFLOP/s alg, {3 * flops / m / 1e6:6.1f} issued")

@@ -34,7 +34,7 @@ d = np.diff(t[:, :, :7], axis=2)
 names = ["prologue (first stage lands)", "projection loop (12 stages)", "drain + barrier", "convert Q/K/V^T + barrier",
          "attention loop (7 steps)", "normalise + store"]
 tot = t[:, :, 6] - t[:, :, 0]
-print(f"kernel {os.environ.get('SM_QKV_RING', 'm16x2')}: s_memtime ticks, median over {WG} workgroups")
+print(f"qkv_attention_m16_kernel<2, 3, 4>: s_memtime ticks, median over {WG} workgroups")
 print(" phases: " + " | ".join(names))
 for w in range(WAVES):
     print(f" wave {w}: " + "  ".join(f"{np.median(d[:, w, i]):8.0f}" for i in range(6)) + f"   total {np.median(tot[:, w]):8.0f}")
