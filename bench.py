@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: images/sec of the SelfMask inference hot path (ViT-S/16, 224^2, nq=20, batch 64 per GPU).
 
-    python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run, one rank/GPU)
+    python bench.py --gpus N --steps K --warmup W [--full]   (N>1: launched by torch.distributed.run, one rank/GPU)
 
 A "step" is one evaluator iteration - MaskFormer.forward + mask post-processing + the 14 metrics - over one batch of
 synthetic images already resident in HBM (weights = synthetic checkpoint seed 0; there is no dataset or checkpoint
@@ -10,7 +10,8 @@ the shipped Evaluator does.  Images shard across ranks with no data-path collect
 is the evaluator's end-of-run all-gather of per-image result rows (RCCL), issued once after the K steps inside the
 timed region.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: it sets up, warms up, times the K steps,
+writes --dump-outputs and prints the driver's contract (images/s, ms_per_step, ...).  --full adds
   roofline      - the kernel holding the largest share of the forward, timed in situ: HIP events around each of its
                   launches on the launch stream inside real forwards (sm_forward_timing); `traffic` = HBM bytes per launch
                   from the committed PMC passes, quoted only if they were taken on exactly these kernel sources;
@@ -20,8 +21,9 @@ Prints ONE JSON line (rank 0) with the driver's contract plus
                   forward alone on all cores and on one thread, and the reference's own operating point (batch 1);
   end_to_end    - the real Evaluator over a generated DUTS-layout JPEG tree (decode pool -> device resize / normalise ->
                   forward -> metrics): what a user sees, bounded by JPEG decoding on the host cores;
-  serving       - SelfMaskInference.predict_tensors at batch 1 (app.py's call pattern): p50 / p99 latency.
---quick skips everything but the timed steps and the roofline (profiling runs).
+  serving       - SelfMaskInference.predict_tensors at batch 1 (app.py's call pattern): p50 / p99 latency;
+  and, N=1 only, the f16 throughput-mode diagnostic, the other shapes, bilateral refinement and pseudo-mask legs.
+--full --quick skips everything but the timed steps and the roofline (profiling runs).
 --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32), for comparing two builds output for
 output: `rows` - the per-image result rows of that step, every rank's (B*N, 16: 7 metrics of the picked mask, 7 of the upper
 bound, the two query ids); `mask_pred`, `objectness`, `features` - rank 0's MaskFormer.forward outputs for that batch.  The
@@ -414,6 +416,42 @@ def roofline_of(kern, gemm_mode, name=None):
     return r
 
 
+def headline_roofline(kern, gemm_mode, step_tflops):
+    """--full: the `roofline` / `roofline_other_kernels` fields of the headline line from the per-kernel taps behind the timed
+    steps; `step_tflops` = algorithmic TFLOP/s of the timed region per GPU."""
+    dom_name = next(iter(kern))
+    # HBM bytes per launch from the PMC passes of this same command (scripts/pmc_traffic.sh writes
+    # profiles/r04_pmc_traffic.json with the hash of the kernel sources it ran on).  A profiler cannot run inside the
+    # timed process, so the committed measurement is quoted - only if it was taken on exactly these sources, else null.
+    traffic, traffic_note = None, "no PMC file for these kernel sources"
+    for rnd in ("r04", "r03"):  # the newest PMC passes whose kernel-source hash matches
+        pf = f"profiles/{rnd}_pmc_traffic.json"
+        try:
+            with open(os.path.join(REPO, pf)) as f:
+                pmc = json.load(f)
+        except (OSError, ValueError):
+            continue
+        if pmc.get("source_hash") == source_hash():
+            traffic = pmc.get("kernels", {}).get(dom_name, {}).get("hbm_bytes_per_launch")
+            traffic_note = f"{pf} (separate FETCH_SIZE / WRITE_SIZE passes, FETCH x2 on gfx950)"
+            break
+        traffic_note = f"{pf} was taken on other kernel sources (hash mismatch): not quoted"
+    peak = F32_MFMA_PEAK_TFLOPS if gemm_mode == "fp32" else F16_MFMA_PEAK_TFLOPS
+    issue = 3.0 if gemm_mode in ("w16", "f16x2") else 1.0  # MFMA FLOPs issued per algorithmic FLOP (hi*hi, hi*lo, lo*hi)
+    return {
+        "roofline": dict(roofline_of(kern, gemm_mode, dom_name), traffic=traffic, traffic_source=traffic_note,
+                         how="HIP events around every launch of this kernel inside 3 real forwards on ONE stream "
+                             "(sm_forward_timing); an empty event pair's time (event_overhead_us) is subtracted per launch",
+                         whole_step={"achieved": round(step_tflops, 2), "peak": peak, "unit": "TFLOP/s",
+                                     "frac": round(step_tflops / peak, 4),
+                                     "mfma_issued_tflops": round(step_tflops * issue, 2),
+                                     "what": "algorithmic FLOPs of the forward x images/s of the timed region, per GPU: the rate the "
+                                             "three-batches-in-flight pipeline sustains (the tile shapes are chosen for THIS figure; "
+                                             "a lone launch of the dominant kernel is slower than with smaller tiles)"}),
+        "roofline_other_kernels": {k: roofline_of(kern, gemm_mode, k) for k in list(kern)[1:]},
+    }
+
+
 def shape_leg(dev, P, S, B, streams, steps=20, warmup=5, cpu=True):
     """The same step loop at another shape of BASELINE.json / the shipped YAML (ViT-S/8 224^2: the shipped checkpoint's
     patch size, N = 785; 384^2: configs[2], N = 577): images/s, the dominant kernel's roofline, the CPU oracle beside it."""
@@ -798,9 +836,16 @@ def main():
                          "batch's latency-bound decoder / metrics kernels fill CUs beside another's encoder GEMMs")
     ap.add_argument("--no-graph", action="store_true", help="launch the forward's kernels eagerly instead of replaying "
                                                             "one captured hipGraph per stream")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--sustained-steps", type=int, default=500, help="extra untimed-by-the-contract leg: the same loop for this many steps")
-    ap.add_argument("--quick", action="store_true", help="timed steps + roofline only (no sustained / CPU / end-to-end / serving legs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the legs beyond the headline (roofline taps, sustained, end to end, "
+                         "serving, throughput mode, other shapes, refinement, pseudo masks, CPU baseline); a plain run only "
+                         "sets up, warms up, times the steps, dumps and prints the contract line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle legs")
+    ap.add_argument("--sustained-steps", type=int, default=500,
+                    help="with --full: extra untimed-by-the-contract leg, the same loop for this many steps")
+    ap.add_argument("--quick", action="store_true",
+                    help="with --full: timed steps + roofline only (no sustained / CPU / end-to-end / serving legs); "
+                         "no effect on a plain run, which has neither")
     ap.add_argument("--host-input", action="store_true",
                     help="diagnostic: every step copies its batch from pinned host memory first (PCIe-inclusive rate; "
                          "the metric keeps inputs resident in HBM)")
@@ -810,8 +855,9 @@ def main():
                          "activity in the matrix cores; how far the result rises above the metric is how power-limited it is")
     ap.add_argument("--gemm-mode", default=None, choices=["w16", "f16x2", "fp32", "f16"],
                     help="GEMM back end (default w16; f16 = the one-MFMA-per-product diagnostic, not the metric)")
-    ap.add_argument("--e2e-ranks", action="store_true", help="with --gpus N > 1: also run the end-to-end leg (files -> metrics) on all N ranks")
-    ap.add_argument("--no-other-shapes", action="store_true", help="skip the ViT-S/8 224^2 and ViT-S/16 384^2 legs")
+    ap.add_argument("--e2e-ranks", action="store_true",
+                    help="with --full and --gpus N > 1: also run the end-to-end leg (files -> metrics) on all N ranks")
+    ap.add_argument("--no-other-shapes", action="store_true", help="with --full: skip the ViT-S/8 224^2 and ViT-S/16 384^2 legs")
     ap.add_argument("--only-leg", default=None, choices=["refine_384", "pseudo_masks"],
                     help="run ONE of the extra legs and print its JSON (profiling runs); not the driver's contract")
     ap.add_argument("--launcher-selftest", action="store_true",
@@ -899,13 +945,14 @@ def main():
             dumped = dump_outputs(arrays, a.dump_outputs)
         wl.keep_last, wl.last_out = False, None
 
+    # everything below the dump is --full only: a plain run goes straight to its contract line
     # per-kernel taps right behind the timed steps (same clocks / cache state as the K steps; agreement with rocprofv3's
     # kernel-trace averages of the same command is checked in profiles/)
-    kern = time_forward_kernels(model, x) if rank == 0 else None
+    kern = time_forward_kernels(model, x) if rank == 0 and a.full else None
 
     # sustained leg (outside the contract's timed region): the K-step figure above is a ~0.2 s burst
     sustained = None
-    if a.sustained_steps > 0 and not a.quick:
+    if a.full and a.sustained_steps > 0 and not a.quick:
         sync()
         t1 = time.perf_counter()
         run_steps(a.sustained_steps)
@@ -920,32 +967,12 @@ def main():
     # over RCCL) - opt-in there (--e2e-ranks): the driver's scaling runs measure the contract's K steps, and a leg that walks a
     # file tree on N ranks has no place inside them
     e2e = None
-    if not a.quick and (world == 1 or a.e2e_ranks):
+    if a.full and not a.quick and (world == 1 or a.e2e_ranks):
         e2e = end_to_end(model, dev, P, S, B, len(ring.streams), world=world, rank=rank)
 
     if rank == 0:
         value = world * a.steps * B / dt
         flops_img = forward_flops_per_image(P, S)
-        dom_name, dom = next(iter(kern.items()))
-        # HBM bytes per launch from the PMC passes of this same command (scripts/pmc_traffic.sh writes
-        # profiles/r04_pmc_traffic.json with the hash of the kernel sources it ran on).  A profiler cannot run inside the
-        # timed process, so the committed measurement is quoted - only if it was taken on exactly these sources, else null.
-        traffic, traffic_note = None, "no PMC file for these kernel sources"
-        for rnd in ("r04", "r03"):  # the newest PMC passes whose kernel-source hash matches
-            pf = f"profiles/{rnd}_pmc_traffic.json"
-            try:
-                with open(os.path.join(REPO, pf)) as f:
-                    pmc = json.load(f)
-            except (OSError, ValueError):
-                continue
-            if pmc.get("source_hash") == source_hash():
-                traffic = pmc.get("kernels", {}).get(dom_name, {}).get("hbm_bytes_per_launch")
-                traffic_note = f"{pf} (separate FETCH_SIZE / WRITE_SIZE passes, FETCH x2 on gfx950)"
-                break
-            traffic_note = f"{pf} was taken on other kernel sources (hash mismatch): not quoted"
-        peak = F32_MFMA_PEAK_TFLOPS if model.gemm_mode == "fp32" else F16_MFMA_PEAK_TFLOPS
-        issue = 3.0 if model.gemm_mode in ("w16", "f16x2") else 1.0  # MFMA FLOPs issued per algorithmic FLOP (hi*hi, hi*lo, lo*hi)
-
         res = {
             "metric": "images/sec (224^2, nq=20)", "value": round(value, 1), "unit": "images/sec", "n_gpus": world,
             "rccl_ranks": dist.get_world_size() if world > 1 else 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3),
@@ -961,22 +988,14 @@ def main():
                        "hip_graph": {"captures": fwd.captures, "replays": fwd.replays, "failed": fwd.failed},
                        "parallelism": f"images sharded x{world}, one all-gather of result rows"},
             "model_tflops": round(value * flops_img / 1e12, 2),
-            "roofline": dict(roofline_of(kern, model.gemm_mode, dom_name), traffic=traffic, traffic_source=traffic_note,
-                             how="HIP events around every launch of this kernel inside 3 real forwards on ONE stream "
-                                 "(sm_forward_timing); an empty event pair's time (event_overhead_us) is subtracted per launch",
-                             whole_step={"achieved": round(value / world * flops_img / 1e12, 2), "peak": peak, "unit": "TFLOP/s",
-                                         "frac": round(value / world * flops_img / 1e12 / peak, 4),
-                                         "mfma_issued_tflops": round(value / world * flops_img / 1e12 * issue, 2),
-                                         "what": "algorithmic FLOPs of the forward x images/s of the timed region, per GPU: the rate the "
-                                                 "three-batches-in-flight pipeline sustains (the tile shapes are chosen for THIS figure; "
-                                                 "a lone launch of the dominant kernel is slower than with smaller tiles)"}),
-            "roofline_other_kernels": {k: roofline_of(kern, model.gemm_mode, k) for k in list(kern)[1:]},
         }
-        res["sustained"] = sustained
-        res["end_to_end"] = e2e
+        if a.full:
+            res.update(headline_roofline(kern, model.gemm_mode, value / world * flops_img / 1e12))
+            res["sustained"] = sustained
+            res["end_to_end"] = e2e
         if dumped is not None:
             res["dump_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
-        if world == 1 and not a.quick:
+        if world == 1 and a.full and not a.quick:
             res["serving"] = serving_latency(model, dev)
             if model.gemm_mode == "w16" and not a.zero_data:
                 res["throughput_mode"] = throughput_mode_leg(dev, wl)
@@ -988,7 +1007,7 @@ def main():
                                        "vit_s16_384": shape_leg(dev, 16, 384, 32, len(ring.streams), cpu=not a.no_cpu_baseline)}
                 res["refine_384"] = refine_leg(dev, len(ring.streams), cpu=not a.no_cpu_baseline)       # configs[2]
                 res["pseudo_masks"] = pseudo_masks_leg(dev, len(ring.streams), cpu=not a.no_cpu_baseline)  # configs[4]
-        if world == 1 and not a.no_cpu_baseline and not a.quick:
+        if world == 1 and a.full and not a.no_cpu_baseline and not a.quick:
             res["cpu_baseline"] = cpu_baseline(P, S)
         print(json.dumps(res), flush=True)
     if world > 1:

@@ -26,7 +26,7 @@ def snapshot_then(*args, **kw):  # the single-stream kernel taps run after the t
 
 
 bench.time_forward_kernels = snapshot_then
-sys.argv = ["bench.py", "--quick", "--steps", "60"] + sys.argv[3:]
+sys.argv = ["bench.py", "--full", "--quick", "--steps", "60"] + sys.argv[3:]
 bench.main()
 ntiles = int(os.environ.get("TILES", "150"))
 t = np.frombuffer(buf, dtype=np.uint64).reshape(2048, 4).astype(np.int64)[:ntiles]

@@ -1,15 +1,17 @@
 #!/bin/bash
-# rocprofv3 kernel-trace + stats of the default bench run; summaries land under gpurun_out/<tag>/ (copy the
-# *_kernel_stats.csv you want judged into profiles/).   usage: bash scripts/profile_bench.sh <tag> [bench args]
+# rocprofv3 kernel-trace + stats of the bench run with its per-kernel taps (--full --quick); summaries land under
+# $OUT/<tag>/ (default build/profiles; copy the *_kernel_stats.csv you want judged into profiles/).
+# usage: bash scripts/profile_bench.sh <tag> [bench args]
 set -e
 TAG=${1:-prof}; shift || true
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
+OUT=${OUT:-build/profiles}
 cd /tmp && export TMPDIR=/tmp
 cd "$ROOT"
-mkdir -p gpurun_out
-rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/$TAG -- python3 bench.py --quick "$@" > gpurun_out/$TAG.log 2>&1
+mkdir -p "$OUT"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$TAG" -- python3 bench.py --full --quick "$@" > "$OUT/$TAG.log" 2>&1
 echo "rc=$?"
-tail -1 gpurun_out/$TAG.log
-F=$(find gpurun_out/$TAG -name "*kernel_stats.csv" | head -1)
+tail -1 "$OUT/$TAG.log"
+F=$(find "$OUT/$TAG" -name "*kernel_stats.csv" | head -1)
 echo "stats: $F"
 head -25 "$F"
