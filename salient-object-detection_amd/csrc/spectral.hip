@@ -12,7 +12,14 @@
 //      u_i = v_i / sqrt(d_i)                                                                        [spectral_embed_kernel]
 //   5. k-means on the first k embedding columns for every requested k (ONE eigen-solve serves all)  [kmeans_embed_kernel]
 // Every sum runs in a fixed order (no floating-point atomics): labels are a function of the input alone.
+// Above 8192 points (to 32768) steps 1-3 become a streaming k-NN that never forms the Gram matrix [knn_stream_kernel] and an O(n m)
+// build of the same lists [knn_indegree / knn_lists_scan / knn_reverse_scatter / knn_reverse_sort]: the workspace is linear in n.
 #include "common.h"
+#include <mutex>
+#include <set>
+#include <stdlib.h>
+#include <string.h>
+#include <utility>
 
 // no fused multiply-adds the source does not spell out: the eigen-solver's memory plans are different instantiations of the same
 // expressions and must round them alike (tests: the plans give the same bits), and the oracle is numpy
@@ -24,7 +31,8 @@ constexpr int SP_B = 8;          // block of vectors iterated (wanted kw <= 6 + 
 constexpr int SP_THREADS = 512;  // one workgroup per image (8 waves: 256 registers per lane for the 36-entry Gram accumulations)
 constexpr int SP_WAVES = SP_THREADS / 64;
 constexpr int SP_MAXM = 32;      // neighbours kept per point (n_neighbors - 1)
-constexpr int SP_MAXN = 8192;    // points per image
+constexpr int SP_MAXN = 8192;    // points per image on the Gram-matrix path
+constexpr int SP_MAXN_L = 32768; // points per image on the streaming path (8192 < n: no n x n array)
 
 __device__ __forceinline__ double shfl_d(double v, int src) {
     const unsigned long long u = __double_as_longlong(v);
@@ -235,6 +243,253 @@ __global__ __launch_bounds__(SP_THREADS) void knn_graph_kernel(const int* __rest
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// 2'. streaming k-NN (8192 < n <= 32768; the tuning build's SM_SPECTRAL_KNN=stream at any n): the selection of knn_select_kernel
+// without the n x n Gram matrix.  A workgroup owns 64 query rows of one image (16 per wave, their F16X2 fragments in registers for
+// the whole run) and streams the image's points through the LDS 32 at a time; the 16 x 16 product tiles run on the f16 matrix cores
+// in gemm_f16x2's three-product form (acc = hi hi, crs = hi lo + lo hi, g = acc + crs 2^-11: fp32-grade), and key_j = sq_j - 2 g_ij
+// with sq from the same products (knn_sqnorm_kernel: the diagonal tiles).  Four lanes share a row: each keeps the CAP smallest
+// (key, j) of its quarter of every tile, sorted, j ascending within the lane (a candidate no smaller than the lane's m-th key is
+// rejected before the insertion); the four lists are merged at the end as knn_select_kernel merges its 64.
+constexpr int KS_ROWS = 64;                   // query rows per workgroup
+constexpr int KS_COLS = 32;                   // points per streamed tile
+constexpr int KS_KSTEPS = SM_EMBED / 32;      // 16x16x32 MFMA steps over the 384 features
+constexpr int KS_ROWB = SM_EMBED * 4;         // bytes of an F16X2 row (8 k: 16 B of hi halves, then 16 B of lo halves)
+constexpr int KS_PITCH = KS_ROWB + 16;        // LDS bytes per staged point (+16: the fragment reads of 16 points hit distinct banks)
+constexpr int KS_CHUNKS = KS_COLS * KS_ROWB / 16 / 256;  // 16-B pieces of a tile per thread
+static_assert(KS_CHUNKS * 16 * 256 == KS_COLS * KS_ROWB, "tile staging");
+
+struct KsFrag { f16x8 h[KS_KSTEPS], l[KS_KSTEPS]; };
+
+// lane l: row l & 15 of a 16-row block, k-group 4 s + (l >> 4) of step s (the 16x16x32 operand map; A and B take the same one)
+__device__ __forceinline__ void ks_load_frag(const char* row, KsFrag& f) {
+    const int q = (threadIdx.x & 63) >> 4;
+#pragma unroll
+    for (int s = 0; s < KS_KSTEPS; ++s) {
+        f.h[s] = *reinterpret_cast<const f16x8*>(row + (4 * s + q) * 32);
+        f.l[s] = *reinterpret_cast<const f16x8*>(row + (4 * s + q) * 32 + 16);
+    }
+}
+
+// D[i][j] = sum_k Q[i][k] C[j][k] for the 16 rows of `qf` and the 16 points whose F16X2 rows `crow` points at (lane's point l & 15);
+// lane l returns D[4 (l >> 4) + r][l & 15] in element r
+__device__ __forceinline__ f32x4 ks_tile(const KsFrag& qf, const char* crow) {
+    const int q = (threadIdx.x & 63) >> 4;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f}, crs = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < KS_KSTEPS; ++s) {
+        const f16x8 ch = *reinterpret_cast<const f16x8*>(crow + (4 * s + q) * 32);
+        const f16x8 cl = *reinterpret_cast<const f16x8*>(crow + (4 * s + q) * 32 + 16);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(qf.h[s], ch, acc, 0, 0, 0);
+        crs = __builtin_amdgcn_mfma_f32_16x16x32_f16(qf.h[s], cl, crs, 0, 0, 0);
+        crs = __builtin_amdgcn_mfma_f32_16x16x32_f16(qf.l[s], ch, crs, 0, 0, 0);
+    }
+    f32x4 g;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) g[r] = acc[r] + crs[r] * (1.0f / 2048.0f);
+    return g;
+}
+
+// sq_p = <f_p, f_p> as ks_tile forms it: the diagonal of the 16 x 16 tile of a block of 16 points with itself (one wave per block)
+__global__ __launch_bounds__(256) void knn_sqnorm_kernel(const float* __restrict__ fs, int64_t rows, float* __restrict__ sq) {
+    const int lane = threadIdx.x & 63;
+    const int64_t b0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16;
+    if (b0 >= rows) return;  // whole waves
+    const int64_t p = b0 + (lane & 15) < rows ? b0 + (lane & 15) : rows - 1;
+    const char* row = reinterpret_cast<const char*>(fs) + p * KS_ROWB;
+    KsFrag f;
+    ks_load_frag(row, f);
+    const f32x4 g = ks_tile(f, row);
+    const int i = lane & 15, r = i - 4 * (lane >> 4);  // D[i][i] sits in element i - 4 (lane >> 4) of lane i + 16 (i >> 2)
+    float v = g[0];
+#pragma unroll
+    for (int k = 1; k < 4; ++k) v = r == k ? g[k] : v;
+    if (r >= 0 && r < 4 && b0 + i < rows) sq[b0 + i] = v;
+}
+
+template <int CAP>
+__global__ __launch_bounds__(256) void knn_stream_kernel(const float* __restrict__ fs_all, const float* __restrict__ sq_all, int n, int m,
+                                                         int* __restrict__ idx_all) {
+    __shared__ __attribute__((aligned(16))) char ctile[KS_COLS * KS_PITCH];
+    __shared__ float keys[4][16][KS_COLS + 1];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, img = blockIdx.y;
+    const int q0 = blockIdx.x * KS_ROWS + wave * 16;
+    const char* fs = reinterpret_cast<const char*>(fs_all + (int64_t)img * n * SM_EMBED);
+    const float* sq = sq_all + (int64_t)img * n;
+    KsFrag qf;
+    ks_load_frag(fs + (int64_t)min(q0 + (lane & 15), n - 1) * KS_ROWB, qf);
+    // the selection: lane l keeps row q0 + (l >> 2), columns 8 (l & 3) .. + 8 of every tile
+    const int srow = lane >> 2, ssub = lane & 3, row = q0 + srow;
+    float key[CAP], thr = INFINITY;  // thr: the lane's m-th key so far
+    int id[CAP];
+#pragma unroll
+    for (int p = 0; p < CAP; ++p) { key[p] = INFINITY; id[p] = 0x7fffffff; }
+    // a tile moves global -> registers -> LDS in two halves (the whole tile in flight would spill the query fragments)
+    auto stage = [&](int c0) {
+#pragma unroll
+        for (int hb = 0; hb < 2; ++hb) {
+            float4 v[KS_CHUNKS / 2];
+#pragma unroll
+            for (int i = 0; i < KS_CHUNKS / 2; ++i) {
+                const int ch = tid + 256 * (hb * (KS_CHUNKS / 2) + i), c = ch / (KS_ROWB / 16), pc = ch % (KS_ROWB / 16);
+                v[i] = *reinterpret_cast<const float4*>(fs + (int64_t)min(c0 + c, n - 1) * KS_ROWB + pc * 16);
+            }
+#pragma unroll
+            for (int i = 0; i < KS_CHUNKS / 2; ++i) {
+                const int ch = tid + 256 * (hb * (KS_CHUNKS / 2) + i), c = ch / (KS_ROWB / 16), pc = ch % (KS_ROWB / 16);
+                *reinterpret_cast<float4*>(ctile + c * KS_PITCH + pc * 16) = v[i];
+            }
+        }
+    };
+    const int ntiles = (n + KS_COLS - 1) / KS_COLS;
+#pragma unroll 1
+    for (int t = 0; t < ntiles; ++t) {
+        const int c0 = t * KS_COLS;
+        stage(c0);
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < KS_COLS / 16; ++u) {
+            const f32x4 g = ks_tile(qf, ctile + (u * 16 + (lane & 15)) * KS_PITCH);
+            const float sj = sq[min(c0 + u * 16 + (lane & 15), n - 1)];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) keys[wave][4 * (lane >> 4) + r][u * 16 + (lane & 15)] = sj - 2.0f * g[r];
+        }
+        __syncthreads();  // the tile's fragment reads are done (the next tile may land) and the keys are in place
+#pragma unroll 1
+        for (int cc = 0; cc < 8; ++cc) {
+            const int jl = ssub * 8 + cc, j = c0 + jl;
+            if (j >= n || j == row) continue;
+            const float kj = keys[wave][srow][jl];
+            if (kj < thr) {  // j ascends within a lane: on equal keys the earlier index stays in front
+#pragma unroll
+                for (int p = CAP - 1; p > 0; --p) {
+                    const bool up = kj < key[p - 1];
+                    const bool here = !up && kj < key[p];
+                    key[p] = up ? key[p - 1] : (here ? kj : key[p]);
+                    id[p] = up ? id[p - 1] : (here ? j : id[p]);
+                }
+                if (kj < key[0]) { key[0] = kj; id[0] = j; }
+#pragma unroll
+                for (int p = 0; p < CAP; ++p) thr = p == m - 1 ? key[p] : thr;
+            }
+        }
+    }
+    int* out = idx_all + ((int64_t)img * n + row) * m;
+    for (int r = 0; r < m; ++r) {
+        float bk = key[0];
+        int bi = id[0];
+#pragma unroll
+        for (int o = 1; o < 4; o <<= 1) {
+            const float ok = __shfl_xor(bk, o, 64);
+            const int oi = __shfl_xor(bi, o, 64);
+            if (ok < bk || (ok == bk && oi < bi)) { bk = ok; bi = oi; }
+        }
+        if (ssub == 0 && row < n) out[r] = (unsigned)bi < (unsigned)n ? bi : (row + 1 + r) % n;  // (knn_select_kernel's fallback)
+        if (id[0] == bi) {
+#pragma unroll
+            for (int p = 0; p < CAP - 1; ++p) { key[p] = key[p + 1]; id[p] = id[p + 1]; }
+            key[CAP - 1] = INFINITY;
+            id[CAP - 1] = 0x7fffffff;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// 3'. the same adjacency lists as knn_graph_kernel in O(n m) (8192 < n; the tuning build's SM_SPECTRAL_GRAPH=lists at any n):
+// in-degrees by integer atomics (counts only: their order cannot change a result), an exclusive scan per image, the reverse edges
+// scattered behind each point's own m, then every reverse segment sorted ascending.  A point that lists another twice (the fallback
+// of a row with non-finite features can repeat an index) counts once, as the bitmap's one bit per pair does.
+__device__ __forceinline__ bool sp_first_listing(const int* li, int r, int t) {
+    for (int q = 0; q < r; ++q)
+        if (li[q] == t) return false;
+    return true;
+}
+
+__global__ __launch_bounds__(256) void knn_indegree_kernel(const int* __restrict__ idx_all, int n, int m, int* __restrict__ cnt_all) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)n * m) return;
+    const int* idx = idx_all + (int64_t)blockIdx.y * n * m;
+    const int i = (int)(e / m), r = (int)(e % m), t = idx[e];
+    if (sp_first_listing(idx + (int64_t)i * m, r, t)) atomicAdd(&cnt_all[(int64_t)blockIdx.y * n + t], 1);
+}
+
+// one workgroup per image: lengths, 1 / sqrt(d) and list starts exactly as knn_graph_kernel writes them, the own lists copied, and
+// the counts reset (they are the scatter's cursors next)
+__global__ __launch_bounds__(SP_THREADS) void knn_lists_scan_kernel(const int* __restrict__ idx_all, int n, int m, int* __restrict__ cnt_all,
+                                                                    int* __restrict__ ptr_all, int* __restrict__ len_all,
+                                                                    int* __restrict__ col_all, double* __restrict__ isd_all) {
+    __shared__ int part[SP_THREADS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, img = blockIdx.x;
+    const int* idx = idx_all + (int64_t)img * n * m;
+    int* cnt = cnt_all + (int64_t)img * n;
+    int* ptr = ptr_all + (int64_t)img * (n + 1);
+    int* len = len_all + (int64_t)img * n;
+    int* col = col_all + (int64_t)img * sp_col_capacity(n, m);
+    double* isd = isd_all + (int64_t)img * n;
+    const int per = (n + SP_THREADS - 1) / SP_THREADS, r0 = tid * per, r1 = min(n, r0 + per);
+    int mine = 0;
+    for (int r = r0; r < r1; ++r) {
+        const int c = cnt[r];
+        len[r] = m + c;
+        isd[r] = 1.0 / sqrt(0.5 * (double)(m + c));
+        mine += (m + c + 3) & ~3;
+    }
+    part[tid] = mine;
+    __syncthreads();
+    if (wave == 0) {
+        int s[SP_WAVES], tot = 0;
+#pragma unroll
+        for (int q = 0; q < SP_WAVES; ++q) { s[q] = tot; tot += part[lane * SP_WAVES + q]; }
+        int inc = tot;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int v = __shfl_up(inc, o, 64);
+            if (lane >= o) inc += v;
+        }
+        const int base = inc - tot;
+#pragma unroll
+        for (int q = 0; q < SP_WAVES; ++q) part[lane * SP_WAVES + q] = base + s[q];
+    }
+    __syncthreads();
+    int run = part[tid];
+    for (int r = r0; r < r1; ++r) {
+        ptr[r] = run;
+        for (int q = 0; q < m; ++q) col[run + q] = idx[(int64_t)r * m + q];
+        cnt[r] = 0;
+        run += (len[r] + 3) & ~3;
+    }
+    if (r1 == n && r0 < n) ptr[n] = run;
+}
+
+__global__ __launch_bounds__(256) void knn_reverse_scatter_kernel(const int* __restrict__ idx_all, int n, int m, int* __restrict__ cur_all,
+                                                                  const int* __restrict__ ptr_all, int* __restrict__ rev_all) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)n * m) return;
+    const int img = blockIdx.y;
+    const int* idx = idx_all + (int64_t)img * n * m;
+    const int i = (int)(e / m), r = (int)(e % m), t = idx[e];
+    if (!sp_first_listing(idx + (int64_t)i * m, r, t)) return;
+    const int at = atomicAdd(&cur_all[(int64_t)img * n + t], 1);
+    rev_all[(int64_t)img * sp_col_capacity(n, m) + ptr_all[(int64_t)img * (n + 1) + t] + m + at] = i;
+}
+
+// one wave per point: its reverse segment (distinct indices) in ascending order, by rank
+__global__ __launch_bounds__(256) void knn_reverse_sort_kernel(int n, int m, const int* __restrict__ ptr_all, const int* __restrict__ len_all,
+                                                               const int* __restrict__ rev_all, int* __restrict__ col_all) {
+    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6), img = blockIdx.y;
+    if (r >= n) return;
+    const int64_t cap = sp_col_capacity(n, m);
+    const int s = ptr_all[(int64_t)img * (n + 1) + r] + m, L = len_all[(int64_t)img * n + r] - m;
+    const int* rev = rev_all + img * cap + s;
+    int* col = col_all + img * cap + s;
+    for (int e = lane; e < L; e += 64) {
+        const int v = rev[e];
+        int rank = 0;
+        for (int f = 0; f < L; ++f) rank += rev[f] < v ? 1 : 0;
+        col[rank] = v;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // 4. eigen-solver
 struct SpGraph {
     const int* ptr;     // (n + 1) adjacency list starts, multiples of 4
@@ -252,9 +507,12 @@ struct SpGraph {
 // the current item reads the LDS - all 24 reads first, ONE wait, then the sum.  (Left to the compiler every neighbour was a read ->
 // s_waitcnt lgkmcnt(0) -> add round trip, and an item began with two dependent global latencies: 80 k cycles per step at n = 784,
 // scripts/spectral_stamps.py.)  Entries past cnt are read but add 0; longer lists (hubs) finish in a plain loop.
-template <int CG, bool LAST>
+// MEM (MODE 1, n above what one staged column leaves room for): the same items, each neighbour's value read straight from the block
+// in memory (a row is 64 B; CG = 8, nothing staged) - the same values summed in the same order.
+template <int CG, bool LAST, bool MEM = false>
 __device__ __forceinline__ void sp_filter_step(const SpGraph& g, const double* __restrict__ Yr, double* __restrict__ Xw, double* ylds,
                                                double c0, double f1, double f2) {
+    static_assert(!MEM || CG == SP_B, "the gathering plan takes the whole block row");
     const int total = g.n * CG, zero_row = g.n;  // ylds holds n + 1 rows: the last one is zeros, the target of a list's padding
     struct Meta { int s, cnt; double w; };
     auto meta = [&](int t) {
@@ -272,8 +530,10 @@ __device__ __forceinline__ void sp_filter_step(const SpGraph& g, const double* _
     };
 #pragma unroll 1
     for (int c = 0; c < SP_B; c += CG) {
-        for (int t = threadIdx.x; t < total; t += SP_THREADS) ylds[t] = Yr[(t / CG) * SP_B + c + t % CG];
-        if (threadIdx.x < CG) ylds[total + threadIdx.x] = 0.0;
+        if (!MEM) {
+            for (int t = threadIdx.x; t < total; t += SP_THREADS) ylds[t] = Yr[(t / CG) * SP_B + c + t % CG];
+            if (threadIdx.x < CG) ylds[total + threadIdx.x] = 0.0;
+        }
         int t = threadIdx.x;
         Meta m_cur = meta(t), m_next = meta(t + SP_THREADS);
         Idx x_cur = indices(m_cur);
@@ -288,13 +548,20 @@ __device__ __forceinline__ void sp_filter_step(const SpGraph& g, const double* _
             for (int k = 0; k < 6; ++k) { nb[4 * k] = x_cur.v[k].x; nb[4 * k + 1] = x_cur.v[k].y; nb[4 * k + 2] = x_cur.v[k].z; nb[4 * k + 3] = x_cur.v[k].w; }
             double y[24];
 #pragma unroll
-            for (int u = 0; u < 24; ++u) y[u] = ylds[(u < cnt ? nb[u] : zero_row) * CG + jj];  // past the list: + 0.0 (exact)
-            const double yo = ylds[t], xo = Xw[i * SP_B + c + jj];
+            for (int u = 0; u < 24; ++u) {  // past the list: + 0.0 (exact)
+                if (MEM) {
+                    const double v = Yr[(u < cnt ? nb[u] : i) * SP_B + jj];
+                    y[u] = u < cnt ? v : 0.0;
+                } else {
+                    y[u] = ylds[(u < cnt ? nb[u] : zero_row) * CG + jj];
+                }
+            }
+            const double yo = MEM ? Yr[t] : ylds[t], xo = Xw[i * SP_B + c + jj];
             asm volatile("" ::: "memory");  // every load above is issued before the first add below
             double acc = 0.0;
 #pragma unroll
             for (int u = 0; u < 24; ++u) acc += y[u];
-            for (int e = 24; e < cnt; ++e) acc += ylds[g.col[m_cur.s + e] * CG + jj];
+            for (int e = 24; e < cnt; ++e) acc += MEM ? Yr[g.col[m_cur.s + e] * SP_B + jj] : ylds[g.col[m_cur.s + e] * CG + jj];
             const double w = m_cur.w;
             const double ly = yo - (0.5 * w * w) * acc;
             const double xn = (ly - c0 * yo) * f1 - f2 * xo;
@@ -794,7 +1061,8 @@ __device__ __forceinline__ double sp_init_value(int i, int j) {  // splitmix64 o
     return (double)(long long)(x >> 11) * (2.0 / 9007199254740992.0) - 1.0;
 }
 
-// MODE 0: graph in memory, CG columns of the block staged per step; 2: graph and both blocks in the LDS for the whole solve (CG = 8);
+// MODE 0: graph in memory, CG columns of the block staged per step; 1: graph and block in memory, nothing staged (CG = 8: n above
+// 19 199, where one staged column no longer fits); 2: graph and both blocks in the LDS for the whole solve (CG = 8);
 // 3: graph and CG columns of both blocks in the LDS for a whole filter, column group after column group
 template <int CG, int MODE>
 __global__ __launch_bounds__(SP_THREADS) void spectral_embed_kernel(const int* __restrict__ ptr_all, const int* __restrict__ len_all,
@@ -1018,8 +1286,8 @@ __global__ __launch_bounds__(SP_THREADS) void spectral_embed_kernel(const int* _
             for (int it = 2; it <= degree; ++it) {
                 const double sn = 1.0 / (tau - sig);
                 const double f1 = 2.0 * sn / e, f2 = sig * sn;
-                if (it == degree) sp_filter_step<CG, true>(g, Y, X, ylds, c0, f1, f2);
-                else sp_filter_step<CG, false>(g, Y, X, ylds, c0, f1, f2);
+                if (it == degree) sp_filter_step<CG, true, MODE == 1>(g, Y, X, ylds, c0, f1, f2);
+                else sp_filter_step<CG, false, MODE == 1>(g, Y, X, ylds, c0, f1, f2);
                 ++matvecs;
                 double* sw = X;
                 X = Y;
@@ -1202,6 +1470,7 @@ static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct SpLayout {
     size_t fs, gram, sq, idx, bits, inptr, inlen, incol, isd, blocks, emb, total;
+    size_t cnt, rev;  // the O(n m) graph build: in-degrees / cursors, the scattered reverse edges (streaming layout only)
 };
 static SpLayout sp_layout(int B, int n, int m, int kw) {
     SpLayout l;
@@ -1219,21 +1488,63 @@ static SpLayout sp_layout(int B, int n, int m, int kw) {
     l.blocks = o; o += al256((size_t)B * 2 * n * SP_B * 8);
     l.emb = o;    o += al256((size_t)B * n * kw * 8);
     l.total = o;
+    // the tuning build's forced O(n m) graph build borrows the Gram matrix (read before it) and the bitmap (unused) - where they hold it
+    l.cnt = l.bits;
+    l.rev = (size_t)sp_col_capacity(n, m) <= (size_t)n * n ? l.gram : 0;  // (0: no room - offset 0 is the features')
     return l;
 }
+// 8192 < n: nothing quadratic - the features in F16X2 form, norms, lists, graph, the two blocks of the eigen-solver, the embedding
+static SpLayout sp_layout_stream(int B, int n, int m, int kw) {
+    SpLayout l = {};
+    size_t o = 0;
+    l.fs = o;     o += al256((size_t)B * n * SM_EMBED * 4);
+    l.sq = o;     o += al256((size_t)B * n * 4);
+    l.idx = o;    o += al256((size_t)B * n * m * 4);
+    l.cnt = o;    o += al256((size_t)B * n * 4);
+    l.inptr = o;  o += al256((size_t)B * (n + 1) * 4);
+    l.inlen = o;  o += al256((size_t)B * n * 4);
+    l.incol = o;  o += al256((size_t)B * sp_col_capacity(n, m) * 4);
+    l.rev = o;    o += al256((size_t)B * sp_col_capacity(n, m) * 4);
+    l.isd = o;    o += al256((size_t)B * n * 8);
+    l.blocks = o; o += al256((size_t)B * 2 * n * SP_B * 8);
+    l.emb = o;    o += al256((size_t)B * n * kw * 8);
+    l.total = o;
+    return l;
+}
+
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device): the attribute belongs to the current device, and
+// several host threads may launch at once
+static void sp_allow_lds(const void* kern, int bytes) {
+    static std::mutex mu;
+    static std::set<std::pair<const void*, int>> done;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> lock(mu);
+    if (done.insert({kern, dev}).second) {
+        (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        (void)hipGetLastError();
+    }
+}
+
+#ifdef SM_TUNING  // the tuning build's forcings (tests run each piece of the streaming path at small n against the Gram path)
+static bool sp_env_is(const char* name, const char* value) {
+    const char* e = getenv(name);
+    return e && strcmp(e, value) == 0;
+}
+#endif
 
 }  // namespace sm
 
 extern "C" size_t sm_spectral_workspace_bytes(int32_t B, int32_t n, int32_t n_neighbors, int32_t kw) {
-    if (B < 1 || n < 2 * sm::SP_B || n > sm::SP_MAXN || n_neighbors < 2 || n_neighbors - 1 > sm::SP_MAXM || kw < 1 || kw > 6) return 0;
+    if (B < 1 || n < 2 * sm::SP_B || n > sm::SP_MAXN_L || n_neighbors < 2 || n_neighbors - 1 > sm::SP_MAXM || kw < 1 || kw > 6) return 0;
     const int m = n_neighbors - 1 < n - 1 ? n_neighbors - 1 : n - 1;
-    return sm::sp_layout(B, n, m, kw).total;
+    return (n <= sm::SP_MAXN ? sm::sp_layout(B, n, m, kw) : sm::sp_layout_stream(B, n, m, kw)).total;
 }
 
 extern "C" int sm_spectral_cluster_f32(const sm_spectral_args* a, void* stream) {
     SM_REQUIRE(a && a->features && a->labels && a->cluster_sizes && a->workspace, "sm_spectral_cluster_f32: null pointer");
-    SM_REQUIRE(a->B >= 1 && a->n >= 2 * sm::SP_B && a->n <= sm::SP_MAXN && a->n % 4 == 0,
-               "sm_spectral_cluster_f32: %d points (16 <= n <= %d, n %% 4 == 0)", a->n, sm::SP_MAXN);
+    SM_REQUIRE(a->B >= 1 && a->n >= 2 * sm::SP_B && a->n <= sm::SP_MAXN_L && a->n % 4 == 0,
+               "sm_spectral_cluster_f32: %d points (16 <= n <= %d, n %% 4 == 0)", a->n, sm::SP_MAXN_L);
     SM_REQUIRE(a->n_neighbors >= 2 && a->n_neighbors - 1 <= sm::SP_MAXM, "sm_spectral_cluster_f32: n_neighbors %d (2..%d)", a->n_neighbors,
                sm::SP_MAXM + 1);
     SM_REQUIRE(a->n_sizes >= 1 && a->n_sizes <= 8, "sm_spectral_cluster_f32: 1..8 cluster sizes");
@@ -1245,86 +1556,132 @@ extern "C" int sm_spectral_cluster_f32(const sm_spectral_args* a, void* stream) 
         if (sizes.k[i] > kw) kw = sizes.k[i];
     }
     const int B = a->B, n = a->n, m = a->n_neighbors - 1 < n - 1 ? a->n_neighbors - 1 : n - 1;
-    const sm::SpLayout l = sm::sp_layout(B, n, m, kw);
+    const bool large = n > sm::SP_MAXN;  // the streaming path: k-NN without the Gram matrix, the O(n m) graph build
+    const sm::SpLayout l = large ? sm::sp_layout_stream(B, n, m, kw) : sm::sp_layout(B, n, m, kw);
     SM_REQUIRE(a->workspace_bytes >= l.total && ((uintptr_t)a->workspace % 256 == 0),
                "sm_spectral_cluster_f32: workspace of %zu bytes, %zu needed (256-B aligned)", a->workspace_bytes, l.total);
+    bool knn_stream = large, graph_lists = large;
+#ifdef SM_TUNING
+    if (sm::sp_env_is("SM_SPECTRAL_KNN", "stream")) knn_stream = true;
+    if (sm::sp_env_is("SM_SPECTRAL_GRAPH", "lists") && (large || l.rev)) graph_lists = true;
+#endif
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)a->workspace;
     float* fs = (float*)(ws + l.fs);
-    float* gram = (float*)(ws + l.gram);
     int* idx = a->knn ? a->knn : (int*)(ws + l.idx);
     double* emb = a->embedding ? a->embedding : (double*)(ws + l.emb);
     const double nd = (double)n, Bd = (double)B;
     int rc;
-    {
-        sm::TapGuard tap(stream, "spectral: split_f16x2 + Gram gemm_f16x2", 2.0 * Bd * nd * nd * SM_EMBED, Bd * (nd * SM_EMBED * 8 + nd * nd * 4));
+    float* sq = (float*)(ws + l.sq);
+    int select_tap = -1;
+    if (knn_stream) {
+        // (flops: the three f16 products per multiply-add of every pair, as the tap of gemm_f16x2 counts its own)
+        sm::TapGuard tap(stream, "spectral: split_f16x2 + knn_stream", 2.0 * Bd * nd * nd * SM_EMBED, Bd * nd * SM_EMBED * 8);
         rc = sm_split_f16x2(a->features, SM_EMBED, fs, SM_EMBED, (int64_t)B * n, SM_EMBED, stream);
         if (rc) return rc;
-    sm_gemm_args g = {};
-    g.A = fs;
-    g.W = fs;
-    g.C = gram;
-    g.strideA = g.strideW = (int64_t)n * SM_EMBED;
-    g.strideC = (int64_t)n * n;
-    g.M = g.N = n;
-    g.K = SM_EMBED;
-    g.lda = g.ldw = SM_EMBED;
-    g.ldc = n;
-    g.batch = B;
-    g.epilogue = SM_EPI_BIAS;
-        rc = sm_gemm_f16x2(&g, 0, stream);
-        if (rc) return rc;
+        const int64_t rows = (int64_t)B * n;
+        hipLaunchKernelGGL(sm::knn_sqnorm_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(256), 0, st, fs, rows, sq);
+        const dim3 grid((n + sm::KS_ROWS - 1) / sm::KS_ROWS, B);
+        if (m <= 16) hipLaunchKernelGGL(sm::knn_stream_kernel<16>, grid, dim3(256), 0, st, fs, sq, n, m, idx);
+        else hipLaunchKernelGGL(sm::knn_stream_kernel<32>, grid, dim3(256), 0, st, fs, sq, n, m, idx);
+    } else {
+        float* gram = (float*)(ws + l.gram);
+        {
+            sm::TapGuard tap(stream, "spectral: split_f16x2 + Gram gemm_f16x2", 2.0 * Bd * nd * nd * SM_EMBED, Bd * (nd * SM_EMBED * 8 + nd * nd * 4));
+            rc = sm_split_f16x2(a->features, SM_EMBED, fs, SM_EMBED, (int64_t)B * n, SM_EMBED, stream);
+            if (rc) return rc;
+            sm_gemm_args g = {};
+            g.A = fs;
+            g.W = fs;
+            g.C = gram;
+            g.strideA = g.strideW = (int64_t)n * SM_EMBED;
+            g.strideC = (int64_t)n * n;
+            g.M = g.N = n;
+            g.K = SM_EMBED;
+            g.lda = g.ldw = SM_EMBED;
+            g.ldc = n;
+            g.batch = B;
+            g.epilogue = SM_EPI_BIAS;
+            rc = sm_gemm_f16x2(&g, 0, stream);
+            if (rc) return rc;
+        }
+        // (the Gram path's selection and bitmap graph build share one tap, as they always have)
+        select_tap = sm::tap_begin(stream, graph_lists ? "spectral: knn_select" : "spectral: knn_select + knn_graph", 0.0,
+                                   Bd * (nd * nd * 4 + (graph_lists ? 1.0 : 3.0) * nd * m * 4));
+        hipLaunchKernelGGL(sm::gram_diag_kernel, dim3((unsigned)(((int64_t)B * n + 255) / 256)), dim3(256), 0, st, gram, n, (int64_t)B * n, sq);
+        if (m <= 16)
+            hipLaunchKernelGGL(sm::knn_select_kernel<16>, dim3((n + 3) / 4, B), dim3(256), 0, st, gram, sq, n, m, idx);
+        else
+            hipLaunchKernelGGL(sm::knn_select_kernel<32>, dim3((n + 3) / 4, B), dim3(256), 0, st, gram, sq, n, m, idx);
     }
-    float* sq = (float*)(ws + l.sq);
-    int tap = sm::tap_begin(stream, "spectral: knn_select + knn_graph", 0.0, Bd * (nd * nd * 4 + 3.0 * nd * m * 4));
-    hipLaunchKernelGGL(sm::gram_diag_kernel, dim3((unsigned)(((int64_t)B * n + 255) / 256)), dim3(256), 0, st, gram, n, (int64_t)B * n, sq);
-    if (m <= 16)
-        hipLaunchKernelGGL(sm::knn_select_kernel<16>, dim3((n + 3) / 4, B), dim3(256), 0, st, gram, sq, n, m, idx);
-    else
-        hipLaunchKernelGGL(sm::knn_select_kernel<32>, dim3((n + 3) / 4, B), dim3(256), 0, st, gram, sq, n, m, idx);
-    if (hipMemsetAsync(ws + l.bits, 0, (size_t)B * n * ((n + 63) / 64) * 8, st) != hipSuccess) {
-        sm::set_error("sm_spectral_cluster_f32: hipMemsetAsync failed");
-        return SM_ELAUNCH;
+    if (graph_lists) {
+        if (select_tap >= 0) sm::tap_end(select_tap);
+        sm::TapGuard tap(stream, "spectral: knn_graph lists", 0.0, Bd * (6.0 * nd * m * 4 + nd * 24));
+        int* cnt = (int*)(ws + l.cnt);
+        if (hipMemsetAsync(cnt, 0, (size_t)B * n * 4, st) != hipSuccess) {
+            sm::set_error("sm_spectral_cluster_f32: hipMemsetAsync failed");
+            return SM_ELAUNCH;
+        }
+        const dim3 egrid((unsigned)(((int64_t)n * m + 255) / 256), B);
+        hipLaunchKernelGGL(sm::knn_indegree_kernel, egrid, dim3(256), 0, st, idx, n, m, cnt);
+        hipLaunchKernelGGL(sm::knn_lists_scan_kernel, dim3(B), dim3(sm::SP_THREADS), 0, st, idx, n, m, cnt, (int*)(ws + l.inptr),
+                           (int*)(ws + l.inlen), (int*)(ws + l.incol), (double*)(ws + l.isd));
+        hipLaunchKernelGGL(sm::knn_reverse_scatter_kernel, egrid, dim3(256), 0, st, idx, n, m, cnt, (const int*)(ws + l.inptr),
+                           (int*)(ws + l.rev));
+        hipLaunchKernelGGL(sm::knn_reverse_sort_kernel, dim3((n + 3) / 4, B), dim3(256), 0, st, n, m, (const int*)(ws + l.inptr),
+                           (const int*)(ws + l.inlen), (const int*)(ws + l.rev), (int*)(ws + l.incol));
+    } else {
+        const int tap = select_tap >= 0 ? select_tap : sm::tap_begin(stream, "spectral: knn_graph", 0.0, Bd * 3.0 * nd * m * 4);
+        if (hipMemsetAsync(ws + l.bits, 0, (size_t)B * n * ((n + 63) / 64) * 8, st) != hipSuccess) {
+            sm::set_error("sm_spectral_cluster_f32: hipMemsetAsync failed");
+            return SM_ELAUNCH;
+        }
+        hipLaunchKernelGGL(sm::knn_graph_kernel, dim3(B), dim3(sm::SP_THREADS), 0, st, idx, n, m, (unsigned long long*)(ws + l.bits),
+                           (int*)(ws + l.inptr), (int*)(ws + l.inlen), (int*)(ws + l.incol), (double*)(ws + l.isd));
+        sm::tap_end(tap);
     }
-    hipLaunchKernelGGL(sm::knn_graph_kernel, dim3(B), dim3(sm::SP_THREADS), 0, st, idx, n, m, (unsigned long long*)(ws + l.bits),
-                       (int*)(ws + l.inptr), (int*)(ws + l.inlen), (int*)(ws + l.incol), (double*)(ws + l.isd));
-    sm::tap_end(tap);
     const int degree = a->degree > 1 ? a->degree : 24, max_outer = a->max_outer > 0 ? a->max_outer : 60;
     const double tol = a->tol > 0.0 ? a->tol : 1e-9;
     {
         // 150 KB of LDS beside the kernel's static 3.2 KB (160 KB per workgroup on gfx950).  MODE 2 when graph (longest possible lists)
         // and both whole blocks fit; else MODE 3 with the most columns (4, 2 or 1) that leave room for the 2 n m list entries plus one
         // entry of padding per row (lists are padded to fours: the kernel sees the real lengths and falls back to MODE 0's steps when
-        // they do not fit); else MODE 0 with as many staged columns as fit.
+        // they do not fit); else MODE 0 with as many staged columns as fit (8, 4, 2, 1: n <= 19 199); else MODE 1, nothing staged.
         constexpr size_t LDS_MAX = 159744;  // 156 KB dynamic + the static 3.2 KB (3.4 in the stamps build) of 160
         int cg = 0, mode = 0;
         if (sm::sp_resident_bytes(n, m) <= LDS_MAX && (size_t)n * 64 <= 65535) { cg = 8; mode = 2; }  // (16-bit byte offsets of the rows)
         for (int c : {4, 2, 1})
             if (!cg && sm::sp_resident_ent_offset(n, c) + (size_t)(2 * m + 1) * n * 2 <= LDS_MAX && (size_t)n * c * 8 <= 65535) { cg = c; mode = 3; }
-#ifdef SM_TUNING  // the tuning build can force the graph-in-memory plan (tests: the plans give the same bits)
-        if (const char* e = getenv("SM_SPECTRAL_PLAN"))
-            if (atoi(e) == 0) { cg = 0; mode = 0; }
+#ifdef SM_TUNING  // the tuning build can force the graph-in-memory plans (tests: the plans give the same bits)
+        if (const char* e = getenv("SM_SPECTRAL_PLAN")) {
+            if (strcmp(e, "cg1") == 0) { cg = 1; mode = 0; }        // one staged column per step
+            else if (strcmp(e, "gather") == 0) { cg = 8; mode = 1; }  // nothing staged
+            else if (atoi(e) == 0) { cg = 0; mode = 0; }
+        }
 #endif
-        if (!cg) cg = (size_t)(n + 1) * 8 * 8 <= 153600 ? 8 : (size_t)(n + 1) * 4 * 8 <= 153600 ? 4 : 2;
-        const size_t lds = mode == 2 ? sm::sp_resident_bytes(n, m) : mode == 3 ? LDS_MAX : (size_t)(n + 1) * cg * 8;
+        if (!cg) {
+            for (int c : {8, 4, 2, 1})
+                if (!cg && (size_t)(n + 1) * c * 8 <= 153600) cg = c;
+            if (!cg) { cg = 8; mode = 1; }
+        }
+        const size_t lds = mode == 2 ? sm::sp_resident_bytes(n, m) : mode == 3 ? LDS_MAX : mode == 1 ? 0 : (size_t)(n + 1) * cg * 8;
         auto launch = [&](auto kern) {
-            static bool once = false;  // per instantiation (the lambda is instantiated per kernel type)
-            if (!once) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX);
-                once = true;
-            }
+            if (lds > 65536) sm::sp_allow_lds(reinterpret_cast<const void*>(kern), (int)LDS_MAX);
             hipLaunchKernelGGL(kern, dim3(B), dim3(sm::SP_THREADS), lds, st, (const int*)(ws + l.inptr), (const int*)(ws + l.inlen),
                                (const int*)(ws + l.incol),
                                (const double*)(ws + l.isd), n, m, kw, degree, max_outer, tol, (double*)(ws + l.blocks), a->eigenvalues, emb,
                                a->residuals, a->info, (unsigned)lds);
         };
         // (bytes: what ONE block mat-vec moves - the block read and written + the adjacency lists; the count of mat-vecs is data-dependent)
-        static const char* const names[4][3] = {{"spectral_embed_kernel<8, 0>", "spectral_embed_kernel<4, 0>", "spectral_embed_kernel<2, 0>"},
-                                                {"", "", ""},
-                                                {"spectral_embed_kernel<8, 2>", "", ""},
-                                                {"spectral_embed_kernel<1, 3>", "spectral_embed_kernel<4, 3>", "spectral_embed_kernel<2, 3>"}};
-        sm::TapGuard tap2(stream, names[mode][cg == 8 || cg == 1 ? 0 : cg == 4 ? 1 : 2], 0.0, Bd * (2.0 * nd * 8 * 8 + 2.0 * nd * m * 4));
+        static const char* const names[4][4] = {{"spectral_embed_kernel<8, 0>", "spectral_embed_kernel<4, 0>", "spectral_embed_kernel<2, 0>",
+                                                 "spectral_embed_kernel<1, 0>"},
+                                                {"spectral_embed_kernel<8, 1>", "", "", ""},
+                                                {"spectral_embed_kernel<8, 2>", "", "", ""},
+                                                {"spectral_embed_kernel<1, 3>", "spectral_embed_kernel<4, 3>", "spectral_embed_kernel<2, 3>", ""}};
+        const int slot = mode == 0 ? (cg == 8 ? 0 : cg == 4 ? 1 : cg == 2 ? 2 : 3) : (cg == 8 || cg == 1 ? 0 : cg == 4 ? 1 : 2);
+        sm::TapGuard tap2(stream, names[mode][slot], 0.0, Bd * (2.0 * nd * 8 * 8 + 2.0 * nd * m * 4));
         if (mode == 2) launch(&sm::spectral_embed_kernel<8, 2>);
+        else if (mode == 1) launch(&sm::spectral_embed_kernel<8, 1>);
         else if (mode == 3) {
             if (cg == 4) launch(&sm::spectral_embed_kernel<4, 3>);
             else if (cg == 2) launch(&sm::spectral_embed_kernel<2, 3>);
@@ -1332,7 +1689,8 @@ extern "C" int sm_spectral_cluster_f32(const sm_spectral_args* a, void* stream) 
         } else {
             if (cg == 8) launch(&sm::spectral_embed_kernel<8, 0>);
             else if (cg == 4) launch(&sm::spectral_embed_kernel<4, 0>);
-            else launch(&sm::spectral_embed_kernel<2, 0>);
+            else if (cg == 2) launch(&sm::spectral_embed_kernel<2, 0>);
+            else launch(&sm::spectral_embed_kernel<1, 0>);
         }
     }
     sm::TapGuard tap3(stream, "kmeans_embed_kernel", 0.0, Bd * nd * kw * 8 * a->n_sizes);

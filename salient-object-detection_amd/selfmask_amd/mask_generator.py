@@ -58,11 +58,14 @@ class _Files:
 class MaskGenerator:
     def __init__(self, cluster_sizes: Sequence[int] = VT.DEFAULT_CLUSTER_SIZES, cluster_type: str = VT.DEFAULT_CLUSTER_TYPE,
                  feature_types: Sequence[str] = ("dino",), use_gpu: bool = True, device: torch.device = torch.device("cuda:0"),
-                 network=None, batch_size: int = 128, n_neighbors: int = 10, streams: int = 3, workers: Optional[int] = None):
+                 network=None, batch_size: int = 128, n_neighbors: int = 10, streams: int = 3, workers: Optional[int] = None,
+                 max_stream_bytes: int = 16 << 30):
         """``batch_size``: the most images of ONE size clustered together - the eigen-solver runs one workgroup per image, so a launch
         takes about as long for 128 images as for 8 (profiles/r04_pseudo_masks_by_batch.log); ``streams``: batches in flight (one's
         eigen-solve, half of the CUs at 128 images, runs beside the next one's encoder); ``workers``: decode processes
-        (default: this rank's share of the host cores)."""
+        (default: this rank's share of the host cores); ``max_stream_bytes``: for patch grids of more than 8192 clustered points only
+        (n = 4 gh gw: above about 1024 x 512 pixels at P = 16), the batch is cut so that the clusterer's and the encoder's scratch
+        of one stream stay within this many bytes (default 16 GiB; at least one image per batch) - smaller grids keep ``batch_size``."""
         assert cluster_type in VT.CLUSTER_TYPES + ("kmeans",), cluster_type  # mask_generator.pyc@L30: ('k-means', 'spectral')
         unsupported = [f for f in feature_types if f != "dino"]
         if unsupported:
@@ -75,7 +78,7 @@ class MaskGenerator:
             raise RuntimeError("the MI355X build has no CPU path")
         self.cluster_sizes, self.cluster_type, self.feature_types = tuple(int(k) for k in cluster_sizes), cluster_type, list(feature_types)
         self.device, self.network, self.batch_size, self.n_neighbors = torch.device(device), network, int(batch_size), int(n_neighbors)
-        self.streams, self.workers = max(1, int(streams)), workers
+        self.streams, self.workers, self.max_stream_bytes = max(1, int(streams)), workers, int(max_stream_bytes)
         self._ring = None  # the streams of __call__, made once: the per-stream scratch of the clusterer (voting._arena) stays bounded
 
     # ---- mask_generator.pyc@L136-200 --------------------------------------------------------------------------------------------
@@ -87,16 +90,51 @@ class MaskGenerator:
         x = (rgb - np.asarray(MEAN, np.float32)) / np.asarray(STD, np.float32)               # normalize
         return torch.from_numpy(np.ascontiguousarray(x.transpose(2, 0, 1)))
 
-    def _batches(self, p_images: Sequence[str], pack: bool = False):
+    def _points(self, hw) -> int:
+        """points the clusterer sees for an image of size hw: the patch tokens of its padded grid after the x2 up-sample"""
+        P = self.network.encoder.patch_size
+        return 4 * (-(-int(hw[0]) // P)) * (-(-int(hw[1]) // P))
+
+    def _batch_cap(self, hw) -> int:
+        """the most images of the padded size of hw in one batch: ``batch_size``, and above 8192 clustered points as many as the
+        clusterer's plus the encoder's workspace allow within ``max_stream_bytes`` (both grow linearly in the batch)"""
+        n = self._points(hw)
+        if self.cluster_type != "spectral" or n <= VT.SPECTRAL_GRAM_POINTS:
+            return self.batch_size
+        from . import _native as N
+        lib = N.load()
+        P = self.network.encoder.patch_size
+        Hp, Wp = -(-int(hw[0]) // P) * P, -(-int(hw[1]) // P) * P
+        per = (lib.sm_spectral_workspace_bytes(1, n, self.n_neighbors, max(self.cluster_sizes))
+               + lib.sm_forward_workspace_bytes(self.network._weights(), 1, Hp, Wp))
+        return max(1, min(self.batch_size, self.max_stream_bytes // max(per, 1)))
+
+    def _plan(self, p_images: Sequence[str]):
+        """-> (paths, sizes, batches): the headers' sizes, every one checked against the clusterer's limits BEFORE anything is
+        queued (a file out of range raises ValueError naming it), grouped into native buckets of at most ``_batch_cap`` images"""
+        from .datasets import probe_size
+        from .pipeline import native_buckets
+        p_images = list(p_images)
+        sizes = [probe_size(p) for p in p_images]  # headers only
+        if self.cluster_type == "spectral":
+            for p, hw in zip(p_images, sizes):
+                n = self._points(hw)
+                if not VT.SPECTRAL_MIN_POINTS <= n <= VT.SPECTRAL_MAX_POINTS:
+                    raise ValueError(f"MaskGenerator: {p} ({hw[0]} x {hw[1]}) gives {n} points to the spectral clusterer "
+                                     f"({VT.SPECTRAL_MIN_POINTS} <= n <= {VT.SPECTRAL_MAX_POINTS}); nothing was run")
+        batches = []
+        for b in native_buckets(sizes, self.network.encoder.patch_size, self.batch_size):
+            cap = self._batch_cap(sizes[b[0]])
+            batches += [b[s:s + cap] for s in range(0, len(b), cap)]
+        return p_images, sizes, sorted(batches, key=len, reverse=True)
+
+    def _batches(self, p_images: Sequence[str], pack: bool = False, plan=None):
         """-> (file names, decoded uint8 RGB arrays) per batch of at most ``batch_size`` images that pad to ONE patch grid
         (``pipeline.native_buckets``: the evaluator's native-resolution buckets): the headers give the sizes, the decode processes of the
         input pipeline (decode_pool.py) the pixels, a few batches ahead of the device.  Largest buckets first.  ``pack``: the second item
         is (page-locked staging buffers of the batch, [(H, W)]) assembled on the loader's packing thread - what ``__call__`` consumes."""
-        from .datasets import probe_size
-        from .pipeline import PrefetchingLoader, native_buckets
-        p_images = list(p_images)
-        sizes = [probe_size(p) for p in p_images]  # headers only
-        batches = sorted(native_buckets(sizes, self.network.encoder.patch_size, self.batch_size), key=len, reverse=True)
+        from .pipeline import PrefetchingLoader
+        p_images, _sizes, batches = plan if plan is not None else self._plan(p_images)
         loader = PrefetchingLoader(_Files(p_images), range(len(p_images)), self.batch_size, workers=self.workers, batches=batches, pack=pack)
         for rgbs, _gts, idx in loader:
             yield [p_images[i].split("/")[-1] for i in idx], rgbs
@@ -138,7 +176,10 @@ class MaskGenerator:
         """Candidates and vote of one batch are queued on one stream of a ring and read back ``streams`` batches later: images are
         independent, so the result per file is what the reference's extract-everything-then-vote order gives.  ``comm`` (a
         ``distributed.TorchDistComm``): this rank takes files rank, rank + W, ... of the list (``shard_indices``, as the evaluator
-        shards its images), and every rank returns the codes of ALL files (one all-gather of the encoded shards at the end)."""
+        shards its images), and every rank returns the codes of ALL files (one all-gather of the encoded shards at the end).
+        Every file's size is checked before anything is queued: one out of the clusterer's range raises ValueError naming it."""
+        plan = self._plan(p_images)
+        p_images = plan[0]
         if comm is not None and comm.world_size > 1:
             from .distributed import gather_dicts, shard_indices
             assert encode, "the gather exchanges run-length codes"
@@ -169,7 +210,7 @@ class MaskGenerator:
                 for n, m, (h, w) in zip(names, votes.winners_host().numpy(), sizes):
                     result[n] = m[:h, :w].copy()
 
-        for names, rgbs in self._batches(p_images, pack=True):
+        for names, rgbs in self._batches(p_images, pack=True, plan=plan):
             with ring.next():
                 cands, sizes = self._candidates(rgbs)
                 votes = VT.vote_mask_batch_async(cands, remove_long_masks, remove_small_large_masks, winners="device" if encode else True,

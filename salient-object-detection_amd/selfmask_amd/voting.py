@@ -19,6 +19,8 @@ from . import _native as N
 
 # MaskGenerator.__init__ defaults and CLI choices (mask_generator.pyc@L21-38,255-294), pinned by tests/golden/evaluator_constants.json
 CLUSTER_TYPES = ("k-means", "spectral")
+SPECTRAL_MIN_POINTS, SPECTRAL_MAX_POINTS = 16, 32768  # what sm_spectral_cluster_f32 accepts (n % 4 == 0 always holds for 4 gh gw)
+SPECTRAL_GRAM_POINTS = 8192                           # the most points of the Gram-matrix path (above: the streaming path)
 DEFAULT_CLUSTER_SIZES = (2, 3, 4)
 DEFAULT_CLUSTER_TYPE = "spectral"
 FEATURE_UPSAMPLE = {"scale_factor": 2, "mode": "bilinear", "align_corners": True}  # mask_generator.pyc@L159
@@ -245,7 +247,9 @@ def spectral_cluster(features: torch.Tensor, cluster_sizes: Sequence[int] = (2, 
     """features (B, n, 384) fp32 on a HIP device -> labels (B, len(cluster_sizes), n) int32: normalised spectral clustering
     (csrc/spectral.hip), one eigen-solve per image shared by every cluster size.  ``return_details`` adds a dict with the
     neighbour lists ``knn`` (B, n, n_neighbors - 1), the ``eigenvalues`` (B, kw) of the normalised Laplacian, the ``embedding``
-    (B, n, kw), the eigen-``residuals`` (B, kw) and ``info`` (B, 4: outer iterations, block mat-vecs, converged, guard)."""
+    (B, n, kw), the eigen-``residuals`` (B, kw) and ``info`` (B, 4: outer iterations, block mat-vecs, converged, guard).
+    Up to 8192 points the neighbours come from a Gram matrix; above (to 32768) from a streaming k-NN that never forms one, with a
+    graph build and workspace linear in n (the same results up to fp32-grade ties of neighbour distances)."""
     if not features.is_cuda:
         raise RuntimeError("spectral_cluster (MI355X) needs its features on a HIP device; there is no CPU fallback")
     f = features.contiguous().float()
@@ -256,7 +260,7 @@ def spectral_cluster(features: torch.Tensor, cluster_sizes: Sequence[int] = (2, 
     lib = N.load()
     nbytes = lib.sm_spectral_workspace_bytes(B, n, n_neighbors, kw)
     if nbytes == 0:
-        raise ValueError(f"spectral_cluster: {n} points, n_neighbors {n_neighbors}, {kw} vectors (16 <= n <= 8192, n_neighbors 2..33, k <= 6)")
+        raise ValueError(f"spectral_cluster: {n} points, n_neighbors {n_neighbors}, {kw} vectors (16 <= n <= 32768, n_neighbors 2..33, k <= 6)")
     dev = f.device
     ws = _arena("spectral", nbytes, dev)
     labels = torch.empty((B, len(sizes), n), dtype=torch.int32, device=dev)
