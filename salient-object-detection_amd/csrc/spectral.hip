@@ -6,14 +6,15 @@
 // SpectralClustering(affinity="precomputed") evaluates - the third-party witness of oracle/cluster_oracle.py:
 //   1. Gram matrix G = F F^T of the n x 384 features on the matrix cores (sm_gemm_f16x2: fp32-grade products)
 //   2. k-NN: for every point the n_neighbors - 1 nearest others by (|f_i - f_j|^2, j)            [knn_select_kernel]
-//   3. W = (C + C^T) / 2 (C = connectivity, self loops dropped): the transposed lists by bitmap    [knn_graph_kernel]
+//   3. W = (C + C^T) / 2 (C = connectivity, self loops dropped): per point its own list, then the points that list it, in O(n m)
+//                                                    [knn_indegree / knn_lists_scan / knn_reverse_scatter / knn_reverse_sort]
 //   4. the kw smallest eigenpairs of L = I - D^-1/2 W D^-1/2 in fp64: Chebyshev-filtered subspace
 //      iteration (Zhou & Saad) on a block of 8 vectors, one workgroup per image; embedding rows
 //      u_i = v_i / sqrt(d_i)                                                                        [spectral_embed_kernel]
 //   5. k-means on the first k embedding columns for every requested k (ONE eigen-solve serves all)  [kmeans_embed_kernel]
 // Every sum runs in a fixed order (no floating-point atomics): labels are a function of the input alone.
-// Above 8192 points (to 32768) steps 1-3 become a streaming k-NN that never forms the Gram matrix [knn_stream_kernel] and an O(n m)
-// build of the same lists [knn_indegree / knn_lists_scan / knn_reverse_scatter / knn_reverse_sort]: the workspace is linear in n.
+// Above 8192 points (to 32768) steps 1-2 become a streaming k-NN that never forms the Gram matrix [knn_stream_kernel]: the workspace
+// is linear in n.
 #include "common.h"
 #include <mutex>
 #include <set>
@@ -150,94 +151,6 @@ __global__ __launch_bounds__(256) void knn_select_kernel(const float* __restrict
             for (int p = 0; p < CAP - 1; ++p) { key[p] = key[p + 1]; id[p] = id[p + 1]; }
             key[CAP - 1] = INFINITY;
             id[CAP - 1] = 0x7fffffff;
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// 3. the graph as ONE adjacency list per point: its own m neighbours (nearest first), then the points that list it in ascending
-// order - and 1 / sqrt(degree).  One workgroup per image: bit (t, i) of a n x n bitmap (zeroed by a memset on the stream) <- i
-// lists t (integer atomics: the RESULT does not depend on their order), then one wave per row turns the set bits into a list.
-// A pair listed from both ends appears twice, once per direction: W_ij = (C_ij + C_ji) / 2 is "every entry weighs 1/2", and
-// d_t = (m + in_degree_t) / 2.
-constexpr int SP_COL_SLACK = 32;  // ints readable past the last list (the gathers fetch 24 entries of a list whatever its length)
-__host__ __device__ inline int64_t sp_col_capacity(int n, int m) { return (int64_t)2 * n * m + 4 * (int64_t)n + SP_COL_SLACK; }
-
-__global__ __launch_bounds__(SP_THREADS) void knn_graph_kernel(const int* __restrict__ idx_all, int n, int m,
-                                                               unsigned long long* __restrict__ bits_all, int* __restrict__ ptr_all,
-                                                               int* __restrict__ len_all, int* __restrict__ col_all,
-                                                               double* __restrict__ isd_all) {
-    __shared__ int part[SP_THREADS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, img = blockIdx.x;
-    const int nw = (n + 63) / 64;
-    const int* idx = idx_all + (int64_t)img * n * m;
-    unsigned long long* bits = bits_all + (int64_t)img * n * nw;
-    int* ptr = ptr_all + (int64_t)img * (n + 1);
-    int* len = len_all + (int64_t)img * n;
-    int* col = col_all + (int64_t)img * sp_col_capacity(n, m);
-    double* isd = isd_all + (int64_t)img * n;
-    for (int64_t e = tid; e < (int64_t)n * m; e += SP_THREADS) {
-        const int i = (int)(e / m), t = idx[e];
-        atomicOr(&bits[(int64_t)t * nw + (i >> 6)], 1ull << (i & 63));
-    }
-    __threadfence();
-    __syncthreads();
-    // list length (m + in-degree, rounded up to 4 entries) of this thread's contiguous chunk of rows, exclusive scan over the workgroup
-    const int per = (n + SP_THREADS - 1) / SP_THREADS, r0 = tid * per, r1 = min(n, r0 + per);
-    int mine = 0;
-    for (int r = r0; r < r1; ++r) {
-        int c = 0;
-        for (int w = 0; w < nw; ++w) c += __popcll(__hip_atomic_load(&bits[(int64_t)r * nw + w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        len[r] = m + c;
-        isd[r] = 1.0 / sqrt(0.5 * (double)(m + c));
-        mine += (m + c + 3) & ~3;  // every list starts on a 16-B boundary: the gathers fetch four indices per load
-    }
-    part[tid] = mine;
-    __syncthreads();
-    if (wave == 0) {  // the partial sums: SP_WAVES per lane, then a 64-lane inclusive scan
-        int s[SP_WAVES], tot = 0;
-#pragma unroll
-        for (int q = 0; q < SP_WAVES; ++q) { s[q] = tot; tot += part[lane * SP_WAVES + q]; }
-        int inc = tot;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int v = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += v;
-        }
-        const int base = inc - tot;
-#pragma unroll
-        for (int q = 0; q < SP_WAVES; ++q) part[lane * SP_WAVES + q] = base + s[q];
-    }
-    __syncthreads();
-    {
-        int run = part[tid];
-        for (int r = r0; r < r1; ++r) {
-            ptr[r] = run;
-            run += (len[r] + 3) & ~3;
-        }
-        if (r1 == n && r0 < n) ptr[n] = run;
-    }
-    __syncthreads();
-    for (int r = wave; r < n; r += SP_WAVES) {
-        int pos = ptr[r];
-        if (lane < m) col[pos + lane] = idx[(int64_t)r * m + lane];  // m <= 32
-        pos += m;
-        for (int w0 = 0; w0 < nw; w0 += 64) {
-            const int w = w0 + lane;
-            unsigned long long word = w < nw ? __hip_atomic_load(&bits[(int64_t)r * nw + w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
-            const int c = __popcll(word);
-            int inc = c;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int v = __shfl_up(inc, o, 64);
-                if (lane >= o) inc += v;
-            }
-            int at = pos + inc - c;
-            while (word) {
-                col[at++] = w * 64 + __builtin_ctzll(word);
-                word &= word - 1;
-            }
-            pos += __shfl(inc, 63, 64);
         }
     }
 }
@@ -394,10 +307,15 @@ __global__ __launch_bounds__(256) void knn_stream_kernel(const float* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// 3'. the same adjacency lists as knn_graph_kernel in O(n m) (8192 < n; the tuning build's SM_SPECTRAL_GRAPH=lists at any n):
-// in-degrees by integer atomics (counts only: their order cannot change a result), an exclusive scan per image, the reverse edges
-// scattered behind each point's own m, then every reverse segment sorted ascending.  A point that lists another twice (the fallback
-// of a row with non-finite features can repeat an index) counts once, as the bitmap's one bit per pair does.
+// 3. the graph as ONE adjacency list per point: its own m neighbours (nearest first), then the points that list it in ascending
+// order - and 1 / sqrt(degree).  A pair listed from both ends appears twice, once per direction: W_ij = (C_ij + C_ji) / 2 is "every
+// entry weighs 1/2", and d_t = (m + in_degree_t) / 2.  Built in O(n m): in-degrees by integer atomics (counts only: their order
+// cannot change a result), an exclusive scan per image, the reverse edges scattered behind each point's own m, then every reverse
+// segment sorted ascending.  A point that lists another twice (the fallback of a row with non-finite features can repeat an index)
+// counts once.
+constexpr int SP_COL_SLACK = 32;  // ints readable past the last list (the gathers fetch 24 entries of a list whatever its length)
+__host__ __device__ inline int64_t sp_col_capacity(int n, int m) { return (int64_t)2 * n * m + 4 * (int64_t)n + SP_COL_SLACK; }
+
 __device__ __forceinline__ bool sp_first_listing(const int* li, int r, int t) {
     for (int q = 0; q < r; ++q)
         if (li[q] == t) return false;
@@ -412,8 +330,8 @@ __global__ __launch_bounds__(256) void knn_indegree_kernel(const int* __restrict
     if (sp_first_listing(idx + (int64_t)i * m, r, t)) atomicAdd(&cnt_all[(int64_t)blockIdx.y * n + t], 1);
 }
 
-// one workgroup per image: lengths, 1 / sqrt(d) and list starts exactly as knn_graph_kernel writes them, the own lists copied, and
-// the counts reset (they are the scatter's cursors next)
+// one workgroup per image: lengths (m + in-degree), 1 / sqrt(d) and list starts (every list on a 16-B boundary: the gathers fetch
+// four indices per load), the own lists copied, and the counts reset (they are the scatter's cursors next)
 __global__ __launch_bounds__(SP_THREADS) void knn_lists_scan_kernel(const int* __restrict__ idx_all, int n, int m, int* __restrict__ cnt_all,
                                                                     int* __restrict__ ptr_all, int* __restrict__ len_all,
                                                                     int* __restrict__ col_all, double* __restrict__ isd_all) {
@@ -1468,49 +1386,34 @@ __global__ __launch_bounds__(256) void gram_diag_kernel(const float* __restrict_
 
 static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-struct SpLayout {
-    size_t fs, gram, sq, idx, bits, inptr, inlen, incol, isd, blocks, emb, total;
-    size_t cnt, rev;  // the O(n m) graph build: in-degrees / cursors, the scattered reverse edges (streaming layout only)
-};
+// The features in F16X2 form, the Gram matrix (n <= 8192 only), norms, lists, graph, the two blocks of the eigen-solver, the embedding.
+struct SpLayout { size_t fs, gram, sq, idx, cnt, inptr, inlen, incol, rev, isd, blocks, emb, total; };
 static SpLayout sp_layout(int B, int n, int m, int kw) {
-    SpLayout l;
-    size_t o = 0;
-    const size_t nw = (n + 63) / 64;
-    l.fs = o;     o += al256((size_t)B * n * SM_EMBED * 4);
-    l.gram = o;   o += al256((size_t)B * n * n * 4);
-    l.sq = o;     o += al256((size_t)B * n * 4);
-    l.idx = o;    o += al256((size_t)B * n * m * 4);
-    l.bits = o;   o += al256((size_t)B * n * nw * 8);
-    l.inptr = o;  o += al256((size_t)B * (n + 1) * 4);
-    l.inlen = o;  o += al256((size_t)B * n * 4);
-    l.incol = o;  o += al256((size_t)B * sp_col_capacity(n, m) * 4);
-    l.isd = o;    o += al256((size_t)B * n * 8);
-    l.blocks = o; o += al256((size_t)B * 2 * n * SP_B * 8);
-    l.emb = o;    o += al256((size_t)B * n * kw * 8);
-    l.total = o;
-    // the tuning build's forced O(n m) graph build borrows the Gram matrix (read before it) and the bitmap (unused) - where they hold it
-    l.cnt = l.bits;
-    l.rev = (size_t)sp_col_capacity(n, m) <= (size_t)n * n ? l.gram : 0;  // (0: no room - offset 0 is the features')
-    return l;
-}
-// 8192 < n: nothing quadratic - the features in F16X2 form, norms, lists, graph, the two blocks of the eigen-solver, the embedding
-static SpLayout sp_layout_stream(int B, int n, int m, int kw) {
+    const bool gram = n <= SP_MAXN;
+    const size_t col = (size_t)B * sp_col_capacity(n, m) * 4;
     SpLayout l = {};
     size_t o = 0;
     l.fs = o;     o += al256((size_t)B * n * SM_EMBED * 4);
+    if (gram) { l.gram = o; o += al256((size_t)B * n * n * 4); }
     l.sq = o;     o += al256((size_t)B * n * 4);
     l.idx = o;    o += al256((size_t)B * n * m * 4);
-    l.cnt = o;    o += al256((size_t)B * n * 4);
+    // the in-degrees / cursors; with the Gram matrix at the size of the n x n bitmap that held the graph before the O(n m) build (the
+    // workspace sizes, and the batch caps resting on them, stay as they were)
+    l.cnt = o;    o += al256((size_t)B * n * (gram ? (size_t)(n + 63) / 64 * 8 : 4));
     l.inptr = o;  o += al256((size_t)B * (n + 1) * 4);
     l.inlen = o;  o += al256((size_t)B * n * 4);
-    l.incol = o;  o += al256((size_t)B * sp_col_capacity(n, m) * 4);
-    l.rev = o;    o += al256((size_t)B * sp_col_capacity(n, m) * 4);
+    l.incol = o;  o += al256(col);
+    // the scattered reverse edges: with the Gram matrix in the features (n * 1536 B per image >= the col capacity for m <= 32; dead
+    // once the k-NN lists exist)
+    if (gram) l.rev = l.fs;
+    else { l.rev = o; o += al256(col); }
     l.isd = o;    o += al256((size_t)B * n * 8);
     l.blocks = o; o += al256((size_t)B * 2 * n * SP_B * 8);
     l.emb = o;    o += al256((size_t)B * n * kw * 8);
     l.total = o;
     return l;
 }
+static_assert(SM_EMBED * 4 >= (2 * SP_MAXM + 4) * 4 + SP_COL_SLACK * 4, "the reverse edges fit the features' room");
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device): the attribute belongs to the current device, and
 // several host threads may launch at once
@@ -1526,19 +1429,50 @@ static void sp_allow_lds(const void* kern, int bytes) {
     }
 }
 
-#ifdef SM_TUNING  // the tuning build's forcings (tests run each piece of the streaming path at small n against the Gram path)
-static bool sp_env_is(const char* name, const char* value) {
-    const char* e = getenv(name);
-    return e && strcmp(e, value) == 0;
-}
+// The eigen-solver's plan.  150 KB of LDS beside the kernel's static 3.2 KB (160 KB per workgroup on gfx950).  MODE 2 when graph
+// (longest possible lists) and both whole blocks fit; else MODE 3 with the most columns (4, 2 or 1) that leave room for the 2 n m list
+// entries plus one entry of padding per row (lists are padded to fours: the kernel sees the real lengths and falls back to MODE 0's
+// steps when they do not fit); else MODE 0 with as many staged columns as fit (8, 4, 2, 1: n <= 19 199); else MODE 1, nothing staged.
+constexpr size_t SP_LDS_MAX = 159744;  // 156 KB dynamic + the static 3.2 KB (3.4 in the stamps build) of 160
+struct SpPlan { int mode, cg; size_t lds; };
+static SpPlan sp_plan(int n, int m) {
+    SpPlan p = {0, 0, 0};
+    if (sp_resident_bytes(n, m) <= SP_LDS_MAX && (size_t)n * 64 <= 65535) p = {2, 8, 0};  // (16-bit byte offsets of the rows)
+    for (int c : {4, 2, 1})
+        if (!p.cg && sp_resident_ent_offset(n, c) + (size_t)(2 * m + 1) * n * 2 <= SP_LDS_MAX && (size_t)n * c * 8 <= 65535) p = {3, c, 0};
+#ifdef SM_TUNING  // the tuning build can force the graph-in-memory plans (tests: the plans give the same bits)
+    if (const char* e = getenv("SM_SPECTRAL_PLAN")) {
+        if (strcmp(e, "cg1") == 0) p = {0, 1, 0};        // one staged column per step
+        else if (strcmp(e, "gather") == 0) p = {1, 8, 0};  // nothing staged
+        else if (atoi(e) == 0) p = {0, 0, 0};
+    }
 #endif
+    if (!p.cg) {
+        for (int c : {8, 4, 2, 1})
+            if (!p.cg && (size_t)(n + 1) * c * 8 <= 153600) p.cg = c;
+        if (!p.cg) p = {1, 8, 0};
+    }
+    p.lds = p.mode == 2 ? sp_resident_bytes(n, m) : p.mode == 3 ? SP_LDS_MAX : p.mode == 1 ? 0 : (size_t)(n + 1) * p.cg * 8;
+    return p;
+}
+
+// every instantiation of the eigen-solver, by plan, with its name as the timing taps report it
+struct SpEmbedKernel {
+    int mode, cg;
+    decltype(&spectral_embed_kernel<8, 0>) kern;
+    const char* name;
+};
+#define SP_EMBED(CG, MODE) {MODE, CG, &spectral_embed_kernel<CG, MODE>, "spectral_embed_kernel<" #CG ", " #MODE ">"}
+static const SpEmbedKernel sp_embed_kernels[] = {SP_EMBED(8, 2), SP_EMBED(4, 3), SP_EMBED(2, 3), SP_EMBED(1, 3), SP_EMBED(8, 0),
+                                                 SP_EMBED(4, 0), SP_EMBED(2, 0), SP_EMBED(1, 0), SP_EMBED(8, 1)};
+#undef SP_EMBED
 
 }  // namespace sm
 
 extern "C" size_t sm_spectral_workspace_bytes(int32_t B, int32_t n, int32_t n_neighbors, int32_t kw) {
     if (B < 1 || n < 2 * sm::SP_B || n > sm::SP_MAXN_L || n_neighbors < 2 || n_neighbors - 1 > sm::SP_MAXM || kw < 1 || kw > 6) return 0;
     const int m = n_neighbors - 1 < n - 1 ? n_neighbors - 1 : n - 1;
-    return (n <= sm::SP_MAXN ? sm::sp_layout(B, n, m, kw) : sm::sp_layout_stream(B, n, m, kw)).total;
+    return sm::sp_layout(B, n, m, kw).total;
 }
 
 extern "C" int sm_spectral_cluster_f32(const sm_spectral_args* a, void* stream) {
@@ -1556,14 +1490,12 @@ extern "C" int sm_spectral_cluster_f32(const sm_spectral_args* a, void* stream) 
         if (sizes.k[i] > kw) kw = sizes.k[i];
     }
     const int B = a->B, n = a->n, m = a->n_neighbors - 1 < n - 1 ? a->n_neighbors - 1 : n - 1;
-    const bool large = n > sm::SP_MAXN;  // the streaming path: k-NN without the Gram matrix, the O(n m) graph build
-    const sm::SpLayout l = large ? sm::sp_layout_stream(B, n, m, kw) : sm::sp_layout(B, n, m, kw);
+    const sm::SpLayout l = sm::sp_layout(B, n, m, kw);
     SM_REQUIRE(a->workspace_bytes >= l.total && ((uintptr_t)a->workspace % 256 == 0),
                "sm_spectral_cluster_f32: workspace of %zu bytes, %zu needed (256-B aligned)", a->workspace_bytes, l.total);
-    bool knn_stream = large, graph_lists = large;
-#ifdef SM_TUNING
-    if (sm::sp_env_is("SM_SPECTRAL_KNN", "stream")) knn_stream = true;
-    if (sm::sp_env_is("SM_SPECTRAL_GRAPH", "lists") && (large || l.rev)) graph_lists = true;
+    bool knn_stream = n > sm::SP_MAXN;  // k-NN without the Gram matrix
+#ifdef SM_TUNING  // the tuning build can force it at any n (tests: against the Gram path)
+    if (const char* e = getenv("SM_SPECTRAL_KNN")) knn_stream = knn_stream || strcmp(e, "stream") == 0;
 #endif
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)a->workspace;
@@ -1573,7 +1505,6 @@ extern "C" int sm_spectral_cluster_f32(const sm_spectral_args* a, void* stream) 
     const double nd = (double)n, Bd = (double)B;
     int rc;
     float* sq = (float*)(ws + l.sq);
-    int select_tap = -1;
     if (knn_stream) {
         // (flops: the three f16 products per multiply-add of every pair, as the tap of gemm_f16x2 counts its own)
         sm::TapGuard tap(stream, "spectral: split_f16x2 + knn_stream", 2.0 * Bd * nd * nd * SM_EMBED, Bd * nd * SM_EMBED * 8);
@@ -1605,18 +1536,15 @@ extern "C" int sm_spectral_cluster_f32(const sm_spectral_args* a, void* stream) 
             rc = sm_gemm_f16x2(&g, 0, stream);
             if (rc) return rc;
         }
-        // (the Gram path's selection and bitmap graph build share one tap, as they always have)
-        select_tap = sm::tap_begin(stream, graph_lists ? "spectral: knn_select" : "spectral: knn_select + knn_graph", 0.0,
-                                   Bd * (nd * nd * 4 + (graph_lists ? 1.0 : 3.0) * nd * m * 4));
+        sm::TapGuard tap(stream, "spectral: knn_select", 0.0, Bd * (nd * nd * 4 + nd * m * 4));
         hipLaunchKernelGGL(sm::gram_diag_kernel, dim3((unsigned)(((int64_t)B * n + 255) / 256)), dim3(256), 0, st, gram, n, (int64_t)B * n, sq);
         if (m <= 16)
             hipLaunchKernelGGL(sm::knn_select_kernel<16>, dim3((n + 3) / 4, B), dim3(256), 0, st, gram, sq, n, m, idx);
         else
             hipLaunchKernelGGL(sm::knn_select_kernel<32>, dim3((n + 3) / 4, B), dim3(256), 0, st, gram, sq, n, m, idx);
     }
-    if (graph_lists) {
-        if (select_tap >= 0) sm::tap_end(select_tap);
-        sm::TapGuard tap(stream, "spectral: knn_graph lists", 0.0, Bd * (6.0 * nd * m * 4 + nd * 24));
+    {
+        sm::TapGuard tap(stream, "spectral: knn_graph", 0.0, Bd * (6.0 * nd * m * 4 + nd * 24));
         int* cnt = (int*)(ws + l.cnt);
         if (hipMemsetAsync(cnt, 0, (size_t)B * n * 4, st) != hipSuccess) {
             sm::set_error("sm_spectral_cluster_f32: hipMemsetAsync failed");
@@ -1630,68 +1558,19 @@ extern "C" int sm_spectral_cluster_f32(const sm_spectral_args* a, void* stream) 
                            (int*)(ws + l.rev));
         hipLaunchKernelGGL(sm::knn_reverse_sort_kernel, dim3((n + 3) / 4, B), dim3(256), 0, st, n, m, (const int*)(ws + l.inptr),
                            (const int*)(ws + l.inlen), (const int*)(ws + l.rev), (int*)(ws + l.incol));
-    } else {
-        const int tap = select_tap >= 0 ? select_tap : sm::tap_begin(stream, "spectral: knn_graph", 0.0, Bd * 3.0 * nd * m * 4);
-        if (hipMemsetAsync(ws + l.bits, 0, (size_t)B * n * ((n + 63) / 64) * 8, st) != hipSuccess) {
-            sm::set_error("sm_spectral_cluster_f32: hipMemsetAsync failed");
-            return SM_ELAUNCH;
-        }
-        hipLaunchKernelGGL(sm::knn_graph_kernel, dim3(B), dim3(sm::SP_THREADS), 0, st, idx, n, m, (unsigned long long*)(ws + l.bits),
-                           (int*)(ws + l.inptr), (int*)(ws + l.inlen), (int*)(ws + l.incol), (double*)(ws + l.isd));
-        sm::tap_end(tap);
     }
-    const int degree = a->degree > 1 ? a->degree : 24, max_outer = a->max_outer > 0 ? a->max_outer : 60;
-    const double tol = a->tol > 0.0 ? a->tol : 1e-9;
     {
-        // 150 KB of LDS beside the kernel's static 3.2 KB (160 KB per workgroup on gfx950).  MODE 2 when graph (longest possible lists)
-        // and both whole blocks fit; else MODE 3 with the most columns (4, 2 or 1) that leave room for the 2 n m list entries plus one
-        // entry of padding per row (lists are padded to fours: the kernel sees the real lengths and falls back to MODE 0's steps when
-        // they do not fit); else MODE 0 with as many staged columns as fit (8, 4, 2, 1: n <= 19 199); else MODE 1, nothing staged.
-        constexpr size_t LDS_MAX = 159744;  // 156 KB dynamic + the static 3.2 KB (3.4 in the stamps build) of 160
-        int cg = 0, mode = 0;
-        if (sm::sp_resident_bytes(n, m) <= LDS_MAX && (size_t)n * 64 <= 65535) { cg = 8; mode = 2; }  // (16-bit byte offsets of the rows)
-        for (int c : {4, 2, 1})
-            if (!cg && sm::sp_resident_ent_offset(n, c) + (size_t)(2 * m + 1) * n * 2 <= LDS_MAX && (size_t)n * c * 8 <= 65535) { cg = c; mode = 3; }
-#ifdef SM_TUNING  // the tuning build can force the graph-in-memory plans (tests: the plans give the same bits)
-        if (const char* e = getenv("SM_SPECTRAL_PLAN")) {
-            if (strcmp(e, "cg1") == 0) { cg = 1; mode = 0; }        // one staged column per step
-            else if (strcmp(e, "gather") == 0) { cg = 8; mode = 1; }  // nothing staged
-            else if (atoi(e) == 0) { cg = 0; mode = 0; }
-        }
-#endif
-        if (!cg) {
-            for (int c : {8, 4, 2, 1})
-                if (!cg && (size_t)(n + 1) * c * 8 <= 153600) cg = c;
-            if (!cg) { cg = 8; mode = 1; }
-        }
-        const size_t lds = mode == 2 ? sm::sp_resident_bytes(n, m) : mode == 3 ? LDS_MAX : mode == 1 ? 0 : (size_t)(n + 1) * cg * 8;
-        auto launch = [&](auto kern) {
-            if (lds > 65536) sm::sp_allow_lds(reinterpret_cast<const void*>(kern), (int)LDS_MAX);
-            hipLaunchKernelGGL(kern, dim3(B), dim3(sm::SP_THREADS), lds, st, (const int*)(ws + l.inptr), (const int*)(ws + l.inlen),
-                               (const int*)(ws + l.incol),
-                               (const double*)(ws + l.isd), n, m, kw, degree, max_outer, tol, (double*)(ws + l.blocks), a->eigenvalues, emb,
-                               a->residuals, a->info, (unsigned)lds);
-        };
+        const int degree = a->degree > 1 ? a->degree : 24, max_outer = a->max_outer > 0 ? a->max_outer : 60;
+        const double tol = a->tol > 0.0 ? a->tol : 1e-9;
+        const sm::SpPlan p = sm::sp_plan(n, m);
+        const sm::SpEmbedKernel* k = sm::sp_embed_kernels;
+        while (k->mode != p.mode || k->cg != p.cg) ++k;  // (every plan has its entry)
         // (bytes: what ONE block mat-vec moves - the block read and written + the adjacency lists; the count of mat-vecs is data-dependent)
-        static const char* const names[4][4] = {{"spectral_embed_kernel<8, 0>", "spectral_embed_kernel<4, 0>", "spectral_embed_kernel<2, 0>",
-                                                 "spectral_embed_kernel<1, 0>"},
-                                                {"spectral_embed_kernel<8, 1>", "", "", ""},
-                                                {"spectral_embed_kernel<8, 2>", "", "", ""},
-                                                {"spectral_embed_kernel<1, 3>", "spectral_embed_kernel<4, 3>", "spectral_embed_kernel<2, 3>", ""}};
-        const int slot = mode == 0 ? (cg == 8 ? 0 : cg == 4 ? 1 : cg == 2 ? 2 : 3) : (cg == 8 || cg == 1 ? 0 : cg == 4 ? 1 : 2);
-        sm::TapGuard tap2(stream, names[mode][slot], 0.0, Bd * (2.0 * nd * 8 * 8 + 2.0 * nd * m * 4));
-        if (mode == 2) launch(&sm::spectral_embed_kernel<8, 2>);
-        else if (mode == 1) launch(&sm::spectral_embed_kernel<8, 1>);
-        else if (mode == 3) {
-            if (cg == 4) launch(&sm::spectral_embed_kernel<4, 3>);
-            else if (cg == 2) launch(&sm::spectral_embed_kernel<2, 3>);
-            else launch(&sm::spectral_embed_kernel<1, 3>);
-        } else {
-            if (cg == 8) launch(&sm::spectral_embed_kernel<8, 0>);
-            else if (cg == 4) launch(&sm::spectral_embed_kernel<4, 0>);
-            else if (cg == 2) launch(&sm::spectral_embed_kernel<2, 0>);
-            else launch(&sm::spectral_embed_kernel<1, 0>);
-        }
+        sm::TapGuard tap(stream, k->name, 0.0, Bd * (2.0 * nd * 8 * 8 + 2.0 * nd * m * 4));
+        if (p.lds > 65536) sm::sp_allow_lds(reinterpret_cast<const void*>(k->kern), (int)sm::SP_LDS_MAX);
+        hipLaunchKernelGGL(k->kern, dim3(B), dim3(sm::SP_THREADS), p.lds, st, (const int*)(ws + l.inptr), (const int*)(ws + l.inlen),
+                           (const int*)(ws + l.incol), (const double*)(ws + l.isd), n, m, kw, degree, max_outer, tol, (double*)(ws + l.blocks),
+                           a->eigenvalues, emb, a->residuals, a->info, (unsigned)p.lds);
     }
     sm::TapGuard tap3(stream, "kmeans_embed_kernel", 0.0, Bd * nd * kw * 8 * a->n_sizes);
     hipLaunchKernelGGL(sm::kmeans_embed_kernel, dim3(a->n_sizes, B), dim3(sm::SP_THREADS), 0, st, emb, n, kw, sizes, a->n_sizes,

@@ -1,6 +1,7 @@
 """Spectral clustering above 8192 points (csrc/spectral.hip: streaming k-NN on the matrix cores, the O(n m) graph build, the
 eigen-solver's one-column and gathering plans): every stage against its restatement on the device's own graph, separable features
-as the true partition, and - through the tuning build - each new piece at small n against the Gram-matrix path."""
+as the true partition, the graph build's results pinned at small n, and - through the tuning build - the streaming k-NN and the
+eigen-solver's plans at small n against the Gram-matrix path and the default plan."""
 import json
 import os
 import subprocess
@@ -121,28 +122,38 @@ def tuning_run(code, env):
     return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
 
 
+def result_hashes(grids):
+    """SHA-1 of labels, eigenvalues, embedding, residuals and iteration counts of a batch of two scenes per g x g grid"""
+    import hashlib
+    out = {}
+    for g in grids:
+        x = torch.from_numpy(np.stack([scene(g, 3, 60 + s)[0] for s in range(2)])).to(DEV)
+        labels, det = VT.spectral_cluster(x, (2, 3, 4), return_details=True)
+        h = hashlib.sha1()
+        for t in (labels, det["eigenvalues"], det["embedding"], det["residuals"], det["info"][:, :3]):
+            h.update(t.cpu().numpy().tobytes())
+        out[str(g)] = h.hexdigest()
+    return out
+
+
 HASHES = r"""
-import hashlib, json, os, sys
-import numpy as np, torch
+import json, os, sys
 sys.path[:0] = [os.path.join(sys.argv[1], "salient-object-detection_amd"), sys.argv[1], os.path.join(sys.argv[1], "tests")]
-from selfmask_amd import voting as VT
-from test_oracle_spectral import scene
-out = {}
-for g in (28, 44, 56):
-    x = torch.from_numpy(np.stack([scene(g, 3, 60 + s)[0] for s in range(2)])).cuda()
-    labels, det = VT.spectral_cluster(x, (2, 3, 4), return_details=True)
-    h = hashlib.sha1()
-    for t in (labels, det["eigenvalues"], det["embedding"], det["residuals"], det["info"][:, :3]):
-        h.update(t.cpu().numpy().tobytes())
-    out[str(g)] = h.hexdigest()
-print("RESULT " + json.dumps(out))
+from test_hip_spectral_large import result_hashes
+print("RESULT " + json.dumps(result_hashes((28, 44, 56))))
 """
+
+# result_hashes of the library whose graph had a second builder (an n x n bitmap at n <= 8192), on an MI355X: n = 16 (too small for
+# that library's list build to run), 100, 784, 1936 and 3136
+PINNED_HASHES = {"4": "d8669297eece5e9f0eb4aedc5f1f9d59f7825e82", "10": "36c7e00310d71b075b4e6e35beb99d739df2500e",
+                 "28": "ec4a7dec049cb86974961a1adb1a25a9582734c9", "44": "1bb626eb05cf67785e6d79cadd27a93c91e32066",
+                 "56": "ab432744c71f25f24315e39b7eb82c06491fe963"}
 
 
 def test_list_graph_build_gives_the_same_bits():
-    """SM_SPECTRAL_GRAPH=lists (in-degree count, scan, scatter, sorted reverse segments) against the bitmap build at n = 784, 1936,
-    3136: the same lists, so the same labels, eigenvalues, embedding and residuals bit for bit"""
-    assert tuning_run(HASHES, {"SM_SPECTRAL_GRAPH": "lists"}) == tuning_run(HASHES, {})
+    """the O(n m) list build (in-degree count, scan, scatter, sorted reverse segments) at n <= 8192: the same lists as the bitmap
+    build it replaced, so the same labels, eigenvalues, embedding and residuals bit for bit"""
+    assert result_hashes((4, 10, 28, 44, 56)) == PINNED_HASHES
 
 
 @pytest.mark.parametrize("plan", ["cg1", "gather"])
