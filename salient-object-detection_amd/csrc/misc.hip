@@ -117,11 +117,17 @@ __global__ __launch_bounds__(256) void upsample2x_kernel(const float* __restrict
         const float4 p01 = *reinterpret_cast<const float4*>(base + ((int64_t)y0 * gw + x1) * SM_EMBED);
         const float4 p10 = *reinterpret_cast<const float4*>(base + ((int64_t)y1 * gw + x0) * SM_EMBED);
         const float4 p11 = *reinterpret_cast<const float4*>(base + ((int64_t)y1 * gw + x1) * SM_EMBED);
+        // the blend with its fused multiply-adds spelled out: left to the compiler, the fp32 and the F16X2 instantiation were
+        // contracted differently and the F16X2 tokens were not split(fp32 tokens) in the last bit
+        const auto blend = [&](float a00, float a01, float a10, float a11) {
+            const float top = __builtin_fmaf(lx0, a00, lx1 * a01), bot = __builtin_fmaf(lx0, a10, lx1 * a11);
+            return __builtin_fmaf(ly0, top, ly1 * bot);
+        };
         float4 o;
-        o.x = ly0 * (lx0 * p00.x + lx1 * p01.x) + ly1 * (lx0 * p10.x + lx1 * p11.x);
-        o.y = ly0 * (lx0 * p00.y + lx1 * p01.y) + ly1 * (lx0 * p10.y + lx1 * p11.y);
-        o.z = ly0 * (lx0 * p00.z + lx1 * p01.z) + ly1 * (lx0 * p10.z + lx1 * p11.z);
-        o.w = ly0 * (lx0 * p00.w + lx1 * p01.w) + ly1 * (lx0 * p10.w + lx1 * p11.w);
+        o.x = blend(p00.x, p01.x, p10.x, p11.x);
+        o.y = blend(p00.y, p01.y, p10.y, p11.y);
+        o.z = blend(p00.z, p01.z, p10.z, p11.z);
+        o.w = blend(p00.w, p01.w, p10.w, p11.w);
         if constexpr (SPLIT) {
             const float vv[4] = {o.x, o.y, o.z, o.w};
             store_f16x2_4(up + px * SM_EMBED, c, vv);
