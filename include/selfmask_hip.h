@@ -329,7 +329,6 @@ int sm_evaluate_masks_f32(const sm_eval_args* args, void* stream);
 int sm_upsample_selected_f64(const float* masks, int64_t mask_stride_b, const float* rows, int32_t sel_col, double* out,
                              int32_t B, int32_t mh, int32_t mw, int32_t OH, int32_t OW, void* stream);
 int sm_mask_u8_to_f32(const uint8_t* src, float* dst, int64_t n, void* stream);
-
 /* ---- pseudo-mask voting (BASELINE.json configs[4]) -------------------------------------------------------
  * masks (M, H, W) uint8 0/1, M <= 64 candidate masks of ONE image.  filter_masks (utils/misc.py:285-314; mask_to_bbox
  * :269-282): a candidate is dropped when it predicts nothing, when (remove_long) its bounding box spans the full height or
@@ -435,6 +434,40 @@ int sm_bilateral_solver_f64(const sm_bilateral_args* args, void* stream);
  * binary (n,H,W) u8, info (n,4) or NULL, workspace >= n * sm_bilateral_workspace_bytes(...).  The solver's long kernels
  * use one workgroup per image, so a batch fills the GPU where a single solve occupies one CU. */
 int sm_bilateral_solver_batch_f64(const sm_bilateral_args* args, int32_t n_images, void* stream);
+
+/* n_images solves of DIFFERENT sizes in one launch sequence (the images of a native-resolution token-grid bucket).  Image i is
+ * described by one table entry; sigmas, lam, cg_tol, cg_maxiter and confidence are those of `args` for every image, args->H / W are
+ * unused.  The launch grids are sized by the largest image and a workgroup past its own image's extent leaves at once.  Every image
+ * gives the bits of its own sm_bilateral_solver_f64 call - soft, binary and info - whatever the other images and their order. */
+typedef struct sm_bilateral_image {
+    int64_t img_off;  /* byte offset of this image's (H, W, 3) uint8 RGB inside args->img (sm_pre_image.off fits as it is)      */
+    int64_t px_off;   /* element offset of this image's H*W values inside args->target / soft / binary (packed, row pitch W)    */
+    int64_t ws_off;   /* byte offset of this image's workspace inside args->workspace, a multiple of 256                        */
+    int32_t H, W;
+} sm_bilateral_image;
+/* host only: fills ws_off of every entry (workspaces end to end, in table order) and returns the total; 0 = an empty image or a
+ * size / sigma the lattice cannot take (as sm_bilateral_workspace_bytes) */
+size_t sm_bilateral_mixed_workspace_bytes(sm_bilateral_image* images, int32_t n_images, double sigma_spatial, double sigma_luma,
+                                          double sigma_chroma);
+/* images_host sizes the launch grids and is checked against args->workspace_bytes; images_dev is the same table in device memory,
+ * which the kernels read - the caller uploads it on `stream` (or earlier): this function copies and allocates nothing, so it can be
+ * captured into a graph.  info (n, 4) or NULL. */
+int sm_bilateral_solver_mixed_f64(const sm_bilateral_args* args, const sm_bilateral_image* images_host,
+                                  const sm_bilateral_image* images_dev, int32_t n_images, void* stream);
+
+/* The evaluator's refinement glue at native resolution, where every image of the batch has its own size: `images` is the DEVICE
+ * table of sm_bilateral_solver_mixed_f64 (H, W and px_off are read).
+ * sm_upsample_selected_native_f64: image b's selected mask (sel_col as sm_upsample_selected_f64) in the evaluator's reference
+ * mode, F.interpolate(mask, scale_factor=scale, mode="bilinear")[..., :H_b, :W_b] - the arithmetic of sm_evaluate_masks_f32 with
+ * scale > 0, so the value that call scored, cast to double - written packed (row pitch W_b) at out + px_off_b: the solver's
+ * target.  max_pixels = the largest H_b * W_b sizes the grid.
+ * sm_mask_planes_u8_to_f32: packed 0/1 planes (image b at src + px_off_b, H_b x W_b) into the top-left corners of a ZEROED
+ * (B, Hmax, Wmax) fp32 tensor: a one-query mask_pred for sm_evaluate_masks_f32 with scale = 1. */
+int sm_upsample_selected_native_f64(const float* masks, int64_t mask_stride_b, const float* rows, int32_t sel_col,
+                                    const sm_bilateral_image* images, double* out, int32_t B, int32_t mh, int32_t mw, float scale,
+                                    int32_t max_pixels, void* stream);
+int sm_mask_planes_u8_to_f32(const uint8_t* src, const sm_bilateral_image* images, float* dst, int32_t B, int32_t Hmax,
+                             int32_t Wmax, int32_t max_pixels, void* stream);
 
 /* ---- whole forward --------------------------------------------------------------------------------------------- */
 typedef struct sm_enc_layer {

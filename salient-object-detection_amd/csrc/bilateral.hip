@@ -20,6 +20,7 @@
 //     run meets the row above for the first time or crosses a wave boundary, then a flatten pass (labels are ordered by
 //     their first raster pixel, as ndimage.label).  One workgroup per image took 17 ms per batch of 32 at 384^2.
 #include "common.h"
+#include <algorithm>
 #include <type_traits>
 #include <math.h>
 
@@ -62,10 +63,6 @@ struct BsWs {  // workspace carve-up
 // Batched solves: image i of a launch lives at workspace + i * ws_bytes and at pixel offset i * npx of the image /
 // target / output arrays; blockIdx.z is the image.  Single-workgroup kernels then run one workgroup PER IMAGE, which
 // is what fills the GPU (a lone solve occupies one CU).
-struct BsBatch {
-    size_t ws_bytes;
-    int n_images;
-};
 __device__ __forceinline__ BsWs bs_image_ws(BsWs w, size_t bytes) {
     auto mv = [&](auto*& ptr) { ptr = reinterpret_cast<std::remove_reference_t<decltype(ptr)>>(reinterpret_cast<char*>(ptr) + bytes); };
     mv(w.bitmap); mv(w.wordrank); mv(w.cell); mv(w.idx); mv(w.vcell); mv(w.nbr);
@@ -74,18 +71,22 @@ __device__ __forceinline__ BsWs bs_image_ws(BsWs w, size_t bytes) {
     return w;
 }
 
-static BsDims make_dims(int H, int W, double ss, double sl, double sc) {
+// the lattice of an H x W image; ss, sl, sc and the luma / chroma extents NL, NC are the same for every image of a call
+__host__ __device__ inline BsDims bs_dims_hw(int H, int W, int ss, double sl, double sc, int NL, int NC) {
     BsDims d;
-    d.H = H; d.W = W; d.ss = (int)ss; d.sl = sl; d.sc = sc; d.npx = H * W;
-    d.NX = (W - 1) / d.ss + 1; d.NY = (H - 1) / d.ss + 1;
-    d.NL = (int)(255.0 / sl) + 1;
-    d.NC = (int)(255.5 / sc) + 1;
+    d.H = H; d.W = W; d.ss = ss; d.sl = sl; d.sc = sc; d.npx = H * W;
+    d.NX = (W - 1) / ss + 1; d.NY = (H - 1) / ss + 1;
+    d.NL = NL;
+    d.NC = NC;
     d.ncells = (long long)d.NX * d.NY * d.NL * d.NC * d.NC;
     d.nwords = (int)((d.ncells + 31) / 32);
     return d;
 }
+static BsDims make_dims(int H, int W, double ss, double sl, double sc) {
+    return bs_dims_hw(H, W, (int)ss, sl, sc, (int)(255.0 / sl) + 1, (int)(255.5 / sc) + 1);
+}
 
-static BsWs carve_bs(const BsDims& d, char* base) {
+__host__ __device__ inline BsWs carve_bs(const BsDims& d, char* base) {
     BsWs w;
     size_t off = 0;
     auto take = [&](size_t bytes) {
@@ -100,8 +101,10 @@ static BsWs carve_bs(const BsDims& d, char* base) {
     w.idx = (int*)take((size_t)d.npx * 4);
     w.vcell = (unsigned*)take(maxV * 4);
     w.nbr = (int*)take(maxV * 4 * 10);
-    double** arrs[] = {&w.m, &w.ws, &w.b, &w.n0, &w.n1, &w.diag, &w.minv, &w.x, &w.r, &w.p, &w.q};
-    for (auto a : arrs) *a = (double*)take(maxV * 8);
+    w.m = (double*)take(maxV * 8); w.ws = (double*)take(maxV * 8); w.b = (double*)take(maxV * 8);
+    w.n0 = (double*)take(maxV * 8); w.n1 = (double*)take(maxV * 8); w.diag = (double*)take(maxV * 8);
+    w.minv = (double*)take(maxV * 8); w.x = (double*)take(maxV * 8); w.r = (double*)take(maxV * 8);
+    w.p = (double*)take(maxV * 8); w.q = (double*)take(maxV * 8);
     w.parent = (int*)take((size_t)d.npx * 4);
     w.bin = (unsigned char*)take((size_t)d.npx);
     w.csize = (unsigned*)take((size_t)d.npx * 4);
@@ -114,10 +117,57 @@ static BsWs carve_bs(const BsDims& d, char* base) {
     return w;
 }
 
+// Every kernel below is a template on a "batch provider" P: where image i's lattice, workspace and pixels are.
+//   BsUniform - n images of ONE size (sm_bilateral_solver_batch_f64): dims and the carved workspace of image 0 travel by value,
+//               image i is a strided move of them.
+//   BsMixed   - images of different sizes (sm_bilateral_solver_mixed_f64): a device table of {offsets, H, W}; the lattice and the
+//               carve-up are re-derived from the image's own H, W (integer arithmetic on block-uniform values), and the launch
+//               grids are sized by the largest image, so a workgroup that lies wholly past its image leaves at once (P::mixed).
+struct BsUniform {
+    static constexpr bool mixed = false;
+    BsDims d;
+    BsWs w;
+    size_t ws_bytes;
+    int n_images;
+    __device__ __forceinline__ BsDims dims(int) const { return d; }
+    __device__ __forceinline__ BsWs ws(int i) const { return bs_image_ws(w, i * ws_bytes); }
+    __device__ __forceinline__ size_t img_off(int i) const { return (size_t)i * d.npx * 3; }
+    __device__ __forceinline__ size_t px_off(int i) const { return (size_t)i * d.npx; }
+};
+struct BsMixed {
+    static constexpr bool mixed = true;
+    const sm_bilateral_image* tab;
+    char* base;
+    double sl, sc;
+    int ss, NL, NC;
+    int n_images;
+    __device__ __forceinline__ BsDims dims(int i) const { return bs_dims_hw(tab[i].H, tab[i].W, ss, sl, sc, NL, NC); }
+    __device__ __forceinline__ BsWs ws(int i) const { return carve_bs(dims(i), base + tab[i].ws_off); }
+    __device__ __forceinline__ size_t img_off(int i) const { return (size_t)tab[i].img_off; }
+    __device__ __forceinline__ size_t px_off(int i) const { return (size_t)tab[i].px_off; }
+};
+// image = blockIdx.z
+#define BS_IMAGE                               \
+    const BsDims d = bt.dims(blockIdx.z);      \
+    const BsWs w = bt.ws(blockIdx.z);
+// a workgroup of 256 pixels / bs_scan words per block that starts past the image's own extent (mixed batches only; uniform per block,
+// so the shuffles and ballots below always see whole workgroups)
+#define BS_SKIP_PIXELS if (P::mixed && (int)blockIdx.x * 256 >= d.npx) return;
+#define BS_SKIP_SCAN   if (P::mixed && (int)blockIdx.x * BS_SCAN_WORDS >= d.nwords) return;
+
+// the occupancy bitmaps of a mixed batch (the uniform entry point clears its equally spaced ones with one strided memset); the
+// region is padded to 256 B, so whole uint4s are cleared
+__global__ __launch_bounds__(256) void bs_clear_bitmap_kernel(BsMixed bt) {
+    BS_IMAGE
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < (d.nwords + 3) / 4) reinterpret_cast<uint4*>(w.bitmap)[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+
 // ---- grid construction ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void bs_cells_kernel(const unsigned char* __restrict__ img, BsDims d, BsWs w, BsBatch bb) {
-    w = bs_image_ws(w, blockIdx.z * bb.ws_bytes);
-    img += (size_t)blockIdx.z * d.npx * 3;
+template <class P> __global__ __launch_bounds__(256) void bs_cells_kernel(const unsigned char* __restrict__ img, P bt) {
+    BS_IMAGE
+    BS_SKIP_PIXELS
+    img += bt.img_off(blockIdx.z);
     const int p = min((int)(blockIdx.x * 256 + threadIdx.x), d.npx - 1);  // the tail lanes repeat the last pixel (they take part in the shuffle)
     const int y = p / d.W, x = p - y * d.W;
     const double R = img[p * 3 + 0], G = img[p * 3 + 1], B = img[p * 3 + 2];
@@ -136,8 +186,9 @@ __global__ __launch_bounds__(256) void bs_cells_kernel(const unsigned char* __re
 
 // exclusive prefix sum of popcount(bitmap[w]) (vertex id = occupied cells before this one); scal[0] = number of vertices.
 // Two launches: popcount per block of BS_SCAN_WORDS words, then every block adds the blocks before it and scans its own words.
-__global__ __launch_bounds__(256) void bs_scan_partial_kernel(BsDims d, BsWs w, BsBatch bb) {
-    w = bs_image_ws(w, blockIdx.z * bb.ws_bytes);
+template <class P> __global__ __launch_bounds__(256) void bs_scan_partial_kernel(P bt) {
+    BS_IMAGE
+    BS_SKIP_SCAN
     __shared__ unsigned wsum[4];
     const int t = threadIdx.x, base = blockIdx.x * BS_SCAN_WORDS + t * 4;
     unsigned s = 0;
@@ -150,8 +201,9 @@ __global__ __launch_bounds__(256) void bs_scan_partial_kernel(BsDims d, BsWs w, 
     if (t == 0) w.blocksum[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
 }
 
-__global__ __launch_bounds__(256) void bs_scan_final_kernel(BsDims d, BsWs w, BsBatch bb) {
-    w = bs_image_ws(w, blockIdx.z * bb.ws_bytes);
+template <class P> __global__ __launch_bounds__(256) void bs_scan_final_kernel(P bt) {
+    BS_IMAGE
+    BS_SKIP_SCAN
     __shared__ unsigned wsum[4], wpre[4];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, base = blockIdx.x * BS_SCAN_WORDS + t * 4;
     unsigned before = 0;  // vertices in the blocks before this one
@@ -174,7 +226,8 @@ __global__ __launch_bounds__(256) void bs_scan_final_kernel(BsDims d, BsWs w, Bs
 #pragma unroll
     for (int i = 0; i < 4; ++i)
         if (base + i < d.nwords) { w.wordrank[base + i] = run; run += c[i]; }
-    if (blockIdx.x == gridDim.x - 1 && t == 255) w.scal[0] = (int)run;  // the last thread's running total = all vertices
+    // the last thread of the image's last block: its running total = all vertices
+    if ((int)blockIdx.x == (d.nwords + BS_SCAN_WORDS - 1) / BS_SCAN_WORDS - 1 && t == 255) w.scal[0] = (int)run;
 }
 
 __device__ __forceinline__ int bs_rank(const BsWs& w, unsigned cell) {
@@ -182,8 +235,8 @@ __device__ __forceinline__ int bs_rank(const BsWs& w, unsigned cell) {
     return (int)(w.wordrank[cell >> 5] + __popc(word & ((1u << bit) - 1u)));
 }
 
-__global__ __launch_bounds__(256) void bs_vertices_kernel(BsDims d, BsWs w, BsBatch bb) {
-    w = bs_image_ws(w, blockIdx.z * bb.ws_bytes);
+template <class P> __global__ __launch_bounds__(256) void bs_vertices_kernel(P bt) {
+    BS_IMAGE
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= d.nwords) return;
     unsigned word = w.bitmap[i], r = w.wordrank[i];
@@ -194,15 +247,18 @@ __global__ __launch_bounds__(256) void bs_vertices_kernel(BsDims d, BsWs w, BsBa
     }
 }
 
-__global__ __launch_bounds__(256) void bs_pixel_vertex_kernel(BsDims d, BsWs w, BsBatch bb) {
-    w = bs_image_ws(w, blockIdx.z * bb.ws_bytes);
+template <class P> __global__ __launch_bounds__(256) void bs_pixel_vertex_kernel(P bt) {
+    BS_IMAGE
+    BS_SKIP_PIXELS
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p < d.npx) w.idx[p] = bs_rank(w, w.cell[p]);
 }
 
 // blur matrices (:66-81) as neighbour tables: +-1 along each of the 5 lattice axes, present iff the cell is occupied
-__global__ __launch_bounds__(256) void bs_neighbors_kernel(BsDims d, BsWs w, int maxV, BsBatch bb) {
-    w = bs_image_ws(w, blockIdx.z * bb.ws_bytes);
+template <class P> __global__ __launch_bounds__(256) void bs_neighbors_kernel(P bt) {
+    BS_IMAGE
+    BS_SKIP_PIXELS
+    const int maxV = d.npx;
     const int v = blockIdx.x * 256 + threadIdx.x;
     const int V = w.scal[0];
     if (v >= V) return;
@@ -234,9 +290,10 @@ __global__ __launch_bounds__(256) void bs_neighbors_kernel(BsDims d, BsWs w, int
 // (atomicCAS on the key, atomicMin on the index: integer atomics, the result does not depend on their order); the sum is then one
 // straight pass over the cell by the leaders only.  (Rounds 1-3: every pixel scanned the pixels before it for its vertex id and
 // the leaders the ones after it, two loops of dependent LDS reads with an early exit - 0.42 ms per batch of 32 at 384^2.)
-__global__ void bs_splat_kernel(const double* __restrict__ target, double conf, BsDims d, BsWs w, int table, BsBatch bb) {
-    w = bs_image_ws(w, blockIdx.z * bb.ws_bytes);
-    target += (size_t)blockIdx.z * d.npx;
+template <class P> __global__ void bs_splat_kernel(const double* __restrict__ target, double conf, P bt, int table) {
+    BS_IMAGE
+    if (P::mixed && ((int)blockIdx.x >= d.NX || (int)blockIdx.y >= d.NY)) return;  // a spatial cell past this image
+    target += bt.px_off(blockIdx.z);
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int n = d.ss * d.ss;
     int* vid = (int*)lds;
@@ -345,15 +402,16 @@ constexpr int BS_P_BB = 0, BS_P_RR = 1, BS_P_RZ = 3, BS_P_PQ = 5;  // rr, rz: + 
 // L2 instead of eight.  The grid is (BS_SOLVE_BLOCKS * 8, ceil(images / 8)): linear id L = blockIdx.x + 256 * blockIdx.y.
 #define BS_SOLVE_PROLOGUE                                                          \
     const int bs_img = (int)blockIdx.y * 8 + ((int)blockIdx.x & 7);                \
-    if (bs_img >= batch.n_images) return;                                          \
+    if (bs_img >= bt.n_images) return;                                             \
     const int bs_blk = (int)blockIdx.x >> 3;                                       \
-    w = bs_image_ws(w, bs_img * batch.ws_bytes);                                   \
+    const BsWs w = bt.ws(bs_img);                                                  \
+    const int maxV = bt.dims(bs_img).npx;                                          \
     const int V = w.scal[0];                                                       \
     const int g0 = bs_blk * BS_SOLVE_THREADS + threadIdx.x;                        \
     constexpr int GS = BS_SOLVE_BLOCKS * BS_SOLVE_THREADS;
 
 // bistochastize (:107-118): n <- sqrt(n*m / blur(n)) x10 from n = 1; sweep `it` reads n{it & 1} and writes the other
-__global__ __launch_bounds__(BS_SOLVE_THREADS) void bs_bisto_kernel(BsWs w, int maxV, int it, BsBatch batch) {
+template <class P> __global__ __launch_bounds__(BS_SOLVE_THREADS) void bs_bisto_kernel(P bt, int it) {
     BS_SOLVE_PROLOGUE
     const double* na = (it & 1) ? w.n1 : w.n0;
     double* nb = (it & 1) ? w.n0 : w.n1;
@@ -365,7 +423,7 @@ __global__ __launch_bounds__(BS_SOLVE_THREADS) void bs_bisto_kernel(BsWs w, int 
 }
 
 // after ten sweeps n lives in n0.  A diagonal, Jacobi preconditioner, flat initialisation (:132-142), |b|^2
-__global__ __launch_bounds__(BS_SOLVE_THREADS) void bs_pcg_setup_kernel(BsWs w, int maxV, double lam, double diag_min, BsBatch batch) {
+template <class P> __global__ __launch_bounds__(BS_SOLVE_THREADS) void bs_pcg_setup_kernel(P bt, double lam, double diag_min) {
     BS_SOLVE_PROLOGUE
     const double* n = w.n0;
     double bb = 0.0;
@@ -389,7 +447,7 @@ __global__ __launch_bounds__(BS_SOLVE_THREADS) void bs_pcg_setup_kernel(BsWs w, 
 }
 
 // scipy.sparse.linalg.cg(A, b, x0, M, maxiter, rtol=tol, atol=0): r0 = b - A x0 (or x = b when b = 0), |r|^2 and r.M^-1 r
-__global__ __launch_bounds__(BS_SOLVE_THREADS) void bs_pcg_r0_kernel(BsWs w, int maxV, double lam, BsBatch batch) {
+template <class P> __global__ __launch_bounds__(BS_SOLVE_THREADS) void bs_pcg_r0_kernel(P bt, double lam) {
     BS_SOLVE_PROLOGUE
     const double bnrm = sqrt(bs_total(w.part, BS_P_BB));
     if (bnrm == 0.0) return;  // uniform over the image's workgroups; cg returns b itself: bs_slice_kernel reads it
@@ -414,7 +472,7 @@ __device__ __forceinline__ bool bs_running(const BsWs& w, int it, double tol) {
 }
 
 // phase a of iteration `it`: p <- M^-1 r (+ beta p)
-__global__ __launch_bounds__(BS_SOLVE_THREADS) void bs_pcg_p_kernel(BsWs w, int it, double tol, BsBatch batch) {
+template <class P> __global__ __launch_bounds__(BS_SOLVE_THREADS) void bs_pcg_p_kernel(P bt, int it, double tol) {
     BS_SOLVE_PROLOGUE
     if (!bs_running(w, it, tol)) return;
     if (it > 0) {
@@ -426,7 +484,7 @@ __global__ __launch_bounds__(BS_SOLVE_THREADS) void bs_pcg_p_kernel(BsWs w, int 
 }
 
 // phase b: q <- A p, p.q
-__global__ __launch_bounds__(BS_SOLVE_THREADS) void bs_pcg_q_kernel(BsWs w, int maxV, double lam, int it, double tol, BsBatch batch) {
+template <class P> __global__ __launch_bounds__(BS_SOLVE_THREADS) void bs_pcg_q_kernel(P bt, double lam, int it, double tol) {
     BS_SOLVE_PROLOGUE
     if (!bs_running(w, it, tol)) return;
     double pq = 0.0;
@@ -439,7 +497,7 @@ __global__ __launch_bounds__(BS_SOLVE_THREADS) void bs_pcg_q_kernel(BsWs w, int 
 }
 
 // phase c: x <- x + alpha p, r <- r - alpha q, the next iteration's |r|^2 and r.M^-1 r
-__global__ __launch_bounds__(BS_SOLVE_THREADS) void bs_pcg_x_kernel(BsWs w, int it, double tol, BsBatch batch) {
+template <class P> __global__ __launch_bounds__(BS_SOLVE_THREADS) void bs_pcg_x_kernel(P bt, int it, double tol) {
     BS_SOLVE_PROLOGUE
     if (!bs_running(w, it, tol)) return;
     const double alpha = bs_total(w.part, BS_P_RZ + (it & 1)) / bs_total(w.part, BS_P_PQ);
@@ -456,9 +514,10 @@ __global__ __launch_bounds__(BS_SOLVE_THREADS) void bs_pcg_x_kernel(BsWs w, int 
     if (g0 == 0) w.scal[1] = it + 1;  // the other workgroups of this launch only test scal[1] >= it
 }
 
-__global__ __launch_bounds__(256) void bs_slice_kernel(BsDims d, BsWs w, double* __restrict__ soft, BsBatch bb) {
-    w = bs_image_ws(w, blockIdx.z * bb.ws_bytes);
-    soft += (size_t)blockIdx.z * d.npx;
+template <class P> __global__ __launch_bounds__(256) void bs_slice_kernel(P bt, double* __restrict__ soft) {
+    BS_IMAGE
+    BS_SKIP_PIXELS
+    soft += bt.px_off(blockIdx.z);
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= d.npx) return;
     const bool zero_b = bs_total(w.part, BS_P_BB) == 0.0;  // cg returns b itself when |b| = 0
@@ -484,23 +543,24 @@ __device__ __forceinline__ void uf_union(int* parent, int a, int b) {
 }
 
 #define BS_POST_PROLOGUE                                     \
-    w = bs_image_ws(w, blockIdx.z * bb.ws_bytes);           \
+    BS_IMAGE                                                \
+    BS_SKIP_PIXELS                                          \
     const int p = blockIdx.x * 256 + threadIdx.x;           \
     const int npx = d.npx, W = d.W;                         \
     int* parent = w.parent;                                 \
     unsigned char* bin = w.bin;                             \
     unsigned* csize = w.csize;
 
-__global__ __launch_bounds__(256) void bs_post_threshold_kernel(BsDims d, BsWs w, const double* __restrict__ soft, BsBatch bb) {
+template <class P> __global__ __launch_bounds__(256) void bs_post_threshold_kernel(P bt, const double* __restrict__ soft) {
     BS_POST_PROLOGUE
-    soft += (size_t)blockIdx.z * npx;
+    soft += bt.px_off(blockIdx.z);
     if (p < npx) bin[p] = soft[p] > 0.5;
     if (p == 0) { w.keys[0] = 0; w.keys[1] = 0; w.scal[2] = 0; w.scal[4] = 0; }
 }
 
 // parent <- start of the pixel's run of equal values inside its wave's 64 consecutive pixels of the row (ballot, no atomics);
 // csize <- 0.  fg_only: background pixels stay singletons.
-__global__ __launch_bounds__(256) void bs_post_runs_kernel(BsDims d, BsWs w, int fg_only, BsBatch bb) {
+template <class P> __global__ __launch_bounds__(256) void bs_post_runs_kernel(P bt, int fg_only) {
     BS_POST_PROLOGUE
     const int lane = threadIdx.x & 63;
     const bool in = p < npx;
@@ -517,7 +577,7 @@ __global__ __launch_bounds__(256) void bs_post_runs_kernel(BsDims d, BsWs w, int
 
 // unions: a run that continues across a wave boundary, and a pixel under an equal pixel where its run meets that run of the row
 // above for the first time (the pixels to the left are already joined through the two runs)
-__global__ __launch_bounds__(256) void bs_post_union_kernel(BsDims d, BsWs w, int fg_only, BsBatch bb) {
+template <class P> __global__ __launch_bounds__(256) void bs_post_union_kernel(P bt, int fg_only) {
     BS_POST_PROLOGUE
     if (p >= npx) return;
     const unsigned char b = bin[p];
@@ -531,7 +591,7 @@ __global__ __launch_bounds__(256) void bs_post_union_kernel(BsDims d, BsWs w, in
 // parent <- root.  count != 0 (the labelling of the filled mask): also component sizes and the foreground count, one atomic per
 // stretch of equal roots inside a wave's 64 pixels - and one per workgroup for waves that lie inside a single component (a
 // pixel-wise atomicAdd put all of a component's pixels on one address: 4 ms per batch of 32 at 384^2)
-__global__ __launch_bounds__(256) void bs_post_flatten_kernel(BsDims d, BsWs w, int count, BsBatch bb) {
+template <class P> __global__ __launch_bounds__(256) void bs_post_flatten_kernel(P bt, int count) {
     BS_POST_PROLOGUE
     __shared__ int wroot[4];
     int root = -1;
@@ -569,14 +629,14 @@ __global__ __launch_bounds__(256) void bs_post_flatten_kernel(BsDims d, BsWs w, 
 }
 
 // binary_fill_holes: background components that touch the image border keep their colour ...
-__global__ __launch_bounds__(256) void bs_post_border_kernel(BsDims d, BsWs w, BsBatch bb) {
+template <class P> __global__ __launch_bounds__(256) void bs_post_border_kernel(P bt) {
     BS_POST_PROLOGUE
     if (p >= npx) return;
     const int y = p / W, x = p - y * W;
     if (!bin[p] && (y == 0 || x == 0 || y == d.H - 1 || x == W - 1)) csize[parent[p]] = 1;
 }
 // ... the others become foreground
-__global__ __launch_bounds__(256) void bs_post_fill_kernel(BsDims d, BsWs w, BsBatch bb) {
+template <class P> __global__ __launch_bounds__(256) void bs_post_fill_kernel(P bt) {
     BS_POST_PROLOGUE
     if (p < npx && !bin[p] && !csize[parent[p]]) bin[p] = 1;
 }
@@ -584,7 +644,7 @@ __global__ __launch_bounds__(256) void bs_post_fill_kernel(BsDims d, BsWs w, BsB
 // ndimage.label (4-connectivity) on the filled mask is the second runs / union / flatten round (which also counts the sizes)
 // nb_pixel = [background, label 1, label 2, ...] (labels in raster order of their first pixel); argsort ascending, take [-2]:
 // key = (size << 32 | order) with order 0 = background, root + 1 = component.  Largest key, then the largest below it.
-__global__ __launch_bounds__(256) void bs_post_best_kernel(BsDims d, BsWs w, BsBatch bb) {
+template <class P> __global__ __launch_bounds__(256) void bs_post_best_kernel(P bt) {
     BS_POST_PROLOGUE
     if (p == 0) atomicMax(&w.keys[0], (unsigned long long)(npx - w.scal[4]) << 32);
     if (p < npx && bin[p] && parent[p] == p) {
@@ -592,7 +652,7 @@ __global__ __launch_bounds__(256) void bs_post_best_kernel(BsDims d, BsWs w, BsB
         atomicAdd(&w.scal[2], 1);
     }
 }
-__global__ __launch_bounds__(256) void bs_post_second_kernel(BsDims d, BsWs w, BsBatch bb) {
+template <class P> __global__ __launch_bounds__(256) void bs_post_second_kernel(P bt) {
     BS_POST_PROLOGUE
     const unsigned long long best = w.keys[0];
     if (p == 0) {
@@ -604,9 +664,9 @@ __global__ __launch_bounds__(256) void bs_post_second_kernel(BsDims d, BsWs w, B
         if (k < best) atomicMax(&w.keys[1], k);
     }
 }
-__global__ __launch_bounds__(256) void bs_post_out_kernel(BsDims d, BsWs w, unsigned char* __restrict__ out, BsBatch bb) {
+template <class P> __global__ __launch_bounds__(256) void bs_post_out_kernel(P bt, unsigned char* __restrict__ out) {
     BS_POST_PROLOGUE
-    out += (size_t)blockIdx.z * npx;
+    out += bt.px_off(blockIdx.z);
     const unsigned long long pick = w.keys[1];
     const bool none = w.scal[2] == 0;                       // IndexError branch (:191-192): all ones
     const bool pick_bg = (unsigned)(pick & 0xffffffffu) == 0;
@@ -615,8 +675,8 @@ __global__ __launch_bounds__(256) void bs_post_out_kernel(BsDims d, BsWs w, unsi
     if (p == 0) w.scal[3] = none ? -2 : pick_root;
 }
 
-__global__ void bs_info_kernel(BsWs w, int* info, BsBatch bb) {
-    w = bs_image_ws(w, blockIdx.z * bb.ws_bytes);
+template <class P> __global__ void bs_info_kernel(P bt, int* info) {
+    const BsWs w = bt.ws(blockIdx.z);
     info += 4 * blockIdx.z;
     if (threadIdx.x < 4) info[threadIdx.x] = w.scal[threadIdx.x];
 }
@@ -630,6 +690,78 @@ extern "C" size_t sm_bilateral_workspace_bytes(int32_t H, int32_t W, double sigm
     if (d.ncells > (1ll << 31) || d.ss * d.ss > 1024) return 0;
     return sm::carve_bs(d, nullptr).total;
 }
+
+namespace sm {
+// launch extents of one call: of the one size (uniform), or of the largest image in each respect (mixed)
+struct BsGrid {
+    int pb;      // blocks of 256 pixels
+    int nscan;   // blocks of BS_SCAN_WORDS bitmap words
+    int vb;      // blocks of 256 bitmap words
+    int NX, NY;  // spatial cells
+    unsigned nz; // images
+    double npx;  // pixels of the whole batch (the taps' byte counts)
+};
+
+// the whole launch sequence, the same for both providers (the bitmaps are already clear)
+template <class P>
+static int bs_launch(const sm_bilateral_args* a, const P& bt, const BsGrid& g, int ss, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned nz = g.nz;
+    const int pb = g.pb;
+    const double npxd = g.npx;
+    int tap = sm::tap_begin(stream, "bilateral: lattice build (bs_cells .. bs_splat)", 0.0, npxd * (3 + 5 * 4 + 8 + 8 + 4 * 16 + 2 * (8 + 4)));
+    hipLaunchKernelGGL(sm::bs_cells_kernel<P>, dim3(pb, 1, nz), dim3(256), 0, st, a->img, bt);
+    const int nscan = g.nscan;
+    hipLaunchKernelGGL(sm::bs_scan_partial_kernel<P>, dim3(nscan, 1, nz), dim3(256), 0, st, bt);
+    hipLaunchKernelGGL(sm::bs_scan_final_kernel<P>, dim3(nscan, 1, nz), dim3(256), 0, st, bt);
+    hipLaunchKernelGGL(sm::bs_vertices_kernel<P>, dim3(g.vb, 1, nz), dim3(256), 0, st, bt);
+    hipLaunchKernelGGL(sm::bs_pixel_vertex_kernel<P>, dim3(pb, 1, nz), dim3(256), 0, st, bt);
+    hipLaunchKernelGGL(sm::bs_neighbors_kernel<P>, dim3(pb, 1, nz), dim3(256), 0, st, bt);
+    const int n = ss * ss;
+    const int threads = ((n + 63) / 64) * 64;
+    int table = 64;
+    while (table < 2 * n) table *= 2;
+    const size_t lds = ((n * 4 + 15) & ~15) + (size_t)n * 8 + (size_t)table * 8;
+    hipLaunchKernelGGL(sm::bs_splat_kernel<P>, dim3(g.NX, g.NY, nz), dim3(threads), lds, st, a->target, a->confidence, bt, table);
+    sm::tap_end(tap);
+    tap = sm::tap_begin(stream, "bilateral: bs_bisto_kernel x 11", 0.0, 0.0);
+    {
+        const dim3 sg(sm::BS_SOLVE_BLOCKS * 8, (nz + 7) / 8, 1), sb(sm::BS_SOLVE_THREADS);
+        for (int it = -1; it < 10; ++it) hipLaunchKernelGGL(sm::bs_bisto_kernel<P>, sg, sb, 0, st, bt, it);
+        sm::tap_end(tap);
+        tap = sm::tap_begin(stream, "bilateral: bs_pcg_* (setup, r0, maxiter x (p, q, x))", 0.0, 0.0);
+        hipLaunchKernelGGL(sm::bs_pcg_setup_kernel<P>, sg, sb, 0, st, bt, a->lam, a->a_diag_min);
+        hipLaunchKernelGGL(sm::bs_pcg_r0_kernel<P>, sg, sb, 0, st, bt, a->lam);
+        for (int it = 0; it < a->cg_maxiter; ++it) {
+            hipLaunchKernelGGL(sm::bs_pcg_p_kernel<P>, sg, sb, 0, st, bt, it, a->cg_tol);
+            hipLaunchKernelGGL(sm::bs_pcg_q_kernel<P>, sg, sb, 0, st, bt, a->lam, it, a->cg_tol);
+            hipLaunchKernelGGL(sm::bs_pcg_x_kernel<P>, sg, sb, 0, st, bt, it, a->cg_tol);
+        }
+    }
+    sm::tap_end(tap);
+    tap = sm::tap_begin(stream, "bilateral: bs_slice + bs_post_*", 0.0, npxd * (8 + 8 + 1 + 2 * 4 * 6));
+    hipLaunchKernelGGL(sm::bs_slice_kernel<P>, dim3(pb, 1, nz), dim3(256), 0, st, bt, a->soft);
+    {
+        const dim3 pg(pb, 1, nz), pt(256);
+        hipLaunchKernelGGL(sm::bs_post_threshold_kernel<P>, pg, pt, 0, st, bt, (const double*)a->soft);
+        for (int fg_only = 0; fg_only < 2; ++fg_only) {
+            hipLaunchKernelGGL(sm::bs_post_runs_kernel<P>, pg, pt, 0, st, bt, fg_only);
+            hipLaunchKernelGGL(sm::bs_post_union_kernel<P>, pg, pt, 0, st, bt, fg_only);
+            hipLaunchKernelGGL(sm::bs_post_flatten_kernel<P>, pg, pt, 0, st, bt, fg_only);
+            if (!fg_only) {
+                hipLaunchKernelGGL(sm::bs_post_border_kernel<P>, pg, pt, 0, st, bt);
+                hipLaunchKernelGGL(sm::bs_post_fill_kernel<P>, pg, pt, 0, st, bt);
+            }
+        }
+        hipLaunchKernelGGL(sm::bs_post_best_kernel<P>, pg, pt, 0, st, bt);
+        hipLaunchKernelGGL(sm::bs_post_second_kernel<P>, pg, pt, 0, st, bt);
+        hipLaunchKernelGGL(sm::bs_post_out_kernel<P>, pg, pt, 0, st, bt, a->binary);
+    }
+    sm::tap_end(tap);
+    if (a->info) hipLaunchKernelGGL(sm::bs_info_kernel<P>, dim3(1, 1, nz), dim3(64), 0, st, bt, a->info);
+    return 0;
+}
+}  // namespace sm
 
 extern "C" int sm_bilateral_solver_batch_f64(const sm_bilateral_args* a, int32_t n_images, void* stream) {
     SM_REQUIRE(a && a->img && a->target && a->soft && a->binary && a->workspace, "sm_bilateral_solver_f64: null pointer");
@@ -648,67 +780,67 @@ extern "C" int sm_bilateral_solver_batch_f64(const sm_bilateral_args* a, int32_t
     hipStream_t st = (hipStream_t)stream;
     const sm::BsDims d = sm::make_dims(a->H, a->W, a->sigma_spatial, a->sigma_luma, a->sigma_chroma);
     const sm::BsWs w = sm::carve_bs(d, (char*)a->workspace);
-    const sm::BsBatch bb = {need1, n_images};  // per-image workspaces are laid end to end (need1 is a multiple of 256)
-    const unsigned nz = (unsigned)n_images;
-    const int maxV = d.npx;
+    const sm::BsUniform bt = {d, w, need1, n_images};  // per-image workspaces are laid end to end (need1 is a multiple of 256)
     // the occupancy bitmap is the first region of each image's workspace: one strided memset clears them all
     if (hipMemset2DAsync(w.bitmap, need1, 0, (size_t)d.nwords * 4, (size_t)n_images, st) != hipSuccess) {
         sm::set_error("sm_bilateral_solver_f64: hipMemset2DAsync failed");
         return SM_ELAUNCH;
     }
-    const int pb = (d.npx + 255) / 256;
-    const double npxd = (double)d.npx * n_images;
-    int tap = sm::tap_begin(stream, "bilateral: lattice build (bs_cells .. bs_splat)", 0.0, npxd * (3 + 5 * 4 + 8 + 8 + 4 * 16 + 2 * (8 + 4)));
-    hipLaunchKernelGGL(sm::bs_cells_kernel, dim3(pb, 1, nz), dim3(256), 0, st, a->img, d, w, bb);
-    const int nscan = (d.nwords + sm::BS_SCAN_WORDS - 1) / sm::BS_SCAN_WORDS;
-    hipLaunchKernelGGL(sm::bs_scan_partial_kernel, dim3(nscan, 1, nz), dim3(256), 0, st, d, w, bb);
-    hipLaunchKernelGGL(sm::bs_scan_final_kernel, dim3(nscan, 1, nz), dim3(256), 0, st, d, w, bb);
-    hipLaunchKernelGGL(sm::bs_vertices_kernel, dim3((d.nwords + 255) / 256, 1, nz), dim3(256), 0, st, d, w, bb);
-    hipLaunchKernelGGL(sm::bs_pixel_vertex_kernel, dim3(pb, 1, nz), dim3(256), 0, st, d, w, bb);
-    hipLaunchKernelGGL(sm::bs_neighbors_kernel, dim3(pb, 1, nz), dim3(256), 0, st, d, w, maxV, bb);
-    const int n = d.ss * d.ss;
-    const int threads = ((n + 63) / 64) * 64;
-    int table = 64;
-    while (table < 2 * n) table *= 2;
-    const size_t lds = ((n * 4 + 15) & ~15) + (size_t)n * 8 + (size_t)table * 8;
-    hipLaunchKernelGGL(sm::bs_splat_kernel, dim3(d.NX, d.NY, nz), dim3(threads), lds, st, a->target, a->confidence, d, w, table, bb);
-    sm::tap_end(tap);
-    tap = sm::tap_begin(stream, "bilateral: bs_bisto_kernel x 11", 0.0, 0.0);
-    {
-        const dim3 sg(sm::BS_SOLVE_BLOCKS * 8, (nz + 7) / 8, 1), sb(sm::BS_SOLVE_THREADS);
-        for (int it = -1; it < 10; ++it) hipLaunchKernelGGL(sm::bs_bisto_kernel, sg, sb, 0, st, w, maxV, it, bb);
-        sm::tap_end(tap);
-        tap = sm::tap_begin(stream, "bilateral: bs_pcg_* (setup, r0, maxiter x (p, q, x))", 0.0, 0.0);
-        hipLaunchKernelGGL(sm::bs_pcg_setup_kernel, sg, sb, 0, st, w, maxV, a->lam, a->a_diag_min, bb);
-        hipLaunchKernelGGL(sm::bs_pcg_r0_kernel, sg, sb, 0, st, w, maxV, a->lam, bb);
-        for (int it = 0; it < a->cg_maxiter; ++it) {
-            hipLaunchKernelGGL(sm::bs_pcg_p_kernel, sg, sb, 0, st, w, it, a->cg_tol, bb);
-            hipLaunchKernelGGL(sm::bs_pcg_q_kernel, sg, sb, 0, st, w, maxV, a->lam, it, a->cg_tol, bb);
-            hipLaunchKernelGGL(sm::bs_pcg_x_kernel, sg, sb, 0, st, w, it, a->cg_tol, bb);
-        }
-    }
-    sm::tap_end(tap);
-    tap = sm::tap_begin(stream, "bilateral: bs_slice + bs_post_*", 0.0, npxd * (8 + 8 + 1 + 2 * 4 * 6));
-    hipLaunchKernelGGL(sm::bs_slice_kernel, dim3(pb, 1, nz), dim3(256), 0, st, d, w, a->soft, bb);
-    {
-        const dim3 pg(pb, 1, nz), pt(256);
-        hipLaunchKernelGGL(sm::bs_post_threshold_kernel, pg, pt, 0, st, d, w, a->soft, bb);
-        for (int fg_only = 0; fg_only < 2; ++fg_only) {
-            hipLaunchKernelGGL(sm::bs_post_runs_kernel, pg, pt, 0, st, d, w, fg_only, bb);
-            hipLaunchKernelGGL(sm::bs_post_union_kernel, pg, pt, 0, st, d, w, fg_only, bb);
-            hipLaunchKernelGGL(sm::bs_post_flatten_kernel, pg, pt, 0, st, d, w, fg_only, bb);
-            if (!fg_only) {
-                hipLaunchKernelGGL(sm::bs_post_border_kernel, pg, pt, 0, st, d, w, bb);
-                hipLaunchKernelGGL(sm::bs_post_fill_kernel, pg, pt, 0, st, d, w, bb);
-            }
-        }
-        hipLaunchKernelGGL(sm::bs_post_best_kernel, pg, pt, 0, st, d, w, bb);
-        hipLaunchKernelGGL(sm::bs_post_second_kernel, pg, pt, 0, st, d, w, bb);
-        hipLaunchKernelGGL(sm::bs_post_out_kernel, pg, pt, 0, st, d, w, a->binary, bb);
-    }
-    sm::tap_end(tap);
-    if (a->info) hipLaunchKernelGGL(sm::bs_info_kernel, dim3(1, 1, nz), dim3(64), 0, st, w, a->info, bb);
+    const sm::BsGrid g = {(d.npx + 255) / 256, (d.nwords + sm::BS_SCAN_WORDS - 1) / sm::BS_SCAN_WORDS, (d.nwords + 255) / 256,
+                          d.NX, d.NY, (unsigned)n_images, (double)d.npx * n_images};
+    sm::bs_launch(a, bt, g, d.ss, stream);
     return sm::check_launch("sm_bilateral_solver_f64");
+}
+
+extern "C" size_t sm_bilateral_mixed_workspace_bytes(sm_bilateral_image* images, int32_t n_images, double sigma_spatial,
+                                                     double sigma_luma, double sigma_chroma) {
+    if (!images || n_images <= 0) return 0;
+    size_t off = 0;
+    for (int i = 0; i < n_images; ++i) {
+        const size_t need = sm_bilateral_workspace_bytes(images[i].H, images[i].W, sigma_spatial, sigma_luma, sigma_chroma);
+        if (need == 0) return 0;
+        images[i].ws_off = (int64_t)off;  // need is a multiple of 256: every region of the carve-up is
+        off += need;
+    }
+    return off;
+}
+
+extern "C" int sm_bilateral_solver_mixed_f64(const sm_bilateral_args* a, const sm_bilateral_image* images_host,
+                                             const sm_bilateral_image* images_dev, int32_t n_images, void* stream) {
+    SM_REQUIRE(a && a->img && a->target && a->soft && a->binary && a->workspace && images_host && images_dev,
+               "sm_bilateral_solver_mixed_f64: null pointer");
+    SM_REQUIRE(n_images >= 1 && n_images <= 65535, "sm_bilateral_solver_mixed_f64: n_images=%d (1..65535)", n_images);
+    SM_REQUIRE(a->sigma_spatial >= 1 && a->sigma_spatial == (int)a->sigma_spatial && a->sigma_luma > 0 && a->sigma_chroma > 0,
+               "sm_bilateral_solver_mixed_f64: bad sigmas (sigma_spatial must be a positive integer)");
+    SM_REQUIRE(((uintptr_t)a->workspace % 256) == 0, "sm_bilateral_solver_mixed_f64: workspace not 256-B aligned");
+    sm::BsGrid g = {0, 0, 0, 0, 0, (unsigned)n_images, 0.0};
+    size_t end = 0;  // the workspaces must not overlap: each begins at or after the end of the one before it
+    for (int i = 0; i < n_images; ++i) {
+        const sm_bilateral_image& im = images_host[i];
+        const size_t need = sm_bilateral_workspace_bytes(im.H, im.W, a->sigma_spatial, a->sigma_luma, a->sigma_chroma);
+        SM_REQUIRE(need != 0, "sm_bilateral_solver_mixed_f64: image %d is %d x %d: empty, lattice too large (>2^31 cells) or sigma_spatial > 32",
+                   i, im.H, im.W);
+        SM_REQUIRE(im.img_off >= 0 && im.px_off >= 0 && im.ws_off >= 0 && im.ws_off % 256 == 0 && (size_t)im.ws_off >= end,
+                   "sm_bilateral_solver_mixed_f64: image %d: negative offset, or ws_off=%lld not a multiple of 256 / inside the workspace before it",
+                   i, (long long)im.ws_off);
+        end = (size_t)im.ws_off + need;
+        if (end > a->workspace_bytes) {
+            sm::set_error("sm_bilateral_solver_mixed_f64: workspace %zu B < %zu B needed by image %d", a->workspace_bytes, end, i);
+            return SM_ENOSPACE;
+        }
+        const sm::BsDims d = sm::make_dims(im.H, im.W, a->sigma_spatial, a->sigma_luma, a->sigma_chroma);
+        g.pb = std::max(g.pb, (d.npx + 255) / 256);
+        g.nscan = std::max(g.nscan, (d.nwords + sm::BS_SCAN_WORDS - 1) / sm::BS_SCAN_WORDS);
+        g.vb = std::max(g.vb, (d.nwords + 255) / 256);
+        g.NX = std::max(g.NX, d.NX);
+        g.NY = std::max(g.NY, d.NY);
+        g.npx += (double)d.npx;
+    }
+    const sm::BsDims d0 = sm::make_dims(1, 1, a->sigma_spatial, a->sigma_luma, a->sigma_chroma);  // the size-independent part
+    const sm::BsMixed bt = {images_dev, (char*)a->workspace, d0.sl, d0.sc, d0.ss, d0.NL, d0.NC, n_images};
+    hipLaunchKernelGGL(sm::bs_clear_bitmap_kernel, dim3((g.vb + 3) / 4, 1, g.nz), dim3(256), 0, (hipStream_t)stream, bt);
+    sm::bs_launch(a, bt, g, d0.ss, stream);
+    return sm::check_launch("sm_bilateral_solver_mixed_f64");
 }
 
 extern "C" int sm_bilateral_solver_f64(const sm_bilateral_args* a, void* stream) {

@@ -952,6 +952,42 @@ __global__ __launch_bounds__(256) void eval_u8_to_f32_kernel(const unsigned char
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) dst[i] = (float)src[i];
 }
 
+// native resolution: every image has its own (H, W) and its own packed plane at px_off[b]
+__global__ __launch_bounds__(256) void eval_upsample_selected_native_kernel(const float* __restrict__ masks, int64_t stride_b,
+                                                                           const float* __restrict__ rows, int sel_col,
+                                                                           const sm_bilateral_image* __restrict__ images,
+                                                                           double* __restrict__ out, int mh, int mw, float scale) {
+    const int b = blockIdx.y;
+    const sm_bilateral_image im = images[b];
+    const int npx = im.H * im.W;
+    if ((int)blockIdx.x * 256 >= npx) return;
+    const int q = (int)rows[(int64_t)b * 16 + sel_col];
+    const float* m = masks + (int64_t)b * stride_b + (int64_t)q * mh * mw;
+    const float sy = 1.0f / scale, sx = 1.0f / scale;  // F.interpolate(scale_factor=scale): as sm_evaluate_masks_f32 with scale > 0
+    double* o = out + im.px_off;
+    for (int p = blockIdx.x * 256 + threadIdx.x; p < npx; p += gridDim.x * 256) {
+        const int y = p / im.W, x = p - y * im.W;
+        const UpIdx uy = up_index(y, sy, mh), ux = up_index(x, sx, mw);
+        // a pixel outside the up-sampled plane (H_b > scale * mh: not a size the crop can produce) reads nothing
+        o[p] = uy.i0 < mh && ux.i0 < mw ? (double)up_sample(m, mw, uy, ux) : 0.0;
+    }
+}
+
+__global__ __launch_bounds__(256) void eval_planes_u8_to_f32_kernel(const unsigned char* __restrict__ src,
+                                                                   const sm_bilateral_image* __restrict__ images,
+                                                                   float* __restrict__ dst, int Hmax, int Wmax) {
+    const int b = blockIdx.y;
+    const sm_bilateral_image im = images[b];
+    const int npx = im.H * im.W;
+    if ((int)blockIdx.x * 256 >= npx || im.H > Hmax || im.W > Wmax) return;
+    const unsigned char* s = src + im.px_off;
+    float* d = dst + (int64_t)b * Hmax * Wmax;
+    for (int p = blockIdx.x * 256 + threadIdx.x; p < npx; p += gridDim.x * 256) {
+        const int y = p / im.W, x = p - y * im.W;
+        d[(int64_t)y * Wmax + x] = (float)s[p];
+    }
+}
+
 struct EvalWs { QueryStats *qs, *qpart; GtStats *gs, *gpart; MetricCounts* cnt; double* part; float* maskT; int *sel, *ytab; float* thr_adapt; size_t total; };
 
 static EvalWs carve_eval(int B, int nq, int nchunk, int mh, int plane, char* base) {
@@ -1005,6 +1041,27 @@ extern "C" int sm_mask_u8_to_f32(const uint8_t* src, float* dst, int64_t n, void
     const int64_t g = (n + 255) / 256;
     hipLaunchKernelGGL(sm::eval_u8_to_f32_kernel, dim3((int)(g < 2048 ? g : 2048)), dim3(256), 0, (hipStream_t)stream, src, dst, n);
     return sm::check_launch("sm_mask_u8_to_f32");
+}
+
+extern "C" int sm_upsample_selected_native_f64(const float* masks, int64_t mask_stride_b, const float* rows, int32_t sel_col,
+                                               const sm_bilateral_image* images, double* out, int32_t B, int32_t mh,
+                                               int32_t mw, float scale, int32_t max_pixels, void* stream) {
+    SM_REQUIRE(masks && rows && images && out && B > 0 && B <= 65535 && mh > 0 && mw > 0 && scale > 0.f && max_pixels > 0 &&
+                   (sel_col == 14 || sel_col == 15),
+               "sm_upsample_selected_native_f64: bad arguments (sel_col 14 = picked query, 15 = upper bound; scale > 0)");
+    const int gx = (max_pixels + 255) / 256 < 256 ? (max_pixels + 255) / 256 : 256;
+    hipLaunchKernelGGL(sm::eval_upsample_selected_native_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, masks, mask_stride_b,
+                       rows, sel_col, images, out, mh, mw, scale);
+    return sm::check_launch("sm_upsample_selected_native_f64");
+}
+
+extern "C" int sm_mask_planes_u8_to_f32(const uint8_t* src, const sm_bilateral_image* images, float* dst, int32_t B,
+                                        int32_t Hmax, int32_t Wmax, int32_t max_pixels, void* stream) {
+    SM_REQUIRE(src && images && dst && B > 0 && B <= 65535 && Hmax > 0 && Wmax > 0 && max_pixels > 0,
+               "sm_mask_planes_u8_to_f32: bad arguments");
+    const int gx = (max_pixels + 255) / 256 < 256 ? (max_pixels + 255) / 256 : 256;
+    hipLaunchKernelGGL(sm::eval_planes_u8_to_f32_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, src, images, dst, Hmax, Wmax);
+    return sm::check_launch("sm_mask_planes_u8_to_f32");
 }
 
 extern "C" int sm_evaluate_masks_f32(const sm_eval_args* a, void* stream) {

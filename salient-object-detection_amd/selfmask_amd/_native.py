@@ -116,6 +116,10 @@ class BilateralArgs(C.Structure):
                 ("confidence", C.c_double), ("cg_maxiter", C.c_int32), ("H", C.c_int32), ("W", C.c_int32)]
 
 
+class BilateralImage(C.Structure):
+    _fields_ = [("img_off", C.c_int64), ("px_off", C.c_int64), ("ws_off", C.c_int64), ("H", C.c_int32), ("W", C.c_int32)]
+
+
 class SpectralArgs(C.Structure):
     _fields_ = [("features", fp), ("labels", fp), ("cluster_sizes", C.POINTER(C.c_int32)), ("knn", fp), ("eigenvalues", fp),
                 ("embedding", fp), ("residuals", fp), ("info", fp), ("workspace", fp), ("workspace_bytes", C.c_size_t),
@@ -161,6 +165,9 @@ SYMBOLS = {
     "sm_preprocess_resize_u8": (C.c_int, [fp, fp, fp, fp, fp, C.c_int64, fp, fp, C.c_int32, C.c_int32, C.c_int32, fp]),
     "sm_upsample_selected_f64": (C.c_int, [fp, C.c_int64, fp, C.c_int32, fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp]),
     "sm_mask_u8_to_f32": (C.c_int, [fp, fp, C.c_int64, fp]),
+    "sm_upsample_selected_native_f64": (C.c_int, [fp, C.c_int64, fp, C.c_int32, fp, fp, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                                  C.c_int32, fp]),
+    "sm_mask_planes_u8_to_f32": (C.c_int, [fp, fp, fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp]),
     "sm_preprocess_normalize_u8": (C.c_int, [fp, fp, fp, fp, C.c_int32, C.c_int32, fp]),
     "sm_preprocess_normalize_pad_u8": (C.c_int, [fp, fp, fp, fp, C.c_int32, C.c_int32, C.c_int32, fp]),
     "sm_pick_mask_f32": (C.c_int, [fp, C.c_int64, fp, C.c_int64, fp, fp, C.c_int32, C.c_int32, C.c_int32, fp]),
@@ -181,6 +188,8 @@ SYMBOLS = {
     "sm_bilateral_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double]),
     "sm_bilateral_solver_f64": (C.c_int, [C.POINTER(BilateralArgs), fp]),
     "sm_bilateral_solver_batch_f64": (C.c_int, [C.POINTER(BilateralArgs), C.c_int32, fp]),
+    "sm_bilateral_mixed_workspace_bytes": (C.c_size_t, [fp, C.c_int32, C.c_double, C.c_double, C.c_double]),
+    "sm_bilateral_solver_mixed_f64": (C.c_int, [C.POINTER(BilateralArgs), fp, fp, C.c_int32, fp]),
     "sm_forward_workspace_bytes": (C.c_size_t, [C.POINTER(Weights), C.c_int32, C.c_int32, C.c_int32]),
     "sm_maskformer_forward": (C.c_int, [C.POINTER(Weights), C.POINTER(ForwardIO), fp, C.c_size_t, fp]),
     "sm_forward_timing": (C.c_int, [C.c_int]),

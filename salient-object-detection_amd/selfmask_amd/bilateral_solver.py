@@ -72,6 +72,88 @@ def bilateral_solver_batch_device(imgs_u8: torch.Tensor, targets: torch.Tensor, 
     return (soft, binary, info) if return_info else (soft, binary)
 
 
+class MixedBatch:
+    """Descriptor table of a batch whose images differ in size (sm_bilateral_image per image), built on the host and uploaded
+    with ONE asynchronous copy from page-locked memory on the current stream.  ``shapes``: (H, W) per image; ``img_offsets``:
+    byte offset of every image's (H, W, 3) uint8 pixels in the caller's pixel buffer (default: packed end to end; the
+    ``off`` of pipeline.pack_images fits as it is).  Targets / outputs are packed: image b's H*W values at ``px_off[b]``."""
+
+    def __init__(self, shapes, device, img_offsets=None, sigma_spatial=16, sigma_luma=16, sigma_chroma=8):
+        import ctypes
+        from .pipeline import _POOL
+        B = len(shapes)
+        if B == 0:
+            raise ValueError("an empty batch")
+        self.shapes = [(int(h), int(w)) for h, w in shapes]
+        self.sigmas = (float(sigma_spatial), float(sigma_luma), float(sigma_chroma))
+        self.host = (N.BilateralImage * B)()
+        io, po, self.px_off = 0, 0, []
+        for b, (h, w) in enumerate(self.shapes):
+            e = self.host[b]
+            e.img_off = int(img_offsets[b]) if img_offsets is not None else io
+            e.px_off, e.H, e.W = po, h, w
+            self.px_off.append(po)
+            io += h * w * 3
+            po += h * w
+        self.B, self.n_pixels, self.max_pixels = B, po, max(h * w for h, w in self.shapes)
+        self.img_bytes = max(self.host[b].img_off + h * w * 3 for b, (h, w) in enumerate(self.shapes))
+        self.ws_bytes = N.load().sm_bilateral_mixed_workspace_bytes(ctypes.addressof(self.host), B, *self.sigmas)
+        if self.ws_bytes == 0:
+            raise ValueError("unsupported size / sigmas for the bilateral lattice")
+        staging = _POOL.get(ctypes.sizeof(self.host), torch.uint8)
+        staging.numpy()[:] = np.frombuffer(bytes(self.host), np.uint8)
+        self.dev = staging.to(device, non_blocking=True)
+        _POOL.release_after((staging,), torch.cuda.current_stream(device))
+
+    def views(self, packed: torch.Tensor):
+        """Per-image (H, W) views of a packed buffer."""
+        return [packed[o:o + h * w].view(h, w) for o, (h, w) in zip(self.px_off, self.shapes)]
+
+
+def bilateral_solver_mixed_packed(pixels: torch.Tensor, target: torch.Tensor, batch: MixedBatch):
+    """The mixed-size solve on packed buffers: ``pixels`` uint8 (every image at its ``img_off``), ``target`` float64
+    (``batch.n_pixels`` values) -> packed (soft float64, binary uint8, info int32 (B, 4)).  One launch sequence for the batch."""
+    import ctypes
+    if not (pixels.is_cuda and target.is_cuda):
+        raise RuntimeError("bilateral solver (MI355X) needs device tensors; there is no CPU fallback")
+    assert pixels.dtype == torch.uint8 and pixels.is_contiguous() and pixels.numel() >= batch.img_bytes
+    assert target.dtype == torch.float64 and target.is_contiguous() and target.numel() == batch.n_pixels
+    dev = target.device
+    ws = torch.empty(batch.ws_bytes, dtype=torch.uint8, device=dev)
+    soft = torch.empty(batch.n_pixels, dtype=torch.float64, device=dev)
+    binary = torch.empty(batch.n_pixels, dtype=torch.uint8, device=dev)
+    info = torch.zeros((batch.B, 4), dtype=torch.int32, device=dev)
+    a = N.BilateralArgs()
+    a.img, a.target, a.soft, a.binary, a.info = pixels.data_ptr(), target.data_ptr(), soft.data_ptr(), binary.data_ptr(), info.data_ptr()
+    a.workspace, a.workspace_bytes = ws.data_ptr(), batch.ws_bytes
+    a.sigma_spatial, a.sigma_luma, a.sigma_chroma = batch.sigmas
+    a.lam, a.a_diag_min, a.cg_tol, a.confidence, a.cg_maxiter = 256.0, 1e-5, 1e-5, 0.999, 25  # bs_params (:170-175)
+    N.check(N.load().sm_bilateral_solver_mixed_f64(a, ctypes.addressof(batch.host), batch.dev.data_ptr(), batch.B,
+                                                   torch.cuda.current_stream(dev).cuda_stream), "sm_bilateral_solver_mixed_f64")
+    return soft, binary, info
+
+
+def bilateral_solver_mixed_device(imgs, targets, sigma_spatial=16, sigma_luma=16, sigma_chroma=8, return_info: bool = False,
+                                  shapes=None, img_offsets=None):
+    """Many images of DIFFERENT sizes in one launch sequence (sm_bilateral_solver_mixed_f64).  ``imgs`` / ``targets``: lists of
+    (H_b, W_b, 3) uint8 and (H_b, W_b) float64 device tensors - or already packed 1-D buffers with ``shapes`` (and, for the
+    pixels, ``img_offsets`` in bytes when they are not end to end).  Returns (list of soft (H_b, W_b) float64, list of binary
+    (H_b, W_b) uint8[, info (B, 4) int32]): views of two packed buffers.  Every image gives the bits of its own
+    ``bilateral_solver_output_device`` call, whatever its neighbours in the batch."""
+    if shapes is None:
+        shapes = [tuple(t.shape) for t in targets]
+        for im, (h, w) in zip(imgs, shapes):
+            assert im.shape == (h, w, 3) and im.dtype == torch.uint8
+        assert len(imgs) == len(targets)
+        imgs = torch.cat([im.reshape(-1) for im in imgs])
+        targets = torch.cat([t.reshape(-1).to(torch.float64) for t in targets])
+    if not (imgs.is_cuda and targets.is_cuda):
+        raise RuntimeError("bilateral solver (MI355X) needs device tensors; there is no CPU fallback")
+    batch = MixedBatch(shapes, targets.device, img_offsets, sigma_spatial, sigma_luma, sigma_chroma)
+    soft, binary, info = bilateral_solver_mixed_packed(imgs.contiguous(), targets.contiguous().to(torch.float64), batch)
+    return (batch.views(soft), batch.views(binary), info) if return_info else (batch.views(soft), batch.views(binary))
+
+
 def bilateral_solver_output(img, target, sigma_spatial=16, sigma_luma=16, sigma_chroma=8,
                             device="cuda:0") -> Tuple[np.ndarray, np.ndarray]:
     reference = np.array(img)  # PIL image or array (:159)

@@ -46,10 +46,12 @@ class Evaluator(BaseStructure):
         (image sharding, batches in flight, graph replay) and ``input_pipeline``: "device" (default) decodes on a pool of
         ``workers`` host threads running ahead of the GPU and does resize + ToTensor + Normalize in HIP kernels
         (pipeline.py, bit-identical inputs), "host" is the reference's order of work: one thread, PIL + numpy per image.
-        ``refine="bilateral"`` (batched mode only; BASELINE.json configs[2]): the picked query's mask is up-sampled to the
-        S x S input, refined by ``bilateral_solver_output`` (bilateral_solver.py:152-193) against the resized RGB image -
-        the whole batch in one launch sequence - and the solver's binary mask is scored by the same metric kernels; the
-        returned dict gains the seven ``*_refined`` values and ``metrics_<dataset>_refined.txt`` is written."""
+        ``refine="bilateral"`` (BASELINE.json configs[2]): the picked query's mask is up-sampled to the S x S input, refined
+        by ``bilateral_solver_output`` (bilateral_solver.py:152-193) against the resized RGB image - the whole batch in one
+        launch sequence - and the solver's binary mask is scored by the same metric kernels; the returned dict gains the seven
+        ``*_refined`` values and ``metrics_<dataset>_refined.txt`` is written.  At native resolution (``img_size=None``, batch 1
+        or token-grid buckets) the target is the mask the metrics scored - up-sampled by the reference factor and cropped to the
+        image - the reference image is the decoded one at its own size, and a bucket is ONE mixed-size solve."""
         assert cost_type == "iou", "the upper bound is chosen by IoU (evaluator.pyc@L216); other costs are unused"
         if not getattr(self.model, "use_binary_classifier", True):
             raise RuntimeError("the evaluator dereferences objectness unconditionally (evaluator.pyc@L219): "
@@ -75,8 +77,8 @@ class Evaluator(BaseStructure):
             plan = native_buckets([dataset.image_size(i) for i in mine], patch, batch_size)  # positions into `mine`
         if refine not in (None, "bilateral"):
             raise ValueError(f"refine={refine!r}: None or 'bilateral'")
-        if refine and (img_size is None or input_pipeline != "device"):
-            raise ValueError("refine='bilateral' runs in the batched mode (img_size given) on the device input pipeline")
+        if refine and input_pipeline != "device":
+            raise ValueError("refine='bilateral' runs on the device input pipeline")
         # One encoder attention path for the whole run (maskformer.attention_path): ragged last batches, token-grid buckets of
         # any size and shards of any world size then give the same bits per image as every other way of batching them
         prev_path = getattr(self.model, "attention_path", None)
@@ -131,7 +133,7 @@ class Evaluator(BaseStructure):
                     yield s, (shapes, lambda sh, S, dev, packed=packed, **kw: preprocess_on_device(sh, S, dev, packed=packed, **kw)), gts
                     s += len(shapes)
 
-        bucket_pos, bucket_rows = [], []
+        bucket_pos, bucket_rows, bucket_rows_refined = [], [], []
         try:
             if pin_path is not None:  # inside the try: whatever fails below, the shared model gets its "auto" back
                 self.model.attention_path = pin_path
@@ -142,6 +144,7 @@ class Evaluator(BaseStructure):
                         rgbs, pre = x
                         if refine:
                             x, u8 = pre(rgbs, img_size, device, pinned=True, return_u8=True)
+                            x = x if (img_size is not None or bucketed) else x[0]
                         else:
                             x = pre(rgbs, img_size, device, pinned=True)
                             x = x if (img_size is not None or bucketed) else x[0]
@@ -156,7 +159,20 @@ class Evaluator(BaseStructure):
                         bucket_rows.append(rows)  # stream's work: it serialised the three streams (2.2 ms per batch)
                     else:
                         rows_local[s:s + gtb.B] = rows
-                    if refine:
+                    if refine and img_size is None:
+                        # native sizes: u8 = the pixel bytes the input kernels read, image b at its pack_images offset
+                        from .bilateral_solver import MixedBatch, bilateral_solver_mixed_packed
+                        from .pipeline import packed_pixel_offsets
+                        assert gtb.shapes == [tuple(sh[:2]) for sh in rgbs], "ground truth and image sizes differ"
+                        mb = MixedBatch(gtb.shapes, device, packed_pixel_offsets(gtb.shapes))
+                        target = ops.upsample_selected_native(mask_pred, rows, mb, scale, "pick")
+                        _, binary, _ = bilateral_solver_mixed_packed(u8, target, mb)
+                        refined = ops.evaluate_masks(ops.mask_planes_u8_to_f32(binary, mb), rows[:, 0:1], gtb, scale=1.0)
+                        if bucketed:
+                            bucket_rows_refined.append(refined)
+                        else:
+                            rows_refined[s:s + gtb.B] = refined
+                    elif refine:
                         from .bilateral_solver import bilateral_solver_batch_device
                         target = ops.upsample_selected(mask_pred, rows, (img_size, img_size), "pick")
                         _, binary = bilateral_solver_batch_device(u8, target)
@@ -164,7 +180,10 @@ class Evaluator(BaseStructure):
                         rows_refined[s:s + gtb.B] = ops.evaluate_masks(refined, rows[:, 0:1], gtb, scale=0.0)
             ring.join()
             if bucket_rows:
-                rows_local[torch.as_tensor(bucket_pos, device=device)] = torch.cat(bucket_rows)
+                at = torch.as_tensor(bucket_pos, device=device)
+                rows_local[at] = torch.cat(bucket_rows)
+                if bucket_rows_refined:
+                    rows_refined[at] = torch.cat(bucket_rows_refined)
         finally:
             if prev_path == "auto":
                 self.model.attention_path = prev_path

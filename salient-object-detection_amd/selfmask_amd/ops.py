@@ -401,3 +401,32 @@ def mask_u8_to_f32(m: torch.Tensor) -> torch.Tensor:
     out = torch.empty(m.shape, dtype=torch.float32, device=m.device)
     N.check(N.load().sm_mask_u8_to_f32(m.data_ptr(), out.data_ptr(), m.numel(), _stream()), "sm_mask_u8_to_f32")
     return out
+
+
+def upsample_selected_native(mask_pred_last: torch.Tensor, rows: torch.Tensor, batch, scale: float, which: str = "pick") -> torch.Tensor:
+    """Native resolution: image b's picked ("pick") or upper-bound ("ub") mask as the evaluator's reference mode up-samples it,
+    F.interpolate(scale_factor=scale)[..., :H_b, :W_b], as float64 packed at ``batch.px_off`` (a bilateral_solver.MixedBatch) -
+    the value evaluate_masks(..., scale=scale) scored for that image, and the target of the mixed-size bilateral solve."""
+    _dev(mask_pred_last, rows)
+    B, nq, mh, mw = mask_pred_last.shape
+    assert mask_pred_last.stride(3) == 1 and mask_pred_last.stride(2) == mw and mask_pred_last.stride(1) == mh * mw
+    assert rows.shape == (B, 16) and rows.is_contiguous() and batch.B == B and scale > 0
+    for (h, w) in batch.shapes:
+        assert h <= int(mh * scale) and w <= int(mw * scale), "image larger than the up-sampled mask"
+    out = torch.empty(batch.n_pixels, dtype=torch.float64, device=mask_pred_last.device)
+    N.check(N.load().sm_upsample_selected_native_f64(mask_pred_last.data_ptr(), mask_pred_last.stride(0), rows.data_ptr(),
+                                                     14 if which == "pick" else 15, batch.dev.data_ptr(), out.data_ptr(), B, mh, mw,
+                                                     float(scale), batch.max_pixels, _stream()), "sm_upsample_selected_native_f64")
+    return out
+
+
+def mask_planes_u8_to_f32(binary: torch.Tensor, batch) -> torch.Tensor:
+    """Packed 0/1 planes of a MixedBatch -> (B, 1, Hmax, Wmax) float32, every image in the top-left corner of its zeroed plane: a
+    one-query mask_pred that evaluate_masks(..., scale=1.0) crops back to (H_b, W_b)."""
+    if not binary.is_cuda or binary.dtype != torch.uint8 or binary.numel() != batch.n_pixels:
+        raise RuntimeError("mask_planes_u8_to_f32 takes the packed uint8 planes of the batch on a HIP device")
+    Hm, Wm = max(h for h, _ in batch.shapes), max(w for _, w in batch.shapes)
+    out = torch.zeros((batch.B, 1, Hm, Wm), dtype=torch.float32, device=binary.device)
+    N.check(N.load().sm_mask_planes_u8_to_f32(binary.data_ptr(), batch.dev.data_ptr(), out.data_ptr(), batch.B, Hm, Wm,
+                                              batch.max_pixels, _stream()), "sm_mask_planes_u8_to_f32")
+    return out

@@ -140,10 +140,8 @@ def pack_images(images: Sequence[np.ndarray], S: Optional[int], pinned: bool = F
     import ctypes
     B = len(images)
     descr = (N.PreImage * B)()
-    offs, off = [], 0
-    for im in images:
-        offs.append(off)
-        off += (im.shape[0] * im.shape[1] * 3 + 15) & ~15
+    offs = packed_pixel_offsets([im.shape[:2] for im in images])
+    off = offs[-1] + ((images[-1].shape[0] * images[-1].shape[1] * 3 + 15) & ~15) if B else 0
     mk = (lambda n, dt: _POOL.get(n, dt)) if pinned else (lambda n, dt: torch.empty(n, dtype=dt))
     pixels = mk(max(off, 16), torch.uint8)
     pv = pixels.numpy()
@@ -174,6 +172,15 @@ def pack_images(images: Sequence[np.ndarray], S: Optional[int], pinned: bool = F
     dt = mk(ctypes.sizeof(descr), torch.uint8)
     dt.numpy()[:] = np.frombuffer(bytes(descr), np.uint8)
     return pixels, coef, dt, max(im.shape[0] for im in images), max(im.shape[0] * im.shape[1] for im in images), out_off
+
+
+def packed_pixel_offsets(shapes) -> List[int]:
+    """Byte offset of every image inside the pixel buffer pack_images lays out (each image starts on a 16-byte boundary)."""
+    offs, off = [], 0
+    for h, w in shapes:
+        offs.append(off)
+        off += (h * w * 3 + 15) & ~15
+    return offs
 
 
 _LUT = {}
@@ -226,7 +233,8 @@ def preprocess_on_device(images, S: Optional[int], device, pinned: bool = False,
     """Decoded uint8 images -> normalised fp32 model input on ``device``.  S given: (B, 3, S, S) after the PIL-exact
     bilinear resize (``return_u8``: also the resized uint8 images (B, S, S, 3)); S None: a list of (1, 3, H, W) tensors at
     native resolution (views of one buffer), or - ``pad_to=(Hp, Wp)`` - ONE (B, 3, Hp, Wp) batch with every image in the
-    top-left corner and zeros elsewhere (what make_input_divisible builds per image, vision_transformer.py:260-267)."""
+    top-left corner and zeros elsewhere (what make_input_divisible builds per image, vision_transformer.py:260-267).  At native
+    resolution ``return_u8`` adds the uploaded pixel buffer itself: image b's (H, W, 3) bytes at ``packed_pixel_offsets``."""
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("the input pipeline's resize / normalise kernels run on a HIP device (no CPU fallback)")
@@ -257,7 +265,7 @@ def preprocess_on_device(images, S: Optional[int], device, pinned: bool = False,
         out = torch.empty((B, 3, Hp, Wp), dtype=torch.float32, device=device)
         N.check(lib.sm_preprocess_normalize_pad_u8(pd.data_ptr(), dd.data_ptr(), _lut(device).data_ptr(), out.data_ptr(), B, Hp, Wp, st),
                 "sm_preprocess_normalize_pad_u8")
-        return out
+        return (out, pd) if return_u8 else out
     out = torch.empty(out_elems, dtype=torch.float32, device=device)
     N.check(lib.sm_preprocess_normalize_u8(pd.data_ptr(), dd.data_ptr(), _lut(device).data_ptr(), out.data_ptr(), B, max_px, st),
             "sm_preprocess_normalize_u8")
@@ -266,7 +274,7 @@ def preprocess_on_device(images, S: Optional[int], device, pinned: bool = False,
         h, w = (im.shape[:2] if hasattr(im, "shape") else im[:2])
         views.append(out[o:o + 3 * h * w].view(1, 3, h, w))
         o += 3 * h * w
-    return views
+    return (views, pd) if return_u8 else views
 
 
 from .decode_pool import decode_item  # noqa: E402  (sm_decode_worker.decode_item, loaded from the file's own path)
