@@ -469,6 +469,35 @@ int sm_upsample_selected_native_f64(const float* masks, int64_t mask_stride_b, c
 int sm_mask_planes_u8_to_f32(const uint8_t* src, const sm_bilateral_image* images, float* dst, int32_t B, int32_t Hmax,
                              int32_t Wmax, int32_t max_pixels, void* stream);
 
+/* ---- predictor finish (SaliencyPredictor): query masks -> the picked query's mask per image at the image's own size ------ */
+/* One fused step from the last decoder layer to the results: best[b] = arg-max objectness, and the picked mask up-sampled
+ * to (H_b, W_b) - pixel for pixel the value sm_evaluate_masks_f32 scores and sm_upsample_selected*_f64 emit - leaves as run
+ * boundaries (binary = value > 0.5f), as packed 0/1 planes, as packed 8-bit planes, or any subset of the three: an output
+ * whose pointer is NULL is neither computed nor written.  No up-sampled plane is stored in between: every pixel is computed from
+ * the low-resolution mask where it is needed (column-major for the runs, row-major for the planes).
+ * Nothing is allocated, copied or synchronised: the grids are sized from images_host (the same table on the host; H, W and
+ * px_off are checked against max_pixels), the kernels read args->images (device).  starts and info come together. */
+typedef struct sm_predict_args {
+    const float* masks;  int64_t mask_stride_b;   /* last decoder layer: image b, query q at + b*stride + q*mh*mw        */
+    const float* objectness; int64_t obj_stride_b;/* (B, nq) of that layer                                               */
+    const sm_bilateral_image* images;             /* DEVICE table, as the native refinement glue: H, W, px_off are read  */
+    int32_t* best;                                /* out (B): arg-max objectness, FIRST maximum (as sm_pick_mask_f32;   */
+                                                  /* NaN as its scan: never wins, except at q = 0 where it always does) */
+    int32_t* starts; int32_t* info; int32_t cap;  /* out, or NULL: exactly sm_rle_runs_u8's contract (positions x*H_b+y) */
+    uint8_t* binary;                              /* out, or NULL: packed 0/1 planes, image b at + px_off, row pitch W_b */
+    uint8_t* soft;                                /* out, or NULL: packed (uint8)(clip(v,0,1)*255), truncating           */
+    void* workspace; size_t workspace_bytes;      /* sm_predict_workspace_bytes, 256-B aligned; needed with starts only  */
+    int32_t B, nq, mh, mw, max_pixels;            /* nq <= 960; max_pixels >= every H_b*W_b, <= 2^22                     */
+    float scale;   /* > 0: F.interpolate(scale_factor=scale)[..., :H_b, :W_b]; 0: F.interpolate(size=(H_b, W_b))         */
+} sm_predict_args;
+size_t sm_predict_workspace_bytes(int32_t B, int32_t max_pixels); /* 0: B or max_pixels out of range */
+int sm_predict_masks_f32(const sm_predict_args* args, const sm_bilateral_image* images_host, void* stream);
+/* run boundaries of packed 0/1 planes of different sizes (the mixed solver's binary output): same outputs as sm_rle_runs_u8.
+ * Image b's H_b x W_b bytes (any non-zero = 1) lie at planes + px_off_b, row pitch W_b; workspace: sm_predict_workspace_bytes(B,
+ * largest H_b*W_b). */
+int sm_rle_runs_packed_u8(const uint8_t* planes, const sm_bilateral_image* images_dev, const sm_bilateral_image* images_host,
+                          int32_t B, int32_t* starts, int32_t cap, int32_t* info, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- whole forward --------------------------------------------------------------------------------------------- */
 typedef struct sm_enc_layer {
     const float *norm1_w, *norm1_b, *qkv_w, *qkv_b, *proj_w, *proj_b, *norm2_w, *norm2_b, *fc1_w, *fc1_b, *fc2_w,

@@ -22,6 +22,9 @@ def __getattr__(name):  # lazy: `python -m selfmask_amd.evaluator` must not find
     if name == "MaskGenerator":
         from .mask_generator import MaskGenerator
         return MaskGenerator
+    if name == "SaliencyPredictor":
+        from .predictor import SaliencyPredictor
+        return SaliencyPredictor
     if name == "SelfMaskInference":
         from .inference import SelfMaskInference
         return SelfMaskInference

@@ -120,6 +120,13 @@ class BilateralImage(C.Structure):
     _fields_ = [("img_off", C.c_int64), ("px_off", C.c_int64), ("ws_off", C.c_int64), ("H", C.c_int32), ("W", C.c_int32)]
 
 
+class PredictArgs(C.Structure):
+    _fields_ = [("masks", fp), ("mask_stride_b", C.c_int64), ("objectness", fp), ("obj_stride_b", C.c_int64), ("images", fp),
+                ("best", fp), ("starts", fp), ("info", fp), ("cap", C.c_int32), ("binary", fp), ("soft", fp), ("workspace", fp),
+                ("workspace_bytes", C.c_size_t), ("B", C.c_int32), ("nq", C.c_int32), ("mh", C.c_int32), ("mw", C.c_int32),
+                ("max_pixels", C.c_int32), ("scale", C.c_float)]
+
+
 class SpectralArgs(C.Structure):
     _fields_ = [("features", fp), ("labels", fp), ("cluster_sizes", C.POINTER(C.c_int32)), ("knn", fp), ("eigenvalues", fp),
                 ("embedding", fp), ("residuals", fp), ("info", fp), ("workspace", fp), ("workspace_bytes", C.c_size_t),
@@ -190,6 +197,9 @@ SYMBOLS = {
     "sm_bilateral_solver_batch_f64": (C.c_int, [C.POINTER(BilateralArgs), C.c_int32, fp]),
     "sm_bilateral_mixed_workspace_bytes": (C.c_size_t, [fp, C.c_int32, C.c_double, C.c_double, C.c_double]),
     "sm_bilateral_solver_mixed_f64": (C.c_int, [C.POINTER(BilateralArgs), fp, fp, C.c_int32, fp]),
+    "sm_predict_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "sm_predict_masks_f32": (C.c_int, [C.POINTER(PredictArgs), fp, fp]),
+    "sm_rle_runs_packed_u8": (C.c_int, [fp, fp, fp, C.c_int32, fp, C.c_int32, fp, fp, C.c_size_t, fp]),
     "sm_forward_workspace_bytes": (C.c_size_t, [C.POINTER(Weights), C.c_int32, C.c_int32, C.c_int32]),
     "sm_maskformer_forward": (C.c_int, [C.POINTER(Weights), C.POINTER(ForwardIO), fp, C.c_size_t, fp]),
     "sm_forward_timing": (C.c_int, [C.c_int]),

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from .ops import PackedImages
 
 
 def bilateral_solver_output_device(img_u8: torch.Tensor, target: torch.Tensor, sigma_spatial=16, sigma_luma=16,
@@ -72,38 +73,22 @@ def bilateral_solver_batch_device(imgs_u8: torch.Tensor, targets: torch.Tensor, 
     return (soft, binary, info) if return_info else (soft, binary)
 
 
-class MixedBatch:
+class MixedBatch(PackedImages):
     """Descriptor table of a batch whose images differ in size (sm_bilateral_image per image), built on the host and uploaded
-    with ONE asynchronous copy from page-locked memory on the current stream.  ``shapes``: (H, W) per image; ``img_offsets``:
-    byte offset of every image's (H, W, 3) uint8 pixels in the caller's pixel buffer (default: packed end to end; the
-    ``off`` of pipeline.pack_images fits as it is).  Targets / outputs are packed: image b's H*W values at ``px_off[b]``."""
+    with ONE asynchronous copy from page-locked memory on the current stream (``ops.PackedImages``), plus the solver's workspace
+    layout.  ``shapes``: (H, W) per image; ``img_offsets``: byte offset of every image's (H, W, 3) uint8 pixels in the caller's
+    pixel buffer (default: packed end to end; the ``off`` of pipeline.pack_images fits as it is).  Targets / outputs are packed:
+    image b's H*W values at ``px_off[b]``."""
 
     def __init__(self, shapes, device, img_offsets=None, sigma_spatial=16, sigma_luma=16, sigma_chroma=8):
-        import ctypes
-        from .pipeline import _POOL
-        B = len(shapes)
-        if B == 0:
-            raise ValueError("an empty batch")
-        self.shapes = [(int(h), int(w)) for h, w in shapes]
         self.sigmas = (float(sigma_spatial), float(sigma_luma), float(sigma_chroma))
-        self.host = (N.BilateralImage * B)()
-        io, po, self.px_off = 0, 0, []
-        for b, (h, w) in enumerate(self.shapes):
-            e = self.host[b]
-            e.img_off = int(img_offsets[b]) if img_offsets is not None else io
-            e.px_off, e.H, e.W = po, h, w
-            self.px_off.append(po)
-            io += h * w * 3
-            po += h * w
-        self.B, self.n_pixels, self.max_pixels = B, po, max(h * w for h, w in self.shapes)
-        self.img_bytes = max(self.host[b].img_off + h * w * 3 for b, (h, w) in enumerate(self.shapes))
-        self.ws_bytes = N.load().sm_bilateral_mixed_workspace_bytes(ctypes.addressof(self.host), B, *self.sigmas)
+        super().__init__(shapes, device, img_offsets)
+
+    def _prepare(self) -> None:
+        import ctypes
+        self.ws_bytes = N.load().sm_bilateral_mixed_workspace_bytes(ctypes.addressof(self.host), self.B, *self.sigmas)  # fills ws_off
         if self.ws_bytes == 0:
             raise ValueError("unsupported size / sigmas for the bilateral lattice")
-        staging = _POOL.get(ctypes.sizeof(self.host), torch.uint8)
-        staging.numpy()[:] = np.frombuffer(bytes(self.host), np.uint8)
-        self.dev = staging.to(device, non_blocking=True)
-        _POOL.release_after((staging,), torch.cuda.current_stream(device))
 
     def views(self, packed: torch.Tensor):
         """Per-image (H, W) views of a packed buffer."""

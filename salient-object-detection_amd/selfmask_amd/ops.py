@@ -430,3 +430,193 @@ def mask_planes_u8_to_f32(binary: torch.Tensor, batch) -> torch.Tensor:
     N.check(N.load().sm_mask_planes_u8_to_f32(binary.data_ptr(), batch.dev.data_ptr(), out.data_ptr(), batch.B, Hm, Wm,
                                               batch.max_pixels, _stream()), "sm_mask_planes_u8_to_f32")
     return out
+
+
+class PackedImages:
+    """Descriptor table (sm_bilateral_image per image) of a batch whose images differ in size, for the predictor's finish: built on
+    the host, uploaded with ONE asynchronous copy from page-locked memory on the current stream.  Per-pixel buffers are packed:
+    image b's H*W values at ``px_off[b]``.  ``bilateral_solver.MixedBatch`` is this table plus the solver's workspace layout."""
+
+    def __init__(self, shapes, device, img_offsets=None):
+        import ctypes
+        import numpy as np
+        from .pipeline import _POOL
+        B = len(shapes)
+        if B == 0:
+            raise ValueError("an empty batch")
+        self.shapes = [(int(h), int(w)) for h, w in shapes]
+        self.host = (N.BilateralImage * B)()
+        io, po, self.px_off = 0, 0, []
+        for b, (h, w) in enumerate(self.shapes):
+            if h < 1 or w < 1:
+                raise ValueError(f"image {b} is empty ({h} x {w})")
+            e = self.host[b]
+            e.img_off = int(img_offsets[b]) if img_offsets is not None else io
+            e.px_off, e.H, e.W = po, h, w
+            self.px_off.append(po)
+            io += h * w * 3
+            po += h * w
+        self.B, self.n_pixels, self.max_pixels = B, po, max(h * w for h, w in self.shapes)
+        self.img_bytes = max(self.host[b].img_off + h * w * 3 for b, (h, w) in enumerate(self.shapes))
+        self._prepare()  # a subclass completes the host table (the solver's workspace offsets) before it is uploaded
+        staging = _POOL.get(ctypes.sizeof(self.host), torch.uint8)
+        staging.numpy()[:] = np.frombuffer(bytes(self.host), np.uint8)
+        self.dev = staging.to(device, non_blocking=True)
+        _POOL.release_after((staging,), torch.cuda.current_stream(device))
+
+    def _prepare(self) -> None:
+        pass
+
+
+def _used_columns_host(starts: torch.Tensor, n: int):
+    """the first ``n`` columns of ``starts`` (device) as a numpy array: one asynchronous copy into page-locked memory on the
+    current stream and an event - the only wait is for that copy"""
+    host = torch.empty((starts.shape[0], max(n, 1)), dtype=torch.int32, pin_memory=True)
+    host.copy_(starts[:, :max(n, 1)], non_blocking=True)
+    done = torch.cuda.Event()
+    done.record(torch.cuda.current_stream(starts.device))
+    done.synchronize()
+    return host.numpy()
+
+
+def _runs_to_rle(info, starts, shapes):
+    """info (B, 2) {count, pixel 0}, starts (B, >= count) ascending column-major positions -> COCO uncompressed RLE dicts"""
+    import numpy as np
+    out = []
+    for b, (H, W) in enumerate(shapes):
+        n, first = int(info[b, 0]), int(info[b, 1])
+        counts = np.diff(np.concatenate([[0], starts[b, :n], [H * W]])).tolist()
+        out.append({"size": [H, W], "counts": ([0] + counts) if first else counts})
+    return out
+
+
+class PendingPredictions:
+    """The finish of one batch (``predict_masks``), queued on the current stream: ``result()`` waits for THAT batch's copies only.
+    The inputs are kept until then - on overflow of ``cap`` the runs are found once more with room for the longest code - so the
+    caller must not let the stream overwrite them (a replayed graph's static outputs) before asking."""
+
+    def __init__(self, mask_pred_last, objectness_last, table, scale, rle, binary, soft, cap):
+        B, nq, mh, mw = mask_pred_last.shape
+        dev = mask_pred_last.device
+        self._in = (mask_pred_last, objectness_last, table, float(scale))
+        self.table, self.cap = table, int(cap)
+        self.best = torch.empty(B, dtype=torch.int32, device=dev)
+        self.binary = torch.empty(table.n_pixels, dtype=torch.uint8, device=dev) if binary else None
+        self.soft = torch.empty(table.n_pixels, dtype=torch.uint8, device=dev) if soft else None
+        self._starts = self._info = self._ws = None
+        if rle:
+            self._starts = torch.empty((B, self.cap), dtype=torch.int32, device=dev)
+            self._info = torch.empty((B, 2), dtype=torch.int32, device=dev)
+        self._launch(self._starts, self._info, self.cap, self.binary, self.soft)
+        # best | info in one page-locked row per image; the planes in one buffer each
+        small = self.best[:, None] if not rle else torch.cat([self.best[:, None], self._info], dim=1)
+        self._small_h = torch.empty(small.shape, dtype=torch.int32, pin_memory=True)
+        self._small_h.copy_(small, non_blocking=True)
+        self._planes_h = {}
+        for name, t in (("binary", self.binary), ("soft", self.soft)):
+            if t is not None:
+                self._planes_h[name] = torch.empty(t.shape, dtype=torch.uint8, pin_memory=True)
+                self._planes_h[name].copy_(t, non_blocking=True)
+        self._done = torch.cuda.Event()
+        self._done.record(torch.cuda.current_stream(dev))
+
+    def _launch(self, starts, info, cap, binary, soft):
+        import ctypes
+        mask_pred, obj, table, scale = self._in
+        B, nq, mh, mw = mask_pred.shape
+        dev = mask_pred.device
+        lib = N.load()
+        a = N.PredictArgs()
+        a.masks, a.mask_stride_b = mask_pred.data_ptr(), mask_pred.stride(0)
+        a.objectness, a.obj_stride_b = obj.data_ptr(), obj.stride(0)
+        a.images, a.best = table.dev.data_ptr(), self.best.data_ptr()
+        a.starts, a.info, a.cap = _ptr(starts), _ptr(info), cap
+        a.binary, a.soft = _ptr(binary), _ptr(soft)
+        if starts is not None:
+            if self._ws is None:  # kept for the retry
+                wsb = lib.sm_predict_workspace_bytes(B, table.max_pixels)
+                if wsb == 0:
+                    raise ValueError("unsupported predict_masks shape (an image of more than 2^22 pixels?)")
+                self._ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+            a.workspace, a.workspace_bytes = self._ws.data_ptr(), self._ws.numel()
+        a.B, a.nq, a.mh, a.mw, a.max_pixels, a.scale = B, nq, mh, mw, table.max_pixels, scale
+        N.check(lib.sm_predict_masks_f32(a, ctypes.addressof(table.host), torch.cuda.current_stream(dev).cuda_stream),
+                "sm_predict_masks_f32")
+
+    def result(self) -> dict:
+        """-> {"best": [query index], "rle": [COCO uncompressed RLE dict], "binary" / "soft": [(H_b, W_b) uint8 array]} (the keys
+        asked for)"""
+        self._done.synchronize()
+        small = self._small_h.numpy()
+        out = {"best": small[:, 0].tolist()}
+        if self._starts is not None:
+            info = small[:, 1:3]
+            longest = int(info[:, 0].max(initial=0))
+            starts = self._starts
+            if longest > self.cap:  # noise-like masks: once more, with room for the longest code
+                starts = torch.empty((info.shape[0], longest), dtype=torch.int32, device=starts.device)
+                self._launch(starts, self._info, longest, None, None)
+            out["rle"] = _runs_to_rle(info, _used_columns_host(starts, longest), self.table.shapes)
+        for name, h in self._planes_h.items():
+            flat = h.numpy()
+            out[name] = [flat[o:o + hh * ww].reshape(hh, ww) for o, (hh, ww) in zip(self.table.px_off, self.table.shapes)]
+        self._in = None
+        return out
+
+
+def predict_masks(mask_pred_last: torch.Tensor, objectness_last: torch.Tensor, table, scale: float = 0.0, rle: bool = True,
+                  binary: bool = False, soft: bool = False, cap: int = 8192) -> PendingPredictions:
+    """The predictor's fused finish (sm_predict_masks_f32), without waiting: mask_pred_last (B, nq, mh, mw) probabilities (any batch
+    stride), objectness_last (B, nq), ``table`` a PackedImages / MixedBatch with the output size of every image.  The arg-max query's
+    mask, up-sampled as ``evaluate_masks`` up-samples it (``scale`` as there), thresholded at 0.5: ``rle`` its COCO run-length code,
+    ``binary`` / ``soft`` packed uint8 planes (0/1; clip(v, 0, 1) * 255 truncated).  ``.best`` (B,) int32 stays on the device."""
+    _dev(mask_pred_last, objectness_last)
+    B, nq, mh, mw = mask_pred_last.shape
+    assert mask_pred_last.stride(3) == 1 and mask_pred_last.stride(2) == mw and mask_pred_last.stride(1) == mh * mw
+    assert objectness_last.shape == (B, nq) and objectness_last.stride(1) == 1 and table.B == B
+    return PendingPredictions(mask_pred_last, objectness_last, table, scale, rle, binary, soft, max(1, min(int(cap), table.max_pixels)))
+
+
+class PendingPackedRuns:
+    """Run-length codes of packed 0/1 planes of different sizes (``rle_runs_packed_async``): ``result()`` -> one dict per image."""
+
+    def __init__(self, planes: torch.Tensor, table, cap: int):
+        self.planes, self.table, self.cap = planes, table, int(cap)
+        dev = planes.device
+        self._info = torch.empty((table.B, 2), dtype=torch.int32, device=dev)
+        self._ws = None
+        self._starts = self._launch(self.cap)
+        self._info_h = torch.empty((table.B, 2), dtype=torch.int32, pin_memory=True)
+        self._info_h.copy_(self._info, non_blocking=True)
+        self._done = torch.cuda.Event()
+        self._done.record(torch.cuda.current_stream(dev))
+
+    def _launch(self, cap):
+        import ctypes
+        lib, t, dev = N.load(), self.table, self.planes.device
+        if self._ws is None:  # kept for the retry
+            wsb = lib.sm_predict_workspace_bytes(t.B, t.max_pixels)
+            if wsb == 0:
+                raise ValueError("unsupported rle_runs_packed shape (an image of more than 2^22 pixels?)")
+            self._ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        starts = torch.empty((t.B, cap), dtype=torch.int32, device=dev)
+        N.check(lib.sm_rle_runs_packed_u8(self.planes.data_ptr(), t.dev.data_ptr(), ctypes.addressof(t.host), t.B, starts.data_ptr(), cap,
+                                          self._info.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
+                                          torch.cuda.current_stream(dev).cuda_stream),
+                "sm_rle_runs_packed_u8")
+        return starts
+
+    def result(self):
+        self._done.synchronize()
+        info = self._info_h.numpy()
+        longest = int(info[:, 0].max(initial=0))
+        starts = self._launch(longest) if longest > self.cap else self._starts
+        return _runs_to_rle(info, _used_columns_host(starts, longest), self.table.shapes)
+
+
+def rle_runs_packed_async(planes: torch.Tensor, table, cap: int = 8192) -> PendingPackedRuns:
+    """Packed 0/1 uint8 planes (image b's H_b x W_b bytes at ``table.px_off[b]`` - the mixed bilateral solver's binary output) ->
+    their run-length codes, without waiting (``.result()``): ``voting.rle_runs_async`` for images of different sizes."""
+    if not planes.is_cuda or planes.dtype != torch.uint8 or not planes.is_contiguous() or planes.numel() < table.n_pixels:
+        raise RuntimeError("rle_runs_packed_async takes the packed uint8 planes of the batch on a HIP device (no CPU fallback)")
+    return PendingPackedRuns(planes, table, max(1, min(int(cap), table.max_pixels)))

@@ -1,0 +1,324 @@
+"""Bulk prediction for images WITHOUT ground truth: a list of image files in, the model's saliency mask per file out, at the
+file's own size and at device throughput.
+
+    SaliencyPredictor(network)(p_images, output="rle")  -> {file name: COCO uncompressed RLE dict}
+
+The sibling of ``Evaluator.__call__`` (which needs a ground truth per image and returns metrics, not masks) and of
+``MaskGenerator.__call__`` (pseudo-masks from clustering, not from the decoder): headers probed and checked before anything is
+queued, token-grid buckets at native resolution (``pipeline.native_buckets``) or S x S batches, decode workers and device
+preprocessing, the graphed forward, one batch per stream of a ``StreamRing`` and - new - a fused finish (``ops.predict_masks``,
+csrc/predict.hip) that goes from the last decoder layer's query masks straight to run boundaries (or packed planes), read back
+``streams`` batches later through page-locked buffers.  The mask of a file is the one the evaluator would score: the arg-max
+objectness query, up-sampled by ``patch // scale_factor`` and cropped (native) or resized to the file's size (``img_size``),
+thresholded at ``evaluator.MASK_THRESHOLD``.
+"""
+import argparse
+import os
+from collections import deque
+from typing import Dict, Optional, Sequence
+
+import numpy as np
+import torch
+
+OUTPUTS = ("rle", "binary", "soft")
+DEFAULT_CAP = 8192       # run boundaries stored per image before the retry, as voting.rle_runs_async
+MAX_PIXELS = 1 << 22     # sm_predict_masks_f32's largest image
+
+
+class _Files:
+    """what PrefetchingLoader needs of a dataset: image paths, no ground truth"""
+
+    def __init__(self, p_imgs):
+        self.p_imgs, self.p_gts = list(p_imgs), [None] * len(p_imgs)
+
+
+class SaliencyPredictor:
+    def __init__(self, network, device: torch.device = torch.device("cuda:0"), batch_size: int = 64, streams: int = 3,
+                 workers: Optional[int] = None, hip_graph: bool = True, cap: int = DEFAULT_CAP):
+        """``network``: a ``selfmask_amd.MaskFormer`` with ``use_binary_classifier=True`` on ``device``; ``batch_size``: the most
+        images per forward (of ONE token grid at native resolution); ``streams``: batches in flight; ``workers``: decode processes
+        (default: this rank's share of the host cores); ``hip_graph``: replay recurring batch shapes as captured graphs."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError(f"SaliencyPredictor runs on a HIP device (got {device}); there is no CPU fallback")
+        if network is None:
+            raise ValueError("SaliencyPredictor needs `network` (a selfmask_amd.MaskFormer holding the SelfMask weights)")
+        if not getattr(network, "use_binary_classifier", False):
+            raise RuntimeError("the predictor picks the arg-max objectness query: use_binary_classifier=True is required")
+        params = getattr(network, "parameters", None)
+        p = next(iter(params()), None) if callable(params) else None
+        if p is not None and p.device.type != "cuda":
+            raise RuntimeError(f"SaliencyPredictor needs `network` on a HIP device (its weights are on {p.device}); there is no CPU "
+                               f"fallback - call network.to(device)")
+        self.network, self.device, self.batch_size = network, device, max(1, int(batch_size))
+        self.streams, self.workers, self.hip_graph, self.cap = max(1, int(streams)), workers, bool(hip_graph), int(cap)
+        self.last_best: Dict[str, int] = {}
+        self._ring = None
+
+    # ---- planning: everything that can be refused is refused here, before a byte is queued ------------------------------------
+    def _plan(self, p_images: Sequence[str], img_size: Optional[int], outputs, refine):
+        from .datasets import probe_size
+        for o in outputs:
+            if o not in OUTPUTS:
+                raise ValueError(f"output={o!r}: one of {OUTPUTS}")
+        if refine not in (None, "bilateral"):
+            raise ValueError(f"refine={refine!r}: None or 'bilateral'")
+        if refine and "soft" in outputs:
+            raise ValueError("output='soft' with refine='bilateral': the solver's soft output is not a [0, 1] sigmoid map; ask for "
+                             "'rle' or 'binary'")
+        if img_size is not None and int(img_size) < 1:
+            raise ValueError(f"img_size={img_size}")
+        p_images = [str(p) for p in p_images]
+        names = [p.split("/")[-1] for p in p_images]
+        seen = {}
+        for p, n in zip(p_images, names):
+            if n in seen:
+                raise ValueError(f"SaliencyPredictor: {p} and {seen[n]} share the file name {n!r}, which keys the result; nothing was run")
+            seen[n] = p
+        sizes = []
+        for p in p_images:
+            if not os.path.isfile(p):
+                raise FileNotFoundError(f"SaliencyPredictor: {p} does not exist; nothing was run")
+            try:
+                hw = probe_size(p)
+            except Exception as e:
+                raise ValueError(f"SaliencyPredictor: {p} is not a readable image ({type(e).__name__}: {e}); nothing was run") from e
+            if hw[0] < 1 or hw[1] < 1 or hw[0] * hw[1] > MAX_PIXELS:
+                raise ValueError(f"SaliencyPredictor: {p} is {hw[0]} x {hw[1]}: 1 .. {MAX_PIXELS} pixels per image; nothing was run")
+            sizes.append((int(hw[0]), int(hw[1])))
+        return self._batches(p_images, names, sizes, img_size)
+
+    def _batches(self, p_images, names, sizes, img_size):
+        """-> the plan (paths, names, sizes, batches of positions): token-grid buckets at native resolution, plain slices otherwise"""
+        from .pipeline import native_buckets
+        if img_size is None:
+            batches = native_buckets(sizes, self.network.encoder.patch_size, self.batch_size)
+        else:
+            batches = [list(range(s, min(s + self.batch_size, len(sizes)))) for s in range(0, len(sizes), self.batch_size)]
+        return p_images, names, sizes, batches
+
+    @torch.no_grad()
+    def __call__(self, p_images: Sequence[str], img_size: Optional[int] = None, scale_factor: int = 2, output: str = "rle",
+                 refine: Optional[str] = None, comm=None) -> Dict[str, object]:
+        """-> {file name: COCO uncompressed RLE dict (``output="rle"``) | (H, W) uint8 array: 0/1 (``"binary"``) or
+        clip(p, 0, 1) * 255 truncated (``"soft"``)}, in list order; ``.last_best`` {file name: query index}.
+        ``img_size=None``: native resolution in token-grid buckets, the mask up-sampled by ``patch // scale_factor`` and cropped -
+        the evaluator's reference mode; ``img_size=S``: inputs resized to S x S, the mask resized to the file's own size.
+        ``refine="bilateral"``: the mask the metrics would score goes through the bilateral solver against the decoded pixels (native:
+        one mixed-size solve per bucket; ``img_size``: the S x S solve of the evaluator, its binary mask then resized to the file's
+        size like any mask) and the solver's binary result is returned.  ``comm``: this rank takes files rank, rank + W, ... of the
+        list and every rank returns the codes of ALL files (RLE only)."""
+        sharded = comm is not None and comm.world_size > 1
+        assert not sharded or output == "rle", "the gather exchanges run-length codes"
+        plan = self._plan(p_images, img_size, (output,), refine)
+        if sharded:
+            from .distributed import gather_dicts, shard_indices
+            paths, names = plan[0], plan[1]
+            idx = shard_indices(len(paths), comm.rank, comm.world_size)  # this rank's files, with the sizes already probed
+            mine = self._run([paths[i] for i in idx], img_size, scale_factor, ("rle",), refine,
+                             plan=self._batches([paths[i] for i in idx], [names[i] for i in idx], [plan[2][i] for i in idx], img_size))
+            best = gather_dicts(self.last_best, comm, self.device)
+            merged = gather_dicts(mine["rle"], comm, self.device)
+            self.last_best = {n: best[n] for n in names}
+            return {n: merged[n] for n in names}  # the list's order, whatever the sharding
+        return self._run(plan[0], img_size, scale_factor, (output,), refine, plan=plan)[output]
+
+    # ---- one rank's files -----------------------------------------------------------------------------------------------------
+    def _finish(self, out, shapes, u8, scale, img_size, outputs, refine):
+        """the forward's outputs of one batch -> a pending result (``.result()`` -> {"best", "rle" / "binary" / "soft"})"""
+        from . import ops
+        mask_pred, obj = out["mask_pred"], out["objectness"]
+        if mask_pred.dim() == 5:  # last decoder layer
+            mask_pred, obj = mask_pred[:, -1], obj[:, -1]
+        obj = obj.squeeze(-1)
+        want = dict(rle="rle" in outputs, binary="binary" in outputs, soft="soft" in outputs, cap=self.cap)
+        if not refine:
+            return ops.predict_masks(mask_pred, obj, ops.PackedImages(shapes, self.device), scale, **want)
+        B = mask_pred.shape[0]
+        if img_size is None:
+            from .bilateral_solver import MixedBatch, bilateral_solver_mixed_packed
+            from .pipeline import packed_pixel_offsets
+            mb = MixedBatch(shapes, self.device, packed_pixel_offsets(shapes))
+            head = ops.predict_masks(mask_pred, obj, mb, scale, rle=False)  # the arg-max alone
+            rows = torch.zeros((B, 16), dtype=torch.float32, device=self.device)
+            rows[:, 14] = head.best.float()
+            target = ops.upsample_selected_native(mask_pred, rows, mb, scale, "pick")
+            _, binary, _ = bilateral_solver_mixed_packed(u8, target, mb)
+            return _Refined(head, ops.rle_runs_packed_async(binary, mb, self.cap) if want["rle"] else None,
+                            binary if want["binary"] else None, mb)
+        from .bilateral_solver import bilateral_solver_batch_device
+        head = ops.predict_masks(mask_pred, obj, ops.PackedImages([(img_size, img_size)] * B, self.device), 0.0, rle=False)
+        rows = torch.zeros((B, 16), dtype=torch.float32, device=self.device)
+        rows[:, 14] = head.best.float()
+        target = ops.upsample_selected(mask_pred, rows, (img_size, img_size), "pick")
+        _, binary = bilateral_solver_batch_device(u8, target)
+        # the solver's S x S binary as a one-query mask: resized to the file's own size exactly as the evaluator scores it
+        tail = ops.predict_masks(ops.mask_u8_to_f32(binary).unsqueeze(1), torch.ones((B, 1), dtype=torch.float32, device=self.device),
+                                 ops.PackedImages(shapes, self.device), 0.0, **want)
+        return _Refined(head, tail, None, None)
+
+    def _run(self, p_images, img_size, scale_factor, outputs, refine, plan=None) -> Dict[str, Dict[str, object]]:
+        from .graphs import GraphedForward
+        from .pipeline import PrefetchingLoader, preprocess_on_device
+        from .streams import StreamRing
+        p_images, names, sizes, batches = plan if plan is not None else self._plan(p_images, img_size, outputs, refine)
+        results = {o: {} for o in outputs}
+        best: Dict[str, int] = {}
+        self.last_best = best
+        if not p_images:
+            return results
+        model, device = self.network, self.device
+        patch = model.encoder.patch_size
+        native = img_size is None
+        scale = float(patch // scale_factor) if native else 0.0  # exactly the evaluator's choice
+        # the evaluator's admission policy per mode: S x S shapes recur from the second batch on; token-grid buckets are captured
+        # from their 32nd sighting per stream (a capture costs ~10 ms and ~50 grids on three streams rarely come back that often)
+        graphed = GraphedForward(model, enabled=self.hip_graph and isinstance(model, torch.nn.Module), max_graphs=24 if native else 8,
+                                 admit_after=31 if native else 2)
+        # one encoder attention path for the whole call: a file's result must not depend on the batch it lands in
+        prev_path = getattr(model, "attention_path", None)
+        pin_path = ("fused" if (not native and self.batch_size >= 16) else "unfused") if prev_path == "auto" else None
+        if self._ring is None:
+            self._ring = StreamRing(device, self.streams)
+        ring = self._ring
+        ring.home = torch.cuda.current_stream(device)
+        ring.fork()
+        pending = deque()
+
+        def settle():
+            # a batch is settled before the next one is queued on ITS stream, so a replayed graph's outputs are still that batch's
+            # should the run boundaries have to be found again (more than ``cap`` of them)
+            bnames, pend = pending.popleft()
+            res = pend.result()
+            best.update(zip(bnames, res["best"]))
+            for o in outputs:
+                for n, v in zip(bnames, res[o]):
+                    results[o][n] = v if o == "rle" else v.copy()
+
+        from .decode_pool import default_workers
+        avg = max(1, len(p_images) // len(batches))  # buckets are often smaller than batch_size: keep every decode worker busy
+        depth = max(len(ring.streams) + 1, -(-2 * (self.workers or default_workers()) // avg))
+        loader = PrefetchingLoader(_Files(p_images), range(len(p_images)), self.batch_size, workers=self.workers, depth=depth,
+                                   batches=batches, pack=True, pack_size=img_size)
+        try:
+            if pin_path is not None:
+                model.attention_path = pin_path
+            for ((packed, shapes), _gts, idx) in loader:
+                with ring.next():
+                    if native:
+                        Hp = -(-max(h for h, _ in shapes) // patch) * patch
+                        Wp = -(-max(w for _, w in shapes) // patch) * patch
+                        x = preprocess_on_device(shapes, None, device, packed=packed, pad_to=(Hp, Wp), return_u8=bool(refine))
+                    else:
+                        x = preprocess_on_device(shapes, img_size, device, packed=packed, return_u8=bool(refine))
+                    x, u8 = x if refine else (x, None)
+                    assert [sizes[i] for i in idx] == [tuple(s) for s in shapes], "a file's header and its decoded size differ"
+                    pending.append(([names[i] for i in idx], self._finish(graphed(x), shapes, u8, scale, img_size, outputs, refine)))
+                if len(pending) >= len(ring.streams):
+                    settle()
+            while pending:
+                settle()
+        finally:
+            ring.join()  # also when a batch raised: the caller's stream waits for whatever is still queued on the ring
+            if prev_path == "auto":
+                model.attention_path = prev_path
+        self.graph_stats = {"captures": graphed.captures, "replays": graphed.replays, "failed": graphed.failed}
+        order = {n: k for k, n in enumerate(names)}
+        self.last_best = {n: best[n] for n in names}
+        return {o: dict(sorted(r.items(), key=lambda kv: order[kv[0]])) for o, r in results.items()}
+
+
+class _Refined:
+    """pending result of a refined batch: the arg-max of ``head`` and the solver's binary as runs (``runs``) or packed planes"""
+
+    def __init__(self, head, runs, binary, table):
+        self.head, self.runs, self.table = head, runs, table
+        self._binary_h = None
+        if binary is not None:
+            self._binary_h = torch.empty(binary.shape, dtype=torch.uint8, pin_memory=True)
+            self._binary_h.copy_(binary, non_blocking=True)
+            self._done = torch.cuda.Event()
+            self._done.record(torch.cuda.current_stream(binary.device))
+
+    def result(self):
+        out = {"best": self.head.result()["best"]}
+        if self.table is None:  # resized mode: ``runs`` is the second finish, with whatever was asked for
+            out.update({k: v for k, v in self.runs.result().items() if k != "best"})
+            return out
+        if self.runs is not None:
+            out["rle"] = self.runs.result()
+        if self._binary_h is not None:
+            self._done.synchronize()
+            flat = self._binary_h.numpy()
+            out["binary"] = [flat[o:o + h * w].reshape(h, w) for o, (h, w) in zip(self.table.px_off, self.table.shapes)]
+        return out
+
+
+IMAGE_SUFFIXES = (".jpg", ".jpeg", ".png", ".bmp", ".webp")
+
+
+def list_images(src: str):
+    """a directory (its image files, sorted) or a text file with one path per line"""
+    if os.path.isdir(src):
+        return sorted(os.path.join(src, f) for f in os.listdir(src) if f.lower().endswith(IMAGE_SUFFIXES))
+    with open(src) as f:
+        return [ln.strip() for ln in f if ln.strip()]
+
+
+def write_pngs(soft: Dict[str, np.ndarray], png_dir: str, threads: int = 4) -> None:
+    """the soft maps as 8-bit greyscale PNGs (<file stem>.png: what the external SOD toolkits read), on a small host thread pool"""
+    from concurrent.futures import ThreadPoolExecutor
+    from PIL import Image
+    os.makedirs(png_dir, exist_ok=True)
+    stems = [os.path.splitext(n)[0] for n in soft]
+    assert len(set(stems)) == len(stems), "two files share a stem: their PNGs would overwrite each other"
+
+    def one(item):
+        name, arr = item
+        Image.fromarray(np.ascontiguousarray(arr, np.uint8)).save(os.path.join(png_dir, os.path.splitext(name)[0] + ".png"))
+
+    with ThreadPoolExecutor(max_workers=max(1, threads)) as pool:
+        list(pool.map(one, soft.items()))
+
+
+def build_parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(prog="python -m selfmask_amd.predictor",
+                                 description="masks for a directory (or a list file) of images without ground truth")
+    ap.add_argument("--config", type=str, required=True)
+    ap.add_argument("--p_state_dict", type=str, required=True)
+    ap.add_argument("--images", type=str, required=True, help="a directory, or a text file with one image path per line")
+    ap.add_argument("--out", type=str, required=True, help="JSON: {file name: COCO uncompressed RLE}")
+    ap.add_argument("--img_size", type=int, default=None, help="resize inputs to S x S (default: native resolution in token-grid buckets)")
+    ap.add_argument("--batch_size", type=int, default=64)
+    ap.add_argument("--refine", type=str, default=None, choices=["bilateral"])
+    ap.add_argument("--png_dir", type=str, default=None, help="also write the soft maps as 8-bit PNGs into this directory")
+    ap.add_argument("--gpu_id", type=int, default=0)
+    return ap
+
+
+def main(argv=None):
+    import json
+    import yaml
+    from .maskformer import load_checkpoint
+    from .misc import get_model
+    args = build_parser().parse_args(argv)
+    if args.png_dir and args.refine:
+        raise SystemExit("--png_dir writes soft maps, which --refine does not produce")
+    cfg = argparse.Namespace(**yaml.safe_load(open(args.config)))
+    device = torch.device("cuda", args.gpu_id)
+    model = get_model("maskformer", configs=cfg)
+    load_checkpoint(model, args.p_state_dict)
+    model = model.to(device).eval()
+    pred = SaliencyPredictor(model, device=device, batch_size=args.batch_size)
+    outputs = ("rle", "soft") if args.png_dir else ("rle",)
+    res = pred._run(list_images(args.images), args.img_size, getattr(cfg, "scale_factor", 2), outputs, args.refine)
+    with open(args.out, "w") as f:
+        json.dump(res["rle"], f, separators=(",", ":"))
+    if args.png_dir:
+        write_pngs(res["soft"], args.png_dir)
+    print(f"{len(res['rle'])} masks -> {args.out}" + (f", PNGs -> {args.png_dir}" if args.png_dir else ""))
+    return res
+
+
+if __name__ == "__main__":
+    main()
