@@ -193,6 +193,27 @@ int sm_attention_f32(const sm_attn_args* args, void* stream);
  * times the fp32 MFMA rate. Strides/pointers in float units, multiples of 8 (one F16X2 group), 32-B aligned. */
 int sm_attention_f16x2(const sm_attn_args* args, void* stream);
 
+/* The post-softmax matrix itself - `attn` of Attention.forward (vision_transformer.py:122-123: (q @ k^T) * scale, then
+ * .softmax(dim=-1)), what VisionTransformer.get_last_selfattention returns (:307-314):
+ *   P[b, h, i - q0, j] = softmax_j(scale * q_i . k_j)   for the query rows i in [q0, q0 + nq), every key j < n_k.
+ * Q and K in the F16X2 split format with the strides and alignment rules of sm_attn_args: float units, multiples of 8,
+ * pointers 32-B aligned.  Products are the three-MFMA split form of sm_attention_f16x2.  P is fp32 (batch, heads, nq, n_k),
+ * row-major, rows of exactly n_k floats without padding (only the images' blocks may lie apart: sPb).  Head dimension 64, heads <= 6, any n_k >= 1.  Two passes over the
+ * keys (maximum and sum, then recompute and write); a row's bits do not depend on q0 / nq or on the batch it is launched
+ * in; keys past n_k contribute exactly 0 and are never written; no atomics. */
+typedef struct sm_attn_probs_args {
+    const float *Q, *K;
+    float* P;
+    int64_t sQb, sQr, sKb, sKr;
+    int64_t sPb;    /* floats between the images' blocks of P; 0 = packed (heads * nq * n_k) */
+    int32_t batch, heads;
+    int32_t n_q;    /* rows of Q per image (q0 + nq <= n_q) */
+    int32_t n_k;
+    int32_t q0, nq; /* the query rows written */
+    float scale;
+} sm_attn_probs_args;
+int sm_attention_probs_f16x2(const sm_attn_probs_args* args, void* stream);
+
 /* Fused QKV projection + attention of one encoder block - Attention.forward up to (excluding) the output projection
  * (vision_transformer.py:113-131: self.qkv(x) -> reshape/permute -> (q @ k^T) * scale -> softmax -> @ v -> merge heads).
  * One workgroup per (image, head): K and V of the head are produced into LDS, Q into registers; the (B*N, 1152) QKV
@@ -583,6 +604,16 @@ typedef struct sm_forward_io {
                                 batch sizes pins one (the Evaluator does) */
     int32_t last_layer_only; /* 1: return_intermediate=False (maskformer.py:219-220) - only the last decoder layer reaches the mask
                                 einsum; mask_logits / mask_pred are then (B,1,nq,2gh,2gw).  features / queries keep all L layers */
+    /* attention of the LAST encoder block (VisionTransformer.get_last_selfattention, vision_transformer.py:307-314: the
+     * post-softmax `attn` of Attention.forward :122-123), N = 1 + gh*gw tokens.  When block 12's normalised input is ready its
+     * Q|K projection (rows [0, 768) of the qkv weight) goes to the workspace's QKV region and sm_attention_probs_f16x2 writes
+     * what is asked for; the forward then carries on unchanged (block 12's own attention overwrites that region in stream
+     * order), every other output keeps its bits.  gemm_mode 0, 1, 2 (3 -> SM_EINVAL).  All three zero: today's launch sequence. */
+    float* last_attn;        /* (B, 6, N, N) or NULL */
+    float* last_attn_cls;    /* (B, 6, N): row 0, the CLS token's attention over all tokens, or NULL */
+    int32_t attn_only;       /* 1: return right after the attention output(s), as get_last_selfattention does - block 12's V
+                                projection, attn V, proj, MLP, the final norm and the decoder are not launched.  Needs at least one
+                                of the two pointers; every other output pointer may be NULL */
 } sm_forward_io;
 
 /* bytes of workspace MaskFormer.forward needs for this shape */

@@ -124,6 +124,12 @@ static Ws carve(const Shape& s, float* base) {
     return w;
 }
 
+#define TRY_(x)               \
+    do {                      \
+        int _rc = (x);        \
+        if (_rc) return _rc;  \
+    } while (0)
+
 struct Ctx {
     bool S;    // split-operand GEMM mode (activations that only feed GEMMs are F16X2)
     bool W16;  // ... with the weights in the W16 format: weight GEMMs run the single-accumulator kernel (gemm_w16.hip)
@@ -189,6 +195,34 @@ static int attn(const Ctx& c, sm_attn_args& a) {
                  8.0 * a.batch * a.heads * SM_HEAD_DIM * ((double)a.n_q + a.n_k));  // Q, O and K, V once, 4 B per element
     a.out_f16x2 = c.S;
     return c.S ? sm_attention_f16x2(&a, c.st) : sm_attention_f32(&a, c.st);
+}
+
+// The last block's attention matrix (sm_forward_io.last_attn / last_attn_cls; vision_transformer.py:307-314): Q|K of block 12 -
+// rows [0, 768) of its qkv weight, a prefix of the same tensor in every weight format, with the same fold arguments - into
+// ws.QKV as (M, 768), then the probabilities kernel once per requested output.  `x` is what the block's own qkv projection reads.
+static int last_attention(const Ctx& c, const sm_forward_io* io, int B, int N, int64_t M, const float* x, const float* qkv_w, float qkv_s,
+                          const float* qkv_b, const Fold& fq, float* QK, float* tmp) {
+    const int D = SM_EMBED;
+    if (c.S) {
+        TRY_(linear(c, x, D, qkv_w, qkv_s, qkv_b, QK, 2 * D, M, 2 * D, D, SM_EPI_BIAS, nullptr, 0, true, fq));
+    } else {  // exact-fp32 mode: the projection is fp32 (into `tmp`), the kernel's operands are its F16X2 split
+        TRY_(linear(c, x, D, qkv_w, qkv_s, qkv_b, tmp, 2 * D, M, 2 * D, D, SM_EPI_BIAS, nullptr, 0, false, fq));
+        TRY_(sm_split_f16x2(tmp, 2 * D, QK, 2 * D, M, 2 * D, c.st));
+    }
+    sm_attn_probs_args a = {};
+    a.Q = QK; a.K = QK + D;
+    a.sQb = a.sKb = (int64_t)N * 2 * D; a.sQr = a.sKr = 2 * D;
+    a.batch = B; a.heads = SM_HEADS; a.n_q = N; a.n_k = N; a.scale = 0.125f;
+    for (int pass = 0; pass < 2; ++pass) {
+        a.P = pass ? io->last_attn_cls : io->last_attn;
+        if (!a.P) continue;
+        a.q0 = 0; a.nq = pass ? 1 : N;
+        // both walks over the keys count: 2 x (2 nq n_k 64) per head; bytes: Q, K once + P
+        TapScope tap(c.st, "attention_probs_f16x2_kernel", 4.0 * B * SM_HEADS * a.nq * (double)N * SM_HEAD_DIM,
+                     4.0 * B * SM_HEADS * (SM_HEAD_DIM * ((double)a.nq + N) + (double)a.nq * N));
+        TRY_(sm_attention_probs_f16x2(&a, c.st));
+    }
+    return SM_OK;
 }
 
 struct LnOpt {
@@ -314,6 +348,11 @@ static int forward(const sm_weights* w, const sm_forward_io* io, float* wsbase, 
         const float* qkv_w = f1 ? e.qkv_fw : e.qkv_w;
         const float* qkv_b = f1 ? e.qkv_fb : e.qkv_b;
         const float qkv_s = f1 ? e.qkv_fs : e.qkv_s;
+        if (i == SM_ENC_DEPTH - 1 && (io->last_attn || io->last_attn_cls)) {
+            // ws.HID is free here (block 11's fc2 has consumed it), ws.QKV is rewritten by this block's own projection below
+            TRY(last_attention(c, io, s.B, s.N, s.M, ws.Xn, qkv_w, qkv_s, qkv_b, fq, ws.QKV, ws.HID));
+            if (io->attn_only) return SM_OK;
+        }
         if (fused_qkv) {
             sm_qkv_attn_args q = {};
             q.Xn = ws.Xn; q.Wqkv = qkv_w; q.bias = qkv_b; q.O = ws.AO; q.ldx = D; q.ldo = D;
@@ -576,7 +615,14 @@ static int validate(const sm_weights* w, const sm_forward_io* io) {
             SM_REQUIRE(ok, "sm_maskformer_forward: ln_fold needs the gain-scaled weights, folded biases and row sums (*_fw, *_fb, *_c, *_fs) of every encoder layer");
         }
     }
-    if (!io->encoder_only)
+    const bool want_attn = io->last_attn || io->last_attn_cls;
+    SM_REQUIRE(io->attn_only == 0 || io->attn_only == 1, "sm_maskformer_forward: attn_only=%d (0 or 1)", io->attn_only);
+    SM_REQUIRE(!io->attn_only || want_attn, "sm_maskformer_forward: attn_only needs last_attn or last_attn_cls");
+    SM_REQUIRE(!want_attn || w->gemm_mode != 3,
+               "sm_maskformer_forward: last_attn / last_attn_cls are not available in gemm_mode 3 (the one-MFMA diagnostic)");
+    if (io->attn_only)
+        ;  // the forward stops inside block 12: no other output is written
+    else if (!io->encoder_only)
         SM_REQUIRE(io->mask_pred && (io->objectness || w->mask_head_ffn || w->no_objectness) && io->features,
                    "sm_maskformer_forward: null output");
     else

@@ -47,6 +47,13 @@ class AttnArgs(C.Structure):
                 ("scale", C.c_float), ("out_f16x2", C.c_int32)]
 
 
+class AttnProbsArgs(C.Structure):
+    _fields_ = [("Q", fp), ("K", fp), ("P", fp),
+                ("sQb", C.c_int64), ("sQr", C.c_int64), ("sKb", C.c_int64), ("sKr", C.c_int64), ("sPb", C.c_int64),
+                ("batch", C.c_int32), ("heads", C.c_int32), ("n_q", C.c_int32), ("n_k", C.c_int32),
+                ("q0", C.c_int32), ("nq", C.c_int32), ("scale", C.c_float)]
+
+
 class QkvAttnArgs(C.Structure):
     _fields_ = [("Xn", fp), ("Wqkv", fp), ("bias", fp), ("O", fp), ("ldx", C.c_int64), ("ldo", C.c_int64),
                 ("B", C.c_int32), ("N", C.c_int32), ("w_scale", C.c_float), ("scale", C.c_float), ("out_f16x2", C.c_int32),
@@ -85,7 +92,8 @@ class ForwardIO(C.Structure):
     _fields_ = [("x", fp), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
                 ("mask_logits", fp), ("mask_pred", fp), ("objectness", fp), ("features", fp), ("queries", fp),
                 ("patch_tokens", fp), ("encoder_only", C.c_int32), ("attn_path", C.c_int32),
-                ("last_layer_only", C.c_int32)]
+                ("last_layer_only", C.c_int32),
+                ("last_attn", fp), ("last_attn_cls", fp), ("attn_only", C.c_int32)]
 
 
 class KernelTime(C.Structure):
@@ -157,6 +165,7 @@ SYMBOLS = {
     "sm_broadcast_rows_f32": (C.c_int, [fp, fp, C.c_int32, C.c_int32, fp]),
     "sm_attention_f32": (C.c_int, [C.POINTER(AttnArgs), fp]),
     "sm_attention_f16x2": (C.c_int, [C.POINTER(AttnArgs), fp]),
+    "sm_attention_probs_f16x2": (C.c_int, [C.POINTER(AttnProbsArgs), fp]),
     "sm_qkv_attention_w16": (C.c_int, [C.POINTER(QkvAttnArgs), fp]),
     "sm_qkv_attention_max_tokens": (C.c_int, []),
     "sm_im2col_patches_f32": (C.c_int, [fp, fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp]),

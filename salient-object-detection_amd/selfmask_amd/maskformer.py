@@ -63,6 +63,14 @@ class VisionTransformerParams(nn.Module):
         self.n_heads = num_heads
         self.patch_size = patch_size
 
+    def get_last_selfattention(self, x: torch.Tensor) -> torch.Tensor:
+        """vision_transformer.py:307-314: the post-softmax attention of the last block, (B, heads, N, N) with N = 1 + gh*gw.
+        The arithmetic lives in the owning MaskFormer's forward (``MaskFormer.get_last_selfattention``)."""
+        owner = self.__dict__.get("_owner")
+        if owner is None:
+            raise RuntimeError("this encoder is a parameter container: get_last_selfattention needs the MaskFormer that owns it")
+        return owner.get_last_selfattention(x)
+
     def make_input_divisible(self, x: torch.Tensor) -> torch.Tensor:
         """vision_transformer.py:260-267 (shape helper for callers; the HIP im2col pads implicitly)."""
         h0, w0 = x.shape[-2:]
@@ -139,6 +147,9 @@ class MaskFormer(nn.Module):
         d = N.EMBED
         # NB: unlike utils/misc.py:196,243 no remote DINO weights are fetched; the checkpoint overwrites them anyway.
         self.encoder = VisionTransformerParams(patch_size=patch_size)
+        # back-reference for encoder.get_last_selfattention, kept out of nn.Module's registries (no submodule cycle, no
+        # state_dict entries)
+        self.encoder.__dict__["_owner"] = self
         self.decoder = _Decoder(d, N.HEADS, d * self.encoder.mlp_ratio, n_decoder_layers)
         self.query_embed = nn.Embedding(n_queries, d).weight  # registered as parameter "query_embed"
         if use_binary_classifier:
@@ -320,14 +331,62 @@ class MaskFormer(nn.Module):
         return ws
 
     # ---- forward ----------------------------------------------------------------------------------------------
+    _ATTN_PATHS = {"auto": 0, "fused": 1, "unfused": 2}
+
+    @torch.no_grad()
+    def get_last_selfattention(self, x: torch.Tensor, cls_only: bool = False, attn_path=0,
+                               workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """VisionTransformer.get_last_selfattention (vision_transformer.py:307-314): the post-softmax attention matrix of the last
+        encoder block, (B, 6, N, N) with N = 1 + gh*gw - or, with ``cls_only``, only row 0 (the CLS token's attention over all
+        tokens) as (B, 6, N), the same bits as ``[:, :, 0, :]`` of the full result.  The forward stops right after writing it
+        (sm_forward_io.attn_only).  ``attn_path``: the encoder kernel set of blocks 1-11 (0 / "auto": the model's
+        ``attention_path``; 1 / "fused"; 2 / "unfused")."""
+        if not x.is_cuda:
+            raise RuntimeError("MaskFormer (MI355X) needs its input on a HIP device; there is no CPU fallback")
+        if self.gemm_mode == "f16":
+            raise RuntimeError("attention maps are not available in the 'f16' throughput-mode diagnostic")
+        lib = N.load()
+        x = x.contiguous().float()
+        B, c, H, W = x.shape
+        assert c == 3, "expected an RGB image batch (B,3,H,W)"
+        p = self.encoder.patch_size
+        n_tok = ceil(H / p) * ceil(W / p) + 1
+        w = self._weights()
+        ws = workspace if workspace is not None else self._get_workspace(w, x)
+        io = N.ForwardIO()
+        io.x, io.B, io.H, io.W = x.data_ptr(), B, H, W
+        path = self._ATTN_PATHS.get(attn_path, attn_path)
+        if path not in (0, 1, 2):
+            raise ValueError(f"attn_path={attn_path!r}: 0 / 'auto', 1 / 'fused' or 2 / 'unfused'")
+        io.attn_path = path if path else self._ATTN_PATHS[self.attention_path]
+        io.attn_only = 1
+        if cls_only:
+            out = torch.empty((B, N.HEADS, n_tok), device=x.device, dtype=torch.float32)
+            io.last_attn_cls = out.data_ptr()
+        else:
+            out = torch.empty((B, N.HEADS, n_tok, n_tok), device=x.device, dtype=torch.float32)
+            io.last_attn = out.data_ptr()
+        N.check(lib.sm_maskformer_forward(w, io, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream),
+                "sm_maskformer_forward")
+        return out
+
     @torch.no_grad()
     def forward(self, x: torch.Tensor, encoder_only: bool = False, skip_decoder: bool = False,
-                return_logits: bool = False, workspace: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                return_logits: bool = False, workspace: Optional[torch.Tensor] = None,
+                return_attention=False) -> Dict[str, torch.Tensor]:
         """x: (B,3,H,W) normalised image on a HIP device.  Output dict as maskformer.py:240-251:
         5-D path -> {"objectness" (B,L,nq,1), "mask_pred" (B,L,nq,s gh,s gw) in [0,1] (s = scale_factor), "features" (B,384)};
         3-D path (return_intermediate=False, use_binary_classifier=False) -> {"mask_pred" logits (B,nq,s gh,s gw),
         "features"}.  ``return_logits`` additionally returns the pre-sigmoid einsum as "mask_logits" and the decoder
-        queries / encoder patch tokens (parity taps)."""
+        queries / encoder patch tokens (parity taps).  ``return_attention``: True adds "last_selfattention" (B,6,N,N), the last
+        encoder block's post-softmax attention (vision_transformer.py:307-314), "cls" adds "cls_attention" (B,6,gh,gw), its CLS
+        row without the CLS column on the token grid; every other entry keeps the bits it has without it."""
+        if return_attention not in (False, True, "cls"):
+            raise ValueError(f"return_attention={return_attention!r}: False, True or 'cls'")
+        if return_attention and encoder_only:
+            raise ValueError("return_attention with encoder_only: call get_last_selfattention(x) for the attention alone")
+        if return_attention and self.gemm_mode == "f16":
+            raise RuntimeError("attention maps are not available in the 'f16' throughput-mode diagnostic")
         if not x.is_cuda:
             raise RuntimeError("MaskFormer (MI355X) needs its input on a HIP device; there is no CPU fallback")
         if self.training:
@@ -351,7 +410,7 @@ class MaskFormer(nn.Module):
         ws = workspace if workspace is not None else self._get_workspace(w, x)
         io = N.ForwardIO()
         io.x, io.B, io.H, io.W = x.data_ptr(), B, H, W
-        io.attn_path = {"auto": 0, "fused": 1, "unfused": 2}[self.attention_path]
+        io.attn_path = self._ATTN_PATHS[self.attention_path]
         if encoder_only:
             # the reference's encoder_only branch raises on a non-contiguous view (maskformer.py:188); return the
             # evident intent: (B, gh, gw, 384) patch tokens
@@ -376,6 +435,14 @@ class MaskFormer(nn.Module):
             extras["queries"] = torch.empty((B, L, nq, N.EMBED), device=dev, dtype=torch.float32)
             extras["patch_tokens"] = torch.empty((B, gh * gw, N.EMBED), device=dev, dtype=torch.float32)
             io.queries, io.patch_tokens = extras["queries"].data_ptr(), extras["patch_tokens"].data_ptr()
+        attn = {}
+        if return_attention == "cls":
+            cls_row = torch.empty((B, N.HEADS, gh * gw + 1), device=dev, dtype=torch.float32)
+            io.last_attn_cls = cls_row.data_ptr()
+            attn["cls_attention"] = cls_row[:, :, 1:].reshape(B, N.HEADS, gh, gw)
+        elif return_attention:
+            attn["last_selfattention"] = torch.empty((B, N.HEADS, gh * gw + 1, gh * gw + 1), device=dev, dtype=torch.float32)
+            io.last_attn = attn["last_selfattention"].data_ptr()
         N.check(lib.sm_maskformer_forward(w, io, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream),
                 "sm_maskformer_forward")
         if not self.return_intermediate:  # 3-D path: last layer, un-sigmoided (maskformer.py:219-220)
@@ -386,6 +453,7 @@ class MaskFormer(nn.Module):
             out = {"objectness": objectness, "mask_pred": mask_pred, "features": features}
         if return_logits:
             out.update(extras)
+        out.update(attn)
         return out
 
 

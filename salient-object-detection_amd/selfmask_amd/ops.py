@@ -221,6 +221,27 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float = 
     return o
 
 
+def attention_probs(q: torch.Tensor, k: torch.Tensor, scale: float = 0.125, q0: int = 0, nq: Optional[int] = None,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The post-softmax attention matrix itself (vision_transformer.py:122-123): q (B,Nq,H,64), k (B,Nk,H,64) fp32 views (last two
+    dims contiguous), converted to F16X2 rows here -> softmax(scale * q k^T) for the query rows [q0, q0 + nq) as (B,H,nq,Nk) fp32
+    (sm_attention_probs_f16x2).  ``out``: a (B,H,nq,Nk) view to write into - contiguous per image, any stride between images."""
+    _dev(q, k, out)
+    B, n_q, H, dh = q.shape
+    nk = k.shape[1]
+    nq = n_q - q0 if nq is None else nq
+    q, k = (split_f16x2(t.reshape(t.shape[0], t.shape[1], H * dh).contiguous()).view(t.shape[0], t.shape[1], H, dh) for t in (q, k))
+    assert dh == 64 and q.stride(3) == 1 and q.stride(2) == 64 and k.stride(2) == 64
+    p = out if out is not None else torch.empty((B, H, max(nq, 0), nk), device=q.device, dtype=torch.float32)
+    assert tuple(p.shape) == (B, H, nq, nk) and (p.numel() == 0 or p[0].is_contiguous())
+    a = N.AttnProbsArgs()
+    a.Q, a.K, a.P = q.data_ptr(), k.data_ptr(), p.data_ptr()
+    a.sQb, a.sQr, a.sKb, a.sKr, a.sPb = q.stride(0), q.stride(1), k.stride(0), k.stride(1), p.stride(0) if B > 1 else 0
+    a.batch, a.heads, a.n_q, a.n_k, a.q0, a.nq, a.scale = B, H, n_q, nk, q0, nq, scale
+    N.check(N.load().sm_attention_probs_f16x2(a, _stream()), "sm_attention_probs_f16x2")
+    return p
+
+
 def fold_layernorm(weight: torch.Tensor, bias: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor):
     """LayerNorm(gamma, beta) folded into the Linear(weight, bias) it feeds -> (W16 tensor of weight * gamma, its 2^-s, folded
     bias b + W beta, row sums c of the gain-scaled weight as rounded to W16): LN(x) W^T + b = r (x W'^T - mu c) + b'."""
