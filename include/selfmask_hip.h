@@ -519,6 +519,51 @@ int sm_predict_masks_f32(const sm_predict_args* args, const sm_bilateral_image* 
 int sm_rle_runs_packed_u8(const uint8_t* planes, const sm_bilateral_image* images_dev, const sm_bilateral_image* images_host,
                           int32_t B, int32_t* starts, int32_t cap, int32_t* info, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- baseline JPEG decode, bit-identical to Pillow (libjpeg-turbo: JDCT_ISLOW, fancy up-sampling): host entropy decode + device
+ * dequantise / IDCT / chroma up-sampling / YCbCr -> RGB (csrc/jpeg.hip, csrc/jpeg_host.h) ------------------------------------- */
+#define SM_JPEG_UNSUPPORTED 1 /* not an error: the file (or something inside it) is not for this decoder - decode it with Pillow */
+#define SM_JPEG_GRAY 0        /* sm_jpeg_info.sampling / sm_jpeg_image.sampling: one component                                 */
+#define SM_JPEG_444 1         /* Y Cb Cr, luma 1x1                                                                             */
+#define SM_JPEG_422 2         /* luma 2x1 (chroma at half the width)                                                           */
+#define SM_JPEG_420 3         /* luma 2x2 (chroma at half the width and height)                                                */
+typedef struct sm_jpeg_info {
+    int32_t width, height, components;   /* of the frame header, also of an unsupported file as far as it could be read (else 0) */
+    int32_t h_samp[4], v_samp[4];        /* sampling factors per component                                                       */
+    int32_t supported;                   /* 1: SOF0, 8 bits, ONE scan over all components, grey or YCbCr (no Adobe transform 0,
+                                            ids not 'R','G','B'), luma 1x1 / 2x1 / 2x2 with chroma 1x1, 8- or 16-bit tables    */
+    int32_t sampling;                    /* SM_JPEG_*                                                                            */
+    int32_t mcus_x, mcus_y;
+    int32_t blocks_w[3], blocks_h[3];    /* 8 x 8 blocks per component row / column, padded to whole MCUs                        */
+    int32_t restart_interval;
+    int64_t coef_bytes;                  /* 128 bytes per block, component after component                                       */
+} sm_jpeg_info;
+/* HOST functions over the bytes of a file (no GPU involved; thread-safe; every read is bounds-checked).
+ * Probe: the markers up to the scan header.  Always SM_OK for non-null arguments; look at info->supported.
+ * Entropy decode: probe + Huffman decode of the scan (restart intervals, byte stuffing) -> coef_out: int16 coefficients, 64 per
+ * block in natural (de-zigzagged, row-major) order, DC prediction undone, component c's blocks_h[c] x blocks_w[c] blocks in raster
+ * order, components end to end (`cap` bytes of room, SM_ENOSPACE if info->coef_bytes is more); qt_out: components x 64 quantisation
+ * values in natural order.  SM_JPEG_UNSUPPORTED (info->supported = 0) for an unsupported file AND for any anomaly in the stream -
+ * a bit pattern that is no code, a run past coefficient 63, data that ends early or goes on after the last MCU, an unexpected marker,
+ * coefficients beyond what an encoder produces: nothing is guessed, such a file is Pillow's. */
+int sm_jpeg_probe(const uint8_t* bytes, size_t len, sm_jpeg_info* info);
+int sm_jpeg_entropy_decode(const uint8_t* bytes, size_t len, int16_t* coef_out, size_t cap, uint16_t* qt_out, sm_jpeg_info* info);
+/* DEVICE half: one table entry per image of a batch whose images may all differ in size and sampling */
+typedef struct sm_jpeg_image {
+    int64_t coef_off;  /* byte offset of the image's coefficients inside `coef`, a multiple of 16                                */
+    int64_t out_off;   /* byte offset of its (H, W, 3) interleaved uint8 RGB inside `pixels_out`, a multiple of 16               */
+    int32_t qt_off;    /* element offset of its tables inside `qt`: components x 64 uint16                                       */
+    int32_t H, W;
+    int32_t sampling;  /* SM_JPEG_*                                                                                              */
+    int32_t blocks_w[3], blocks_h[3]; /* sm_jpeg_info's; 0 for the components a grey image lacks                                */
+    int32_t reserved[2];
+} sm_jpeg_image;
+/* B images in two launches (dequantise + islow IDCT per block; up-sample + colour-convert + 16-byte RGB stores).  descr_host sizes
+ * the grids and is validated, descr_dev is the same table in device memory; `coef` (device, what the entropy decode wrote, uploaded
+ * by the caller) is CONSUMED: each block's first 64 bytes are overwritten with its samples.  Nothing is allocated, copied or
+ * synchronised.  Image b's pixels are the bits Pillow's Image.open(f).convert("RGB") gives, whatever else is in the batch. */
+int sm_jpeg_decode_batch_u8(const sm_jpeg_image* descr_host, const sm_jpeg_image* descr_dev, int32_t B, int16_t* coef,
+                            const uint16_t* qt, uint8_t* pixels_out, void* stream);
+
 /* ---- whole forward --------------------------------------------------------------------------------------------- */
 typedef struct sm_enc_layer {
     const float *norm1_w, *norm1_b, *qkv_w, *qkv_b, *proj_w, *proj_b, *norm2_w, *norm2_b, *fc1_w, *fc1_b, *fc2_w,

@@ -135,6 +135,22 @@ class PredictArgs(C.Structure):
                 ("max_pixels", C.c_int32), ("scale", C.c_float)]
 
 
+class JpegInfo(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("components", C.c_int32), ("h_samp", C.c_int32 * 4),
+                ("v_samp", C.c_int32 * 4), ("supported", C.c_int32), ("sampling", C.c_int32), ("mcus_x", C.c_int32),
+                ("mcus_y", C.c_int32), ("blocks_w", C.c_int32 * 3), ("blocks_h", C.c_int32 * 3), ("restart_interval", C.c_int32),
+                ("coef_bytes", C.c_int64)]
+
+
+class JpegImage(C.Structure):
+    _fields_ = [("coef_off", C.c_int64), ("out_off", C.c_int64), ("qt_off", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("sampling", C.c_int32), ("blocks_w", C.c_int32 * 3), ("blocks_h", C.c_int32 * 3), ("reserved", C.c_int32 * 2)]
+
+
+JPEG_UNSUPPORTED = 1
+JPEG_GRAY, JPEG_444, JPEG_422, JPEG_420 = range(4)
+
+
 class SpectralArgs(C.Structure):
     _fields_ = [("features", fp), ("labels", fp), ("cluster_sizes", C.POINTER(C.c_int32)), ("knn", fp), ("eigenvalues", fp),
                 ("embedding", fp), ("residuals", fp), ("info", fp), ("workspace", fp), ("workspace_bytes", C.c_size_t),
@@ -209,6 +225,9 @@ SYMBOLS = {
     "sm_predict_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "sm_predict_masks_f32": (C.c_int, [C.POINTER(PredictArgs), fp, fp]),
     "sm_rle_runs_packed_u8": (C.c_int, [fp, fp, fp, C.c_int32, fp, C.c_int32, fp, fp, C.c_size_t, fp]),
+    "sm_jpeg_probe": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(JpegInfo)]),
+    "sm_jpeg_entropy_decode": (C.c_int, [C.c_char_p, C.c_size_t, fp, C.c_size_t, fp, C.POINTER(JpegInfo)]),
+    "sm_jpeg_decode_batch_u8": (C.c_int, [fp, fp, C.c_int32, fp, fp, fp, fp]),
     "sm_forward_workspace_bytes": (C.c_size_t, [C.POINTER(Weights), C.c_int32, C.c_int32, C.c_int32]),
     "sm_maskformer_forward": (C.c_int, [C.POINTER(Weights), C.POINTER(ForwardIO), fp, C.c_size_t, fp]),
     "sm_forward_timing": (C.c_int, [C.c_int]),

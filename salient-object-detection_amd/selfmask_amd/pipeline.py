@@ -119,6 +119,14 @@ class PinnedPool:
             self._by_ptr[ent[0].data_ptr()] = ent
             return ent[0][:n]
 
+    def release(self, tensors) -> None:
+        """The buffers behind ``tensors`` were never handed to a copy (their batch failed on the host): free at once."""
+        with self._lock:
+            for t in tensors:
+                ent = self._by_ptr.get(t.data_ptr())
+                if ent is not None:
+                    ent[1] = None
+
     def release_after(self, tensors, stream) -> None:
         """The buffers behind ``tensors`` may be reused once the work queued on ``stream`` so far has finished."""
         ev = torch.cuda.Event()
@@ -133,24 +141,17 @@ class PinnedPool:
 _POOL = PinnedPool()
 
 
-def pack_images(images: Sequence[np.ndarray], S: Optional[int], pinned: bool = False):
-    """images: list of (H, W, 3) uint8 arrays -> (pixels u8 tensor, coef int32 tensor, descr u8 tensor, max_h, max_pixels,
-    out_elems).  S = output side for the resize path, None for native resolution.  ``pinned``: buffers come from the
-    page-locked pool (the caller must call ``_POOL.release_after`` once the H2D copies are queued)."""
+def pack_tables(shapes, S: Optional[int], pinned: bool = False):
+    """The part of ``pack_images`` that depends on the sizes alone: -> (coef int32 tensor, descr u8 tensor, out_elems) for images of
+    ``shapes`` [(H, W)] laid out at ``packed_pixel_offsets(shapes)`` - also what pixels that are already on the device need."""
     import ctypes
-    B = len(images)
+    B = len(shapes)
     descr = (N.PreImage * B)()
-    offs = packed_pixel_offsets([im.shape[:2] for im in images])
-    off = offs[-1] + ((images[-1].shape[0] * images[-1].shape[1] * 3 + 15) & ~15) if B else 0
+    offs = packed_pixel_offsets(shapes)
     mk = (lambda n, dt: _POOL.get(n, dt)) if pinned else (lambda n, dt: torch.empty(n, dtype=dt))
-    pixels = mk(max(off, 16), torch.uint8)
-    pv = pixels.numpy()
     coef_parts, coef_index, ci = [], {}, 0
     out_off = 0
-    for b, im in enumerate(images):
-        assert im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3, "decoded images must be (H, W, 3) uint8"
-        h, w = im.shape[:2]
-        pv[offs[b]:offs[b] + h * w * 3] = im.reshape(-1)
+    for b, (h, w) in enumerate(shapes):
         d = descr[b]
         d.off, d.H, d.W, d.out_off = offs[b], h, w, out_off
         out_off += 3 * h * w
@@ -171,6 +172,25 @@ def pack_images(images: Sequence[np.ndarray], S: Optional[int], pinned: bool = F
         coef.numpy()[:ci] = np.concatenate(coef_parts)
     dt = mk(ctypes.sizeof(descr), torch.uint8)
     dt.numpy()[:] = np.frombuffer(bytes(descr), np.uint8)
+    return coef, dt, out_off
+
+
+def pack_images(images: Sequence[np.ndarray], S: Optional[int], pinned: bool = False):
+    """images: list of (H, W, 3) uint8 arrays -> (pixels u8 tensor, coef int32 tensor, descr u8 tensor, max_h, max_pixels,
+    out_elems).  S = output side for the resize path, None for native resolution.  ``pinned``: buffers come from the
+    page-locked pool (the caller must call ``_POOL.release_after`` once the H2D copies are queued)."""
+    B = len(images)
+    for im in images:
+        assert im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3, "decoded images must be (H, W, 3) uint8"
+    shapes = [im.shape[:2] for im in images]
+    offs = packed_pixel_offsets(shapes)
+    off = offs[-1] + ((images[-1].shape[0] * images[-1].shape[1] * 3 + 15) & ~15) if B else 0
+    pixels = _POOL.get(max(off, 16), torch.uint8) if pinned else torch.empty(max(off, 16), dtype=torch.uint8)
+    pv = pixels.numpy()
+    for b, im in enumerate(images):
+        h, w = im.shape[:2]
+        pv[offs[b]:offs[b] + h * w * 3] = im.reshape(-1)
+    coef, dt, out_off = pack_tables(shapes, S, pinned)
     return pixels, coef, dt, max(im.shape[0] for im in images), max(im.shape[0] * im.shape[1] for im in images), out_off
 
 
@@ -244,9 +264,10 @@ def preprocess_on_device(images, S: Optional[int], device, pinned: bool = False,
         pinned = True
     pixels, coef, descr, max_h, max_px, out_elems = packed if packed is not None else pack_images(images, S, pinned)
     st = torch.cuda.current_stream(device).cuda_stream
-    pd, cd, dd = (t.to(device, non_blocking=True) for t in (pixels, coef, descr))
+    # pixels that are on the device already (selfmask_amd.jpeg.packed_from_device) stay where they are
+    pd, cd, dd = (t if t.is_cuda else t.to(device, non_blocking=True) for t in (pixels, coef, descr))
     if pinned:
-        _POOL.release_after((pixels, coef, descr), torch.cuda.current_stream(device))
+        _POOL.release_after([t for t in (pixels, coef, descr) if not t.is_cuda], torch.cuda.current_stream(device))
     lib = N.load()
     B = len(images)
     if S is not None:

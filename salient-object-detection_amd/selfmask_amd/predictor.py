@@ -23,6 +23,7 @@ import torch
 OUTPUTS = ("rle", "binary", "soft")
 DEFAULT_CAP = 8192       # run boundaries stored per image before the retry, as voting.rle_runs_async
 MAX_PIXELS = 1 << 22     # sm_predict_masks_f32's largest image
+DECODES = ("host", "device")
 
 
 class _Files:
@@ -32,12 +33,56 @@ class _Files:
         self.p_imgs, self.p_gts = list(p_imgs), [None] * len(p_imgs)
 
 
+def _probe(p):
+    """(H, W) from the library's own header parser where the device decode takes the file, from Pillow's otherwise"""
+    from .datasets import probe_size
+    from .jpeg import probe_jpeg
+    h = probe_jpeg(p)
+    return (h.height, h.width) if h.supported else probe_size(p)
+
+
+class _DeviceDecoded:
+    """``decode="device"``: the loader of the loop - ((host half of ``jpeg.decode_jpeg_batch``, shapes), None, positions) per batch.
+    One feeder thread runs the host halves (file reads + entropy decode on the thread pool) ``depth`` batches ahead; the consumer
+    queues the device half on its batch's stream (``HostBatch.to_device``)."""
+
+    def __init__(self, p_images, batches, threads, depth):
+        self.p_images, self.batches, self.threads, self.depth = p_images, batches, threads, max(1, depth)
+
+    def __iter__(self):
+        from concurrent.futures import ThreadPoolExecutor
+        from .jpeg import HostBatch
+        with ThreadPoolExecutor(max_workers=1, thread_name_prefix="sm_jpeg_feed") as feeder:
+            def submit(k):
+                return feeder.submit(HostBatch, [self.p_images[i] for i in self.batches[k]], self.threads)
+            inflight = deque(submit(k) for k in range(min(self.depth, len(self.batches))))
+            hb = None
+            try:
+                for k in range(len(self.batches)):
+                    hb = inflight.popleft().result()
+                    if k + self.depth < len(self.batches):
+                        inflight.append(submit(k + self.depth))
+                    yield (hb, hb.shapes), None, self.batches[k]
+                    hb = None  # the consumer came back for more: it has queued this batch's copy
+            finally:  # the loop ended early: batches prepared ahead (and one the consumer may not have queued) go back to the pool
+                for fut in inflight:
+                    fut.cancel()
+                for left in [hb] + [f.result() for f in inflight if not f.cancelled() and f.exception() is None]:
+                    if left is not None and not left.queued:
+                        left.discard()
+
+
 class SaliencyPredictor:
     def __init__(self, network, device: torch.device = torch.device("cuda:0"), batch_size: int = 64, streams: int = 3,
-                 workers: Optional[int] = None, hip_graph: bool = True, cap: int = DEFAULT_CAP):
+                 workers: Optional[int] = None, hip_graph: bool = True, cap: int = DEFAULT_CAP, decode: str = "host"):
         """``network``: a ``selfmask_amd.MaskFormer`` with ``use_binary_classifier=True`` on ``device``; ``batch_size``: the most
         images per forward (of ONE token grid at native resolution); ``streams``: batches in flight; ``workers``: decode processes
-        (default: this rank's share of the host cores); ``hip_graph``: replay recurring batch shapes as captured graphs."""
+        (default: this rank's share of the host cores); ``hip_graph``: replay recurring batch shapes as captured graphs;
+        ``decode``: "host" = Pillow in the decode worker processes; "device" = ``selfmask_amd.jpeg.decode_jpeg_batch`` - baseline
+        JPEGs entropy-decoded on at most 16 host THREADS (``workers`` caps them) and finished on the device, every other file by
+        Pillow on those threads: the same pixels, so the same results, without worker processes."""
+        if decode not in DECODES:
+            raise ValueError(f"decode={decode!r}: one of {DECODES}")
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError(f"SaliencyPredictor runs on a HIP device (got {device}); there is no CPU fallback")
@@ -52,6 +97,7 @@ class SaliencyPredictor:
                                f"fallback - call network.to(device)")
         self.network, self.device, self.batch_size = network, device, max(1, int(batch_size))
         self.streams, self.workers, self.hip_graph, self.cap = max(1, int(streams)), workers, bool(hip_graph), int(cap)
+        self.decode = decode
         self.last_best: Dict[str, int] = {}
         self._ring = None
 
@@ -80,7 +126,7 @@ class SaliencyPredictor:
             if not os.path.isfile(p):
                 raise FileNotFoundError(f"SaliencyPredictor: {p} does not exist; nothing was run")
             try:
-                hw = probe_size(p)
+                hw = _probe(p) if self.decode == "device" else probe_size(p)
             except Exception as e:
                 raise ValueError(f"SaliencyPredictor: {p} is not a readable image ({type(e).__name__}: {e}); nothing was run") from e
             if hw[0] < 1 or hw[1] < 1 or hw[0] * hw[1] > MAX_PIXELS:
@@ -198,13 +244,19 @@ class SaliencyPredictor:
         from .decode_pool import default_workers
         avg = max(1, len(p_images) // len(batches))  # buckets are often smaller than batch_size: keep every decode worker busy
         depth = max(len(ring.streams) + 1, -(-2 * (self.workers or default_workers()) // avg))
-        loader = PrefetchingLoader(_Files(p_images), range(len(p_images)), self.batch_size, workers=self.workers, depth=depth,
-                                   batches=batches, pack=True, pack_size=img_size)
+        if self.decode == "device":
+            loader = _DeviceDecoded(p_images, batches, self.workers, len(ring.streams) + 1)
+        else:
+            loader = PrefetchingLoader(_Files(p_images), range(len(p_images)), self.batch_size, workers=self.workers, depth=depth,
+                                       batches=batches, pack=True, pack_size=img_size)
         try:
             if pin_path is not None:
                 model.attention_path = pin_path
             for ((packed, shapes), _gts, idx) in loader:
                 with ring.next():
+                    if self.decode == "device":  # the batch's pixels are decoded on the device, on this batch's stream
+                        from .jpeg import packed_from_device
+                        packed = packed_from_device(packed.to_device(device), shapes, img_size)
                     if native:
                         Hp = -(-max(h for h, _ in shapes) // patch) * patch
                         Wp = -(-max(w for _, w in shapes) // patch) * patch
@@ -292,6 +344,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--batch_size", type=int, default=64)
     ap.add_argument("--refine", type=str, default=None, choices=["bilateral"])
     ap.add_argument("--png_dir", type=str, default=None, help="also write the soft maps as 8-bit PNGs into this directory")
+    ap.add_argument("--decode", type=str, default="host", choices=list(DECODES),
+                    help="device: baseline JPEGs are entropy-decoded on host threads and finished on the GPU (same pixels as Pillow)")
     ap.add_argument("--gpu_id", type=int, default=0)
     return ap
 
@@ -309,7 +363,7 @@ def main(argv=None):
     model = get_model("maskformer", configs=cfg)
     load_checkpoint(model, args.p_state_dict)
     model = model.to(device).eval()
-    pred = SaliencyPredictor(model, device=device, batch_size=args.batch_size)
+    pred = SaliencyPredictor(model, device=device, batch_size=args.batch_size, decode=args.decode)
     outputs = ("rle", "soft") if args.png_dir else ("rle",)
     res = pred._run(list_images(args.images), args.img_size, getattr(cfg, "scale_factor", 2), outputs, args.refine)
     with open(args.out, "w") as f:
