@@ -71,7 +71,14 @@ __device__ int g_gemm_stamp_filter[3];  // (N, K, M) of the launches that stamp;
 // piece.  Letting only the first half of the waves issue the pieces took 11 % off the fused QKV kernel's projection loop
 // (qkv_attention.hip, shipped there) but nothing off these GEMMs: K loop of the 256 x 128 fc2 tile 102.5k cycles against 97.4k,
 // pipeline 21.75k vs 21.75k images/s (profiles/r03_loader_half_ab.log) - four waves per SIMD already cover each other's issue time.
-template <int BM, int BN, int NST, int NWM, int NWN, int WPS, int TERMS = 3>
+//
+// Epilogue selection.  EPI_T >= 0: the epilogue (SM_EPI_*) and the output format (F16OUT: F16X2 instead of fp32) are fixed at
+// compile time; EPI_T < 0: chosen at run time from g.epilogue / g.patch_n < 0, every epilogue in one kernel.  PLAIN: the launch
+// uses none of ln_stats, C2, ln_stats_out, A_alt and split-K, and the kernel carries no code, registers or LDS for them.  The host
+// instantiates <EPI_T, F16OUT, PLAIN = true> for the (tile, epilogue, format) combinations the forward launches and ONE generic
+// <-1, false, false> kernel per tile for everything else (launch_gemm_m16): a specialisation's register allocation and the code
+// behind its K loop are those of the one epilogue it runs.  Same arithmetic per element in both: results are bit-identical.
+template <int BM, int BN, int NST, int NWM, int NWN, int WPS, int TERMS = 3, int EPI_T = -1, bool F16OUT = false, bool PLAIN = false>
 __global__ __launch_bounds__(NWM * NWN * 64, WPS) void gemm_w16m16_kernel(sm_gemm_args g) {
     constexpr int NW = NWM * NWN, WTM = BM / NWM, WTN = BN / NWN;
     constexpr int TM = WTM / 16, TN = WTN / 16;       // 16x16 tiles per wave
@@ -95,10 +102,10 @@ __global__ __launch_bounds__(NWM * NWN * 64, WPS) void gemm_w16m16_kernel(sm_gem
     }
     const int n0 = (tile_id % ntn) * BN, m0 = (tile_id / ntn) * BM;
     const int M = g.M, N = g.N;
-    const int split = g.split_k > 1 ? g.split_k : 1;
+    const int split = (!PLAIN && g.split_k > 1) ? g.split_k : 1;
     const int nk = g.K / 32 / split;
     const int k_begin = split > 1 ? (int)blockIdx.z * nk * 32 : 0;
-    const char* A = reinterpret_cast<const char*>(((g.alt_from_n > 0 && n0 >= g.alt_from_n) ? g.A_alt : g.A) + k_begin);
+    const char* A = reinterpret_cast<const char*>(((!PLAIN && g.alt_from_n > 0 && n0 >= g.alt_from_n) ? g.A_alt : g.A) + k_begin);
     const char* W = reinterpret_cast<const char*>(g.W + k_begin);
     // DMA: lane -> (row = lane >> 3 of its 8-row piece, slot p = lane & 7); the slot holds chunk (2 kg + x) with
     // kg = ((p >> 1) + 2 * ((row >> 3) & 1)) & 3 (the pair rotation is its own inverse), x = (p & 1) ^ ((row >> 1) & 1)
@@ -152,9 +159,9 @@ __global__ __launch_bounds__(NWM * NWN * 64, WPS) void gemm_w16m16_kernel(sm_gem
     // LayerNorm folded into this GEMM (g.ln_stats): A holds the RAW residual stream x (F16X2), W the weight times the norm's gain,
     // and LN(x) W^T + b = r (x W'^T - mu c) + b' with c = row sums of W', b' = b + W beta - applied in the epilogue.  Here, under
     // the latency of the first K-tile: (mu r, r) of this tile's rows from the twelve 32-column partials (mean, M2) the producing
-    // residual GEMM left per row, merged in segment order, into LDS behind the ring.
+    // residual GEMM left per row, merged in segment order, into LDS behind the ring (a PLAIN launch has no such tail).
     float2* lnrow = reinterpret_cast<float2*>(smemm + RING_BYTES);
-    if (g.ln_stats && tid < BM) {
+    if (!PLAIN && g.ln_stats && tid < BM) {
         int m = m0 + tid;
         m = m < M ? m : M - 1;
         const float4* sp = reinterpret_cast<const float4*>(g.ln_stats + (int64_t)m * 24);
@@ -238,29 +245,35 @@ __global__ __launch_bounds__(NWM * NWN * 64, WPS) void gemm_w16m16_kernel(sm_gem
     __builtin_amdgcn_s_barrier();
     char* ep = smemm + wave * (32 * EPLD);
 
-    auto run = [&](auto epi_tag, auto fmt_tag) {
+    auto run = [&](auto epi_tag, auto fmt_tag, auto full_tag) {
         constexpr int EPI = decltype(epi_tag)::value;
         constexpr bool F = decltype(fmt_tag)::value;
+        constexpr bool FULL = decltype(full_tag)::value;  // the whole tile lies inside C: no row / column guard on any load or store
         // The rows added in the epilogue (residual stream / position table) are fetched a 32-row block ahead, all of a
         // block's loads before any of its stores: C may alias R (in-place residual), so left in one loop every load would
         // wait behind the previous store: 16-24 exposed memory latencies per tile (scripts/gemm_stamps.py).
         constexpr int NIT = 32 * PIECES / 64;
         constexpr bool HASR = EPI == SM_EPI_RESIDUAL || EPI == SM_EPI_PATCH;
-        constexpr bool AHEAD = WPS <= 2 && NIT <= 8 && TM * TN <= 16;  // a second block of rows in registers only where there is room
-        float4 res[HASR ? NIT : 1];
+        // A PLAIN two-block tile (256 x 128: proj, fc2, patch) fetches the rows of BOTH blocks here, ahead of everything else: without
+        // the other epilogues' registers in the allocation 2 x NIT float4 fit, and block 1 no longer waits a memory latency for its
+        // rows behind block 0's stores.  Every load of the tile still precedes every store.
+        constexpr bool ALLRES = HASR && PLAIN && TM / 2 == 2 && NIT <= 4;
+        float4 res_[ALLRES ? 2 : 1][HASR ? NIT : 1];
         auto load_res = [&](int ib) {
+            float4* res = res_[ALLRES ? ib : 0];
 #pragma unroll
             for (int it = 0; it < NIT; ++it) {
                 const int idx = it * 64 + lane, row = idx / PIECES, pc = idx % PIECES;
                 const int m = m0 + wm * WTM + ib * 32 + row, n = n0 + wn * WTN + pc * 4;
                 res[it] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (m < M && n < N) {
+                if (FULL || (m < M && n < N)) {
                     if constexpr (EPI == SM_EPI_RESIDUAL) res[it] = *reinterpret_cast<const float4*>(g.R + (int64_t)m * g.ldr + n);
                     else if constexpr (EPI == SM_EPI_PATCH) res[it] = *reinterpret_cast<const float4*>(g.R + (int64_t)(1 + m % g.patch_n) * g.ldr + n);
                 }
             }
         };
         if constexpr (HASR) load_res(0);
+        if constexpr (ALLRES) load_res(1);
         // this lane's bias values (columns 16 j + 4 kg .. + 3 of the wave's slice), fetched ONCE and all together: read per
         // element inside the loops below they were TM x TN x 4 guarded scalar loads, each waited for in its own branch
         float brow[TN][4];
@@ -270,7 +283,7 @@ __global__ __launch_bounds__(NWM * NWN * 64, WPS) void gemm_w16m16_kernel(sm_gem
             for (int j = 0; j < TN; ++j) {
                 const int n = n0 + wn * WTN + j * 16 + 4 * kg;
                 float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (vec && n + 3 < N) {
+                if (vec && (FULL || n + 3 < N)) {
                     bv = *reinterpret_cast<const float4*>(g.bias + n);
                 } else if (g.bias) {
                     if (n < N) bv.x = g.bias[n];
@@ -282,7 +295,7 @@ __global__ __launch_bounds__(NWM * NWN * 64, WPS) void gemm_w16m16_kernel(sm_gem
             }
         }
         // folded LayerNorm (consumer side): c[n] = sum_k W'[n][k] of this lane's columns (N % 4 == 0, c 16-B aligned: host-checked)
-        constexpr bool CANFOLD = !HASR;
+        constexpr bool CANFOLD = !HASR && !PLAIN;
         const bool fold = CANFOLD && g.ln_stats != nullptr;
         float crow[CANFOLD ? TN : 1][4];
         if constexpr (CANFOLD) {
@@ -294,8 +307,12 @@ __global__ __launch_bounds__(NWM * NWN * 64, WPS) void gemm_w16m16_kernel(sm_gem
                 crow[j][0] = cv.x; crow[j][1] = cv.y; crow[j][2] = cv.z; crow[j][3] = cv.w;
             }
         }
-#pragma unroll
-        for (int ib = 0; ib < TM / 2; ++ib) {  // 32 staged rows = two 16-row tiles
+        // One 32-row block (two 16-row tiles) at a time goes through the staging area.  fill(ib, phase): phase 0 = the block's values
+        // computed and written to the LDS piece by piece; 1 = register maths only (kept in the output format); 2 = those registers written
+        float tq[F ? 1 : 2][F ? 1 : TN][4];
+        f16x4 thi[F ? 2 : 1][F ? TN : 1], tlo[F ? 2 : 1][F ? TN : 1];
+        auto fill = [&](int ib, auto phase_tag) {
+            constexpr int PH = decltype(phase_tag)::value;
 #pragma unroll
             for (int ii = 0; ii < 2; ++ii) {
                 const int i = 2 * ib + ii, row = ii * 16 + r16;
@@ -309,57 +326,98 @@ __global__ __launch_bounds__(NWM * NWN * 64, WPS) void gemm_w16m16_kernel(sm_gem
                 }
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
-                    const int nl = j * 16 + 4 * kg, n = n0 + wn * WTN + nl;  // this lane: columns nl .. nl+3 of its row
+                    const int nl = j * 16 + 4 * kg;  // this lane: columns nl .. nl+3 of its row
                     float t[4];
+                    f16x4 hi, lo;
+                    if constexpr (PH != 2) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        if constexpr (CANFOLD) {  // (wave-uniform branch: the plain path keeps its one fma per element)
-                            if (fold) t[e] = acc[i][j][e] * rs + (brow[j][e] - mur * crow[j][e]);
-                            else t[e] = acc[i][j][e] * ws + brow[j][e];
-                        } else {
-                            t[e] = acc[i][j][e] * ws + brow[j][e];
+                        for (int e = 0; e < 4; ++e) {
+                            if constexpr (CANFOLD) {  // (wave-uniform branch: the plain path keeps its one fma per element)
+                                if (fold) t[e] = acc[i][j][e] * rs + (brow[j][e] - mur * crow[j][e]);
+                                else t[e] = acc[i][j][e] * ws + brow[j][e];
+                            } else {
+                                t[e] = acc[i][j][e] * ws + brow[j][e];
+                            }
+                            if constexpr (EPI == SM_EPI_RELU) t[e] = fmaxf(t[e], 0.f);
                         }
-                        if constexpr (EPI == SM_EPI_RELU) t[e] = fmaxf(t[e], 0.f);
-                    }
-                    if constexpr (EPI == SM_EPI_GELU) gelu4(t);
-                    if constexpr (F) {  // F16X2: elements nl..nl+3 of group nl / 8: hi at 32 G + 8 (kg & 1), lo 16 B further
-                        f16x4 hi, lo;
-                        split4(t, hi, lo);
-                        if constexpr (SWZ) {
-                            const int pc = 2 * (nl >> 3), half = ((kg & 1) ^ ((row >> 3) & 1)) * 8;
-                            char* p = ep + row * EPLD + half;
-                            *reinterpret_cast<f16x4*>(p + ((pc ^ (row & 7)) * 16)) = hi;
-                            *reinterpret_cast<f16x4*>(p + (((pc + 1) ^ (row & 7)) * 16)) = lo;
-                        } else {
-                            char* p = ep + row * EPLD + (nl >> 3) * 32 + (kg & 1) * 8;
-                            *reinterpret_cast<f16x4*>(p) = hi;
-                            *reinterpret_cast<f16x4*>(p + 16) = lo;
+                        if constexpr (EPI == SM_EPI_GELU) gelu4(t);
+                        if constexpr (F) split4(t, hi, lo);
+                        if constexpr (PH == 1) {
+                            if constexpr (F) {
+                                thi[ii][j] = hi; tlo[ii][j] = lo;
+                            } else {
+#pragma unroll
+                                for (int e = 0; e < 4; ++e) tq[ii][j][e] = t[e];
+                            }
                         }
                     } else {
-                        const int pc = SWZ ? ((nl >> 2) ^ (row & 7)) : (nl >> 2);
-                        *reinterpret_cast<float4*>(ep + row * EPLD + pc * 16) = make_float4(t[0], t[1], t[2], t[3]);
+                        if constexpr (F) {
+                            hi = thi[ii][j]; lo = tlo[ii][j];
+                        } else {
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) t[e] = tq[ii][j][e];
+                        }
+                    }
+                    if constexpr (PH != 1) {
+                        if constexpr (F) {  // F16X2: elements nl..nl+3 of group nl / 8: hi at 32 G + 8 (kg & 1), lo 16 B further
+                            if constexpr (SWZ) {
+                                const int pc = 2 * (nl >> 3), half = ((kg & 1) ^ ((row >> 3) & 1)) * 8;
+                                char* p = ep + row * EPLD + half;
+                                *reinterpret_cast<f16x4*>(p + ((pc ^ (row & 7)) * 16)) = hi;
+                                *reinterpret_cast<f16x4*>(p + (((pc + 1) ^ (row & 7)) * 16)) = lo;
+                            } else {
+                                char* p = ep + row * EPLD + (nl >> 3) * 32 + (kg & 1) * 8;
+                                *reinterpret_cast<f16x4*>(p) = hi;
+                                *reinterpret_cast<f16x4*>(p + 16) = lo;
+                            }
+                        } else {
+                            const int pc = SWZ ? ((nl >> 2) ^ (row & 7)) : (nl >> 2);
+                            *reinterpret_cast<float4*>(ep + row * EPLD + pc * 16) = make_float4(t[0], t[1], t[2], t[3]);
+                        }
                     }
                 }
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        };
+        using Ph0 = std::integral_constant<int, 0>;
+        using Ph1 = std::integral_constant<int, 1>;
+        using Ph2 = std::integral_constant<int, 2>;
+        // PIPE (the PLAIN kernels): the next block's maths runs right behind this block's LDS writes, before the wave waits for
+        // anything, and a block's pieces are ALL read back before the first is stored (read and stored one by one, each read was
+        // waited for inside its store's guard: four exposed LDS latencies per block).  The staging area is this wave's own and the LDS
+        // executes a wave's instructions in order, so between the writes, the reads and the next block's writes the compiler only has
+        // to keep the program order (the empty asm); the one wait left per block is the one the stores' operands need.  Maths BETWEEN
+        // the reads and the stores (four more float4 live) spilled in the 256 x 256 GELU kernel, and a second staging buffer - block
+        // ib + 1 written before block ib is read - changed nothing: fc1 epilogue 12.15 k cycles against 12.12 k, and one spilled
+        // register in its K loop (profiles/gemm_w16_epilogues.log).  The generic kernel keeps both full drains and its order.
+        constexpr bool PIPE = PLAIN;
+        if constexpr (PIPE) fill(0, Ph1{});
+#pragma unroll
+        for (int ib = 0; ib < TM / 2; ++ib) {
+            if constexpr (PIPE) {
+                fill(ib, Ph2{});
+                asm volatile("" ::: "memory");
+            } else {
+                fill(ib, Ph0{});
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            }
             auto store_piece = [&](int it, const float4& val) {
                 const int idx = it * 64 + lane, row = idx / PIECES, pc = idx % PIECES;
                 int m = m0 + wm * WTM + ib * 32 + row;
                 const int n = n0 + wn * WTN + pc * 4;
-                if (m < M && n < N) {
+                if (FULL || (m < M && n < N)) {
                     if constexpr (EPI == SM_EPI_PATCH) {
                         const int img = m / g.patch_n, p = m - img * g.patch_n;
                         m = img * (g.patch_n + 1) + 1 + p;
                     }
                     *reinterpret_cast<float4*>(C + (int64_t)m * g.ldc + n) = val;
-                    if constexpr (EPI == SM_EPI_RESIDUAL) {
+                    if constexpr (EPI == SM_EPI_RESIDUAL && !PLAIN) {
                         if (g.C2) {  // the F16X2 copy of the new residual stream: A operand of the GEMM the next LayerNorm is folded into
                             const float vv[4] = {val.x, val.y, val.z, val.w};
                             store_f16x2_4(g.C2 + (int64_t)m * g.ldc, n, vv);
                         }
                     }
                 }
-                if constexpr (EPI == SM_EPI_RESIDUAL && WTN == 32) {
+                if constexpr (EPI == SM_EPI_RESIDUAL && WTN == 32 && !PLAIN) {
                     // ... and that norm's row statistics over this wave's 32 columns: (mean, M2) by two 8-lane butterflies (the
                     // eight lanes pc = 0..7 of a row are consecutive), two-pass, written to slot (row, column segment): fixed
                     // order everywhere, no atomics.  Rows past M join the shuffles (their staging rows hold finite values).
@@ -375,6 +433,7 @@ __global__ __launch_bounds__(NWM * NWN * 64, WPS) void gemm_w16m16_kernel(sm_gem
                     }
                 }
             };
+            const float4* res = res_[ALLRES ? ib : 0];
             auto staged = [&](int it) {
                 const int idx = it * 64 + lane, row = idx / PIECES, pc = idx % PIECES;
                 float4 val = *reinterpret_cast<const float4*>(ep + row * EPLD + (SWZ ? (pc ^ (row & 7)) : pc) * 16);
@@ -384,31 +443,42 @@ __global__ __launch_bounds__(NWM * NWN * 64, WPS) void gemm_w16m16_kernel(sm_gem
                 if constexpr (HASR) { val.x = res[it].x + val.x; val.y = res[it].y + val.y; val.z = res[it].z + val.z; val.w = res[it].w + val.w; }
                 return val;
             };
-            if constexpr (HASR && AHEAD) {  // registers to spare: the next block's rows fly under this block's stores
+            if constexpr (PIPE) {
+                if (ib + 1 < TM / 2) fill(ib + 1, Ph1{});
+                __builtin_amdgcn_sched_barrier(0);  // (left alone the scheduler pulls later blocks' maths up as well, and spills)
                 float4 v[NIT];
 #pragma unroll
                 for (int it = 0; it < NIT; ++it) v[it] = staged(it);
-                if (ib + 1 < TM / 2) load_res(ib + 1);
+                if constexpr (HASR && !ALLRES) {  // the next block's rows fly under this block's stores
+                    if (ib + 1 < TM / 2) load_res(ib + 1);
+                }
 #pragma unroll
                 for (int it = 0; it < NIT; ++it) store_piece(it, v[it]);
+                asm volatile("" ::: "memory");
+                __builtin_amdgcn_sched_barrier(0);
             } else {
 #pragma unroll
                 for (int it = 0; it < NIT; ++it) store_piece(it, staged(it));
-                if constexpr (HASR) {
+                if constexpr (HASR && !ALLRES) {
                     if (ib + 1 < TM / 2) load_res(ib + 1);
                 }
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         }
     };
     using T = std::true_type;
     using Fa = std::false_type;
-    switch (g.epilogue) {
-        case SM_EPI_GELU: out_split ? run(std::integral_constant<int, SM_EPI_GELU>{}, T{}) : run(std::integral_constant<int, SM_EPI_GELU>{}, Fa{}); break;
-        case SM_EPI_RELU: out_split ? run(std::integral_constant<int, SM_EPI_RELU>{}, T{}) : run(std::integral_constant<int, SM_EPI_RELU>{}, Fa{}); break;
-        case SM_EPI_RESIDUAL: run(std::integral_constant<int, SM_EPI_RESIDUAL>{}, Fa{}); break;
-        case SM_EPI_PATCH: run(std::integral_constant<int, SM_EPI_PATCH>{}, Fa{}); break;
-        default: out_split ? run(std::integral_constant<int, SM_EPI_BIAS>{}, T{}) : run(std::integral_constant<int, SM_EPI_BIAS>{}, Fa{}); break;
+    if constexpr (EPI_T >= 0) {
+        // interior tiles (all but the last row / column of tiles) take a copy of the epilogue without the per-piece guards
+        const bool full = PLAIN && m0 + BM <= M && n0 + BN <= N;
+        if (full) run(std::integral_constant<int, EPI_T>{}, std::integral_constant<bool, F16OUT>{}, T{});
+        else run(std::integral_constant<int, EPI_T>{}, std::integral_constant<bool, F16OUT>{}, Fa{});
+    } else switch (g.epilogue) {
+        case SM_EPI_GELU: out_split ? run(std::integral_constant<int, SM_EPI_GELU>{}, T{}, Fa{}) : run(std::integral_constant<int, SM_EPI_GELU>{}, Fa{}, Fa{}); break;
+        case SM_EPI_RELU: out_split ? run(std::integral_constant<int, SM_EPI_RELU>{}, T{}, Fa{}) : run(std::integral_constant<int, SM_EPI_RELU>{}, Fa{}, Fa{}); break;
+        case SM_EPI_RESIDUAL: run(std::integral_constant<int, SM_EPI_RESIDUAL>{}, Fa{}, Fa{}); break;
+        case SM_EPI_PATCH: run(std::integral_constant<int, SM_EPI_PATCH>{}, Fa{}, Fa{}); break;
+        default: out_split ? run(std::integral_constant<int, SM_EPI_BIAS>{}, T{}, Fa{}) : run(std::integral_constant<int, SM_EPI_BIAS>{}, Fa{}, Fa{}); break;
     }
 #ifdef SM_TUNING
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the stamp sees the stores retired (tuning build only)
@@ -417,24 +487,41 @@ __global__ __launch_bounds__(NWM * NWN * 64, WPS) void gemm_w16m16_kernel(sm_gem
 #endif
 }
 
-template <int BM, int BN, int NST, int NWM, int NWN, int WPS, int TERMS = 3>
+template <int BM, int BN, int NST, int NWM, int NWN, int WPS, int TERMS = 3, int EPI_T = -1, bool F16OUT = false, bool PLAIN = false>
 static int launch_gemm_m16_terms(const sm_gemm_args& g, hipStream_t st) {
-    dim3 grid(((g.N + BN - 1) / BN) * ((g.M + BM - 1) / BM), 1, g.split_k > 1 ? g.split_k : 1);
-    constexpr size_t lds = (size_t)NST * (BM + BN) * 128 + (size_t)BM * 8;  // ring + (mu r, r) of the tile's rows (folded LayerNorm)
+    dim3 grid(((g.N + BN - 1) / BN) * ((g.M + BM - 1) / BM), 1, (!PLAIN && g.split_k > 1) ? g.split_k : 1);
+    // ring + (generic kernel) (mu r, r) of the tile's rows (folded LayerNorm)
+    constexpr size_t lds = (size_t)NST * (BM + BN) * 128 + (PLAIN ? 0 : (size_t)BM * 8);
     if (lds > 64 * 1024) {
         static std::once_flag attr_once;
         std::call_once(attr_once, [] {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_w16m16_kernel<BM, BN, NST, NWM, NWN, WPS, TERMS>),
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_w16m16_kernel<BM, BN, NST, NWM, NWN, WPS, TERMS, EPI_T, F16OUT, PLAIN>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             (void)hipGetLastError();
         });
     }
-    hipLaunchKernelGGL((gemm_w16m16_kernel<BM, BN, NST, NWM, NWN, WPS, TERMS>), grid, dim3(NWM * NWN * 64), lds, st, g);
+    hipLaunchKernelGGL((gemm_w16m16_kernel<BM, BN, NST, NWM, NWN, WPS, TERMS, EPI_T, F16OUT, PLAIN>), grid, dim3(NWM * NWN * 64), lds, st, g);
     return check_launch("sm_gemm_w16 (16x16x32)");
 }
-template <int BM, int BN, int NST, int NWM, int NWN, int WPS>
-static int launch_gemm_m16(const sm_gemm_args& g, hipStream_t st) {
+// One (epilogue, output format) a tile has a PLAIN specialisation for.  The lists in sm_gemm_w16_tile name what the forward
+// (forward.hip, W16 mode) launches on that tile; anything else - another epilogue, the LayerNorm fold on either side, the second A
+// operand, split-K, throughput mode - runs the tile's generic kernel.
+template <int E, bool F>
+struct EpiSpec {
+    static constexpr int epi = E;
+    static constexpr bool f16 = F;
+};
+template <int BM, int BN, int NST, int NWM, int NWN, int WPS, class... Specs>
+static int launch_gemm_m16(const sm_gemm_args& g, bool f16, hipStream_t st) {
     if (g.mfma_terms == 1) return launch_gemm_m16_terms<BM, BN, NST, NWM, NWN, WPS, 1>(g, st);
+    const bool plain = !g.ln_stats && !g.C2 && !g.ln_stats_out && !(g.alt_from_n > 0) && !(g.split_k > 1);
+    if (plain) {
+        int rc = SM_OK;
+        const bool done = (... || (Specs::epi == g.epilogue && Specs::f16 == f16
+                                       ? (rc = launch_gemm_m16_terms<BM, BN, NST, NWM, NWN, WPS, 3, Specs::epi, Specs::f16, true>(g, st), true)
+                                       : false));
+        if (done) return rc;
+    }
     return launch_gemm_m16_terms<BM, BN, NST, NWM, NWN, WPS, 3>(g, st);
 }
 
@@ -520,13 +607,21 @@ extern "C" int sm_gemm_w16_tile(const sm_gemm_args* g, int out_f16x2, int varian
     sm_gemm_args a = *g;
     if (out_f16x2) a.patch_n = -1;
     hipStream_t st = (hipStream_t)stream;
+    const bool f = out_f16x2 != 0;
+    using sm::EpiSpec;
+    using GeluS = EpiSpec<SM_EPI_GELU, true>;          // fc1
+    using BiasS = EpiSpec<SM_EPI_BIAS, true>;          // all-layer K/V, qkv, decoder projections, the head's last layer
+    using ReluS = EpiSpec<SM_EPI_RELU, true>;          // decoder linear1, the head
+    using Relu = EpiSpec<SM_EPI_RELU, false>;          // the head's middle layer when its output leaves as fp32
+    using Resid = EpiSpec<SM_EPI_RESIDUAL, false>;     // proj, fc2, decoder output projections, linear2
+    using Patch = EpiSpec<SM_EPI_PATCH, false>;        // patch embedding
     switch (variant) {
-        case 40: return sm::launch_gemm_m16<256, 256, 2, 2, 8, 4>(a, st);   // 16 waves of 128x32 (fc1, all-layer K/V)
-        case 42: return sm::launch_gemm_m16<128, 128, 2, 2, 4, 4>(a, st);   // 8 waves of 64x32
-        case 43: return sm::launch_gemm_m16<256, 192, 2, 4, 4, 4>(a, st);   // 16 waves of 64x48: N = 1536 / 4608 in 400 / 1200 tiles
-        case 44: return sm::launch_gemm_m16<64, 64, 3, 2, 2, 3>(a, st);     // 4 waves of 32x32 (decoder, batch 1)
-        case 45: return sm::launch_gemm_m16<128, 64, 2, 2, 2, 3>(a, st);    // 4 waves of 64x32
-        case 47: return sm::launch_gemm_m16<256, 128, 3, 4, 4, 4>(a, st);   // 16 waves of 64x32, ring of three (proj, fc2, qkv, patch)
+        case 40: return sm::launch_gemm_m16<256, 256, 2, 2, 8, 4, GeluS, BiasS>(a, f, st);   // 16 waves of 128x32 (fc1, all-layer K/V)
+        case 42: return sm::launch_gemm_m16<128, 128, 2, 2, 4, 4>(a, f, st);   // 8 waves of 64x32
+        case 43: return sm::launch_gemm_m16<256, 192, 2, 4, 4, 4>(a, f, st);   // 16 waves of 64x48: N = 1536 / 4608 in 400 / 1200 tiles
+        case 44: return sm::launch_gemm_m16<64, 64, 3, 2, 2, 3, BiasS, ReluS, Relu, Resid>(a, f, st);  // 4 waves of 32x32 (decoder, batch 1)
+        case 45: return sm::launch_gemm_m16<128, 64, 2, 2, 2, 3>(a, f, st);    // 4 waves of 64x32
+        case 47: return sm::launch_gemm_m16<256, 128, 3, 4, 4, 4, Resid, Patch, BiasS, GeluS>(a, f, st);  // 16 waves of 64x32, ring of three (proj, fc2, qkv, patch)
     }
     sm::set_error("sm_gemm_w16_tile: unknown variant %d", variant);
     return SM_EINVAL;
