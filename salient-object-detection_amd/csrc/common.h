@@ -263,8 +263,9 @@ __device__ __forceinline__ int m16_chunk_of_slot(int row, int p) { return p ^ m1
 // row of a 32x32 MFMA accumulator held in register v by lane-half h  (cdna_hip_programming.md section 3)
 __device__ __forceinline__ int acc_row(int v, int h) { return (v & 3) + 8 * (v >> 2) + 4 * h; }
 
-// timing taps of sm_forward_timing (forward.hip) for the library's other launch sequences: an event pair on `stream` around what runs
-// between tap_begin and tap_end while timing is on (handle -1 otherwise); read back, summed by name, with sm_forward_timing_read
+// timing taps of sm_forward_timing (defined in forward.hip) for every launch sequence of the library: an event pair on `stream` around
+// what runs between tap_begin and tap_end while timing is on (handle -1 otherwise: nothing is created or recorded); read back, summed
+// by name, with sm_forward_timing_read.  Single caller: the taps are one unguarded list (selfmask_hip.h).
 int tap_begin(void* stream, const char* name, double flops, double bytes);
 void tap_end(int handle);
 struct TapGuard {

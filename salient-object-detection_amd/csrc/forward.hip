@@ -2,21 +2,27 @@
 // stream-ordered sequence of the kernels of this library.  No allocation, no synchronisation: the caller owns the
 // workspace and the stream, so the whole forward can be captured into a hipGraph.
 //
-// Two GEMM back ends behind sm_weights.gemm_mode:
+// Four GEMM back ends behind sm_weights.gemm_mode:
 //   0  exact-fp32 MFMA (gemm.hip): every buffer fp32;
 //   1  split-operand f16 MFMA (gemm_f16x2.hip, fp32-grade, ~2.2x faster): every tensor that only feeds a GEMM is
 //      produced directly in the F16X2 format by its producer (LayerNorm, attention, GELU/ReLU epilogues, im2col,
 //      up-sample); tensors that are also residuals / outputs exist in fp32 as well.  "(S)" marks them below.
+//   2  W16 (gemm_w16.hip, the default): activations as in mode 1, the weights in the W16 format with a per-tensor 2^-s, so every
+//      weight GEMM sums in one fp32 accumulator; products of two activations (the mask einsum) stay on the mode-1 kernel.  Only
+//      this mode and mode 3 have the fused QKV + attention kernel, the folded pre-norms and the encoder's split-K fc2;
+//   3  the W16 kernels with ONE f16 MFMA per product instead of three (sm_gemm_args.mfma_terms = 1): the throughput-mode
+//      diagnostic, two orders of magnitude outside the 1e-4 logit gate - never the metric, and without attention maps.
 #include "common.h"
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace sm {
 
-// ---- timing taps (sm_forward_timing): event pairs around the heavy launches, on the forward's stream -----------------
+// ---- timing taps (sm_forward_timing): event pairs around the heavy launches, on the launch sequence's stream ----------
 struct Tap {
     hipStream_t st;
     hipEvent_t e0, e1;
@@ -26,23 +32,7 @@ struct Tap {
 static bool g_timing = false;
 static std::vector<Tap> g_taps;
 
-struct TapScope {
-    hipStream_t st;
-    bool on;
-    TapScope(hipStream_t st_, const std::string& name, double flops, double bytes) : st(st_), on(g_timing) {
-        if (!on) return;
-        Tap t;
-        t.st = st; t.name = name; t.flops = flops; t.bytes = bytes;
-        if (hipEventCreate(&t.e0) != hipSuccess || hipEventCreate(&t.e1) != hipSuccess) { on = false; return; }
-        (void)hipEventRecord(t.e0, st);
-        g_taps.push_back(t);
-    }
-    ~TapScope() {
-        if (on) (void)hipEventRecord(g_taps.back().e1, st);
-    }
-};
-
-// the same taps for the other launch sequences of the library (spectral.hip, bilateral.hip): begin returns a handle (-1 when timing is off)
+// begin returns a handle (-1 when timing is off: nothing is created or recorded then); TapGuard (common.h) pairs the two
 int tap_begin(void* stream, const char* name, double flops, double bytes) {
     if (!g_timing) return -1;
     Tap t;
@@ -62,7 +52,7 @@ void tap_end(int handle) {
 static const int64_t SM_SPLIT_FC2_ROWS = 512;
 
 struct Shape {
-    int B, H, W, P, gh, gw, n, N, L, nq, sf;  // sf: the pixel decoder's scale_factor (2 as shipped)
+    int B, H, W, P, gh, gw, n, N, L, nq, sf, KVW;  // sf: the pixel decoder's scale_factor (2 as shipped); KVW: row width of ws.KV
     int64_t M, Mp, Md, Mo;  // tokens, patch tokens, decoder rows, objectness rows
 };
 
@@ -72,6 +62,7 @@ static Shape make_shape(const sm_weights* w, int B, int H, int W) {
     s.gh = (H + s.P - 1) / s.P; s.gw = (W + s.P - 1) / s.P;
     s.n = s.gh * s.gw; s.N = s.n + 1; s.L = w->n_dec_layers; s.nq = w->n_queries;
     s.sf = w->scale_factor > 0 ? w->scale_factor : 2;
+    s.KVW = s.L * 2 * SM_EMBED;
     s.M = (int64_t)B * s.N; s.Mp = (int64_t)B * s.n; s.Md = (int64_t)B * s.nq; s.Mo = s.Md * s.L;
     return s;
 }
@@ -124,7 +115,7 @@ static Ws carve(const Shape& s, float* base) {
     return w;
 }
 
-#define TRY_(x)               \
+#define TRY(x)                \
     do {                      \
         int _rc = (x);        \
         if (_rc) return _rc;  \
@@ -137,24 +128,16 @@ struct Ctx {
     int terms;  // MFMAs per product in the W16 kernels: 3 (fp32-grade) or 1 (gemm_mode 3: the throughput-mode diagnostic)
 };
 
-// `ws` = the weight tensor's 2^-s (W16 mode; 0 = W is not a W16 weight: an activation operand, or another mode)
-static int gemm(const Ctx& c, const sm_gemm_args& g, bool out_s = false);
-// C = epilogue(A W^T + b); in split mode A and W are F16X2 / W16 and `out_s` asks for an F16X2 C
-struct Fold {  // LayerNorm folded into the GEMMs around it (sm_gemm_args.ln_stats / ln_stats_out)
-    const float* stats = nullptr;  // consumer: the producer's row statistics ...
-    const float* cvec = nullptr;   // ... and the row sums of the gain-scaled weight
-    float eps = 0.f;
-    float* xs = nullptr;           // producer (RESIDUAL): F16X2 copy of the new residual stream ...
-    float* stats_out = nullptr;    // ... and its row statistics
-};
-static int linear(const Ctx& c, const float* A, int lda, const float* W, float ws, const float* b, float* C, int ldc, int64_t M,
-                  int N, int K, int epi, const float* R, int ldr, bool out_s = false, const Fold& f = Fold()) {
+// ---- launchers: the tap and the mode dispatch; their arguments are the ABI structs themselves -------------------------
+// C = epilogue(A W^T + b).  `ws` = the weight tensor's 2^-s (W16 mode; 0 = W is not a W16 weight: an activation operand, or another
+// mode).  Call sites set the optional fields (the LayerNorm fold, A_alt, split_k) under their sm_gemm_args names.
+static sm_gemm_args linear_args(const float* A, int lda, const float* W, float ws, const float* b, float* C, int ldc, int64_t M,
+                                int N, int K, int epi, const float* R = nullptr, int ldr = 0) {
     sm_gemm_args g = {};
     g.A = A; g.W = W; g.bias = b; g.C = C; g.R = R;
     g.M = (int)M; g.N = N; g.K = K; g.lda = lda; g.ldw = K; g.ldc = ldc; g.ldr = ldr;
     g.batch = 1; g.epilogue = epi; g.w_scale = ws;
-    g.ln_stats = f.stats; g.ln_c = f.cvec; g.ln_eps = f.eps; g.C2 = f.xs; g.ln_stats_out = f.stats_out;
-    return gemm(c, g, out_s);
+    return g;
 }
 static bool use_w16(const Ctx& c, const sm_gemm_args& g) { return c.W16 && g.w_scale > 0.f; }
 static bool pow2(float s) {
@@ -180,8 +163,9 @@ static std::string gemm_name(const Ctx& c, const sm_gemm_args& g) {
     }
     return buf;
 }
-static int gemm(const Ctx& c, const sm_gemm_args& g, bool out_s) {
-    TapScope tap(c.st, gemm_name(c, g), 2.0 * g.M * g.N * g.K * (g.batch > 0 ? g.batch : 1), 0.0);
+// in split mode A and W are F16X2 / W16 and `out_s` asks for an F16X2 C
+static int gemm(const Ctx& c, const sm_gemm_args& g, bool out_s = false) {
+    TapGuard tap(c.st, gemm_name(c, g).c_str(), 2.0 * g.M * g.N * g.K * (g.batch > 0 ? g.batch : 1), 0.0);
     if (use_w16(c, g)) {
         sm_gemm_args gt = g;
         gt.mfma_terms = c.terms;
@@ -190,71 +174,47 @@ static int gemm(const Ctx& c, const sm_gemm_args& g, bool out_s) {
     return c.S ? sm_gemm_f16x2(&g, out_s ? 1 : 0, c.st) : sm_gemm_f32(&g, c.st);
 }
 // in split mode Q, K and V are F16X2 (written so by the projection GEMMs) and the f16 matrix cores do the work
-static int attn(const Ctx& c, sm_attn_args& a) {
-    TapScope tap(c.st, c.S ? "attention_f16x2_kernel<4, false>" : "attention_f32_kernel", 4.0 * a.batch * a.heads * a.n_q * (double)a.n_k * SM_HEAD_DIM,
+static int attn(const Ctx& c, sm_attn_args a) {
+    TapGuard tap(c.st, c.S ? "attention_f16x2_kernel<4, false>" : "attention_f32_kernel", 4.0 * a.batch * a.heads * a.n_q * (double)a.n_k * SM_HEAD_DIM,
                  8.0 * a.batch * a.heads * SM_HEAD_DIM * ((double)a.n_q + a.n_k));  // Q, O and K, V once, 4 B per element
     a.out_f16x2 = c.S;
     return c.S ? sm_attention_f16x2(&a, c.st) : sm_attention_f32(&a, c.st);
 }
-
-// The last block's attention matrix (sm_forward_io.last_attn / last_attn_cls; vision_transformer.py:307-314): Q|K of block 12 -
-// rows [0, 768) of its qkv weight, a prefix of the same tensor in every weight format, with the same fold arguments - into
-// ws.QKV as (M, 768), then the probabilities kernel once per requested output.  `x` is what the block's own qkv projection reads.
-static int last_attention(const Ctx& c, const sm_forward_io* io, int B, int N, int64_t M, const float* x, const float* qkv_w, float qkv_s,
-                          const float* qkv_b, const Fold& fq, float* QK, float* tmp) {
-    const int D = SM_EMBED;
-    if (c.S) {
-        TRY_(linear(c, x, D, qkv_w, qkv_s, qkv_b, QK, 2 * D, M, 2 * D, D, SM_EPI_BIAS, nullptr, 0, true, fq));
-    } else {  // exact-fp32 mode: the projection is fp32 (into `tmp`), the kernel's operands are its F16X2 split
-        TRY_(linear(c, x, D, qkv_w, qkv_s, qkv_b, tmp, 2 * D, M, 2 * D, D, SM_EPI_BIAS, nullptr, 0, false, fq));
-        TRY_(sm_split_f16x2(tmp, 2 * D, QK, 2 * D, M, 2 * D, c.st));
-    }
-    sm_attn_probs_args a = {};
-    a.Q = QK; a.K = QK + D;
-    a.sQb = a.sKb = (int64_t)N * 2 * D; a.sQr = a.sKr = 2 * D;
-    a.batch = B; a.heads = SM_HEADS; a.n_q = N; a.n_k = N; a.scale = 0.125f;
-    for (int pass = 0; pass < 2; ++pass) {
-        a.P = pass ? io->last_attn_cls : io->last_attn;
-        if (!a.P) continue;
-        a.q0 = 0; a.nq = pass ? 1 : N;
-        // both walks over the keys count: 2 x (2 nq n_k 64) per head; bytes: Q, K once + P
-        TapScope tap(c.st, "attention_probs_f16x2_kernel", 4.0 * B * SM_HEADS * a.nq * (double)N * SM_HEAD_DIM,
-                     4.0 * B * SM_HEADS * (SM_HEAD_DIM * ((double)a.nq + N) + (double)a.nq * N));
-        TRY_(sm_attention_probs_f16x2(&a, c.st));
-    }
-    return SM_OK;
+// LayerNorm of packed 384-float rows, identity row maps; call sites set the optional fields under their sm_ln_args names
+static sm_ln_args ln_args(const float* x, const float* gamma, const float* beta, float* y, int64_t rows, float eps) {
+    sm_ln_args a = {};
+    a.x = x; a.gamma = gamma; a.beta = beta; a.y = y; a.rows = (int)rows; a.eps = eps;
+    a.ldx = a.ldy = a.ldy2 = a.chain_ldy = SM_EMBED;
+    return a;
+}
+static int ln(const Ctx& c, const sm_ln_args& a) {
+    TapGuard tap(c.st, "layernorm384_kernel", 0.0, 2.0 * a.rows * SM_EMBED * 4);
+    return sm_layernorm_rows_f32(&a, c.st);
 }
 
-struct LnOpt {
-    sm_row_map in_map = {0, 0, 0}, out_map = {0, 0, 0};
-    float* ys = nullptr;        // F16X2 copy of y
-    float* y2 = nullptr;        // y + add (fp32, or F16X2 when y2_s)
-    bool y2_s = false;
-    const float* add = nullptr;
-    int add_rows = 0;
-    int n_partials = 0;
-    int64_t partial_stride = 0;
-    const float* pre_bias = nullptr;
-    const float* residual = nullptr;
-    float* raw = nullptr;       // the value before normalisation (sm_ln_args.raw)
-    // a second norm chained onto this one in the same launch (sm_ln_args.chain_*): the decoder's shared final norm
-    const float *chain_w = nullptr, *chain_b = nullptr;
-    float *chain_y = nullptr, *chain_ys = nullptr;
-    sm_row_map chain_map = {0, 0, 0};
-    float chain_eps = 0.f;
-};
-static int ln(const Ctx& c, const float* x, const float* gw, const float* gb, float* y, int64_t rows, float eps,
-              const LnOpt& o = LnOpt()) {
-    sm_ln_args a = {};
-    a.x = x; a.ldx = SM_EMBED; a.in_map = o.in_map; a.gamma = gw; a.beta = gb; a.y = y; a.ldy = SM_EMBED;
-    a.out_map = o.out_map; a.y2 = o.y2; a.ldy2 = SM_EMBED; a.add = o.add; a.add_rows = o.add_rows;
-    a.rows = (int)rows; a.eps = eps;
-    a.n_partials = o.n_partials; a.partial_stride = o.partial_stride; a.pre_bias = o.pre_bias; a.residual = o.residual;
-    a.ys = o.ys; a.y2_f16x2 = o.y2_s ? 1 : 0; a.raw = o.raw;
-    a.chain_gamma = o.chain_w; a.chain_beta = o.chain_b; a.chain_y = o.chain_y; a.chain_ys = o.chain_ys; a.chain_ldy = SM_EMBED;
-    a.chain_map = o.chain_map; a.chain_eps = o.chain_eps;
-    TapScope tap(c.st, "layernorm384_kernel", 0.0, 2.0 * rows * SM_EMBED * 4);
-    return sm_layernorm_rows_f32(&a, c.st);
+// ---- the blocks that repeat -------------------------------------------------------------------------------------------
+// self-attention over a packed (B * n, 1152) buffer: Q | K | V are its column thirds, n tokens per image
+static sm_attn_args self_attn_args(const float* qkv, int B, int n, float* O) {
+    const int D = SM_EMBED;
+    sm_attn_args a = {};
+    a.Q = qkv; a.K = qkv + D; a.V = qkv + 2 * D; a.O = O;
+    a.sQb = a.sKb = a.sVb = (int64_t)n * 3 * D; a.sQr = a.sKr = a.sVr = 3 * D;
+    a.sOb = (int64_t)n * D; a.sOr = D;
+    a.batch = B; a.heads = SM_HEADS; a.n_q = n; a.n_k = n; a.scale = 0.125f;
+    return a;
+}
+// K = 1536 products with only M/64 x 6 output tiles (encoder fc2, decoder linear2), split 4-way along K: the GEMM writes four raw
+// slices into PART, the LayerNorm launch that follows sums them in slice order with the bias and the residual
+static sm_gemm_args split_k4_args(const float* A, const float* W, float ws, float* PART, int64_t M) {
+    sm_gemm_args g = linear_args(A, SM_MLP, W, ws, nullptr, PART, SM_EMBED, M, SM_EMBED, SM_MLP, SM_EPI_BIAS);
+    g.split_k = 4; g.strideC = M * SM_EMBED;
+    return g;
+}
+static sm_ln_args split_k4_ln_args(const float* PART, const float* bias, const float* residual, const float* gamma, const float* beta,
+                                   float* y, int64_t M, float eps) {
+    sm_ln_args a = ln_args(PART, gamma, beta, y, M, eps);
+    a.n_partials = 4; a.partial_stride = M * SM_EMBED; a.pre_bias = bias; a.residual = residual;
+    return a;
 }
 
 // decoder start state in one launch: tgt = 0 (fp32 and F16X2 - zero bytes in both), tgt + query_pos = query_pos broadcast
@@ -280,38 +240,87 @@ __global__ __launch_bounds__(256) void decoder_init_kernel(const float* __restri
     }
 }
 
-#define TRY(x)                \
-    do {                      \
-        int _rc = (x);        \
-        if (_rc) return _rc;  \
-    } while (0)
+// ---- one forward: what its stages share, and the stages ---------------------------------------------------------------
+namespace {
+struct Fwd {
+    static constexpr int D = SM_EMBED;
+    const sm_weights* w;
+    const sm_forward_io* io;
+    Shape s;
+    Ws ws;
+    Ctx c;
+    float* tok;          // final-normed patch tokens (the caller's buffer when it asks for them) ...
+    const float* tok_a;  // ... and their GEMM-operand view
+    float* QD;           // normed decoder outputs of every layer, (B, L, nq, 384) (the caller's buffer when it asks for them) ...
+    const float* qd_a;   // ... and their GEMM-operand view
 
-static int forward(const sm_weights* w, const sm_forward_io* io, float* wsbase, hipStream_t st) {
-    const Shape s = make_shape(w, io->B, io->H, io->W);
-    Ws ws = carve(s, wsbase);
-    const int D = SM_EMBED;
-    const Ctx c = {w->gemm_mode >= 1, w->gemm_mode >= 2, st, w->gemm_mode == 3 ? 1 : 3};
-    const bool S = c.S;
+    int tokens() const;
+    int encoder() const;  // returns inside block 12 when io->attn_only
+    int last_attention(const sm_gemm_args& qkv) const;
+    int decoder() const;
+    int heads() const;
+    // the steps of a decoder layer (transformer_decoder.py:260-327); `tgt` is the fp32 residual stream
+    // a norm also writes tgt + query_pos (with_pos_embed): the q = k operand of self-attention, the query operand of cross-attention
+    void also_plus_query_pos(sm_ln_args& a) const { a.y2 = ws.TGTQ; a.y2_f16x2 = c.S ? 1 : 0; a.add = w->query_embed; a.add_rows = s.nq; }
+    int self_attention_block(const sm_dec_layer& d, const float* value, const float* tgt, float* out) const;
+    int cross_attention_block(const sm_dec_layer& d, int l, const float* tgt, float* out) const;
+    int decoder_layer_pre(int l) const;
+    int decoder_layer_post(int l, float* tgt, float* t2) const;
+    sm_row_map layer_rows(int l) const { return {s.nq, s.L * s.nq, l * s.nq}; }  // rows of decoder layer l in the (B, L, nq, 384) stack
+    int ffn01(const float* A, bool out_s) const;
+};
 
-    // ---- tokens: patch embedding + cls + position (vision_transformer.py:269-281) ----------------------------
+// ---- tokens: patch embedding + cls + position (vision_transformer.py:269-281) ----------------------------
+int Fwd::tokens() const {
     const float* pos = w->pos_embed;
     if (s.n != w->pos_grid * w->pos_grid) {  // interpolate_pos_encoding compares token COUNTS (:386-388)
-        TRY(sm_pos_embed_bicubic_f32(w->pos_embed, w->pos_grid, ws.pos, s.gh, s.gw, st));
+        TRY(sm_pos_embed_bicubic_f32(w->pos_embed, w->pos_grid, ws.pos, s.gh, s.gw, c.st));
         pos = ws.pos;
     }
     float* cols = ws.HID;
-    TRY(S ? sm_im2col_patches_f16x2(io->x, cols, s.B, s.H, s.W, s.P, st)
-          : sm_im2col_patches_f32(io->x, cols, s.B, s.H, s.W, s.P, st));
-    TRY(sm_cls_rows_f32(w->cls_token, pos, ws.X, s.B, s.N, st));
-    {
-        sm_gemm_args g = {};
-        g.A = cols; g.W = w->patch_w; g.bias = w->patch_b; g.C = ws.X; g.R = pos;
-        g.M = (int)s.Mp; g.N = D; g.K = 3 * s.P * s.P; g.lda = g.K; g.ldw = g.K; g.ldc = D; g.ldr = D;
-        g.batch = 1; g.epilogue = SM_EPI_PATCH; g.patch_n = s.n; g.w_scale = w->patch_s;
-        TRY(gemm(c, g));
-    }
+    TRY(c.S ? sm_im2col_patches_f16x2(io->x, cols, s.B, s.H, s.W, s.P, c.st)
+            : sm_im2col_patches_f32(io->x, cols, s.B, s.H, s.W, s.P, c.st));
+    TRY(sm_cls_rows_f32(w->cls_token, pos, ws.X, s.B, s.N, c.st));
+    const int K = 3 * s.P * s.P;
+    sm_gemm_args g = linear_args(cols, K, w->patch_w, w->patch_s, w->patch_b, ws.X, D, s.Mp, D, K, SM_EPI_PATCH, pos, D);
+    g.patch_n = s.n;
+    return gemm(c, g);
+}
 
-    // ---- 12 pre-norm blocks (vision_transformer.py:164-170) -----------------------------------------------------
+// The last block's attention matrix (sm_forward_io.last_attn / last_attn_cls; vision_transformer.py:307-314): Q|K of block 12 -
+// rows [0, 768) of its qkv weight, a prefix of the same tensor in every weight format, with the same fold arguments - into
+// ws.QKV as (M, 768), then the probabilities kernel once per requested output.  `qkv` is the block's own qkv projection.
+int Fwd::last_attention(const sm_gemm_args& qkv) const {
+    float* QK = ws.QKV;
+    sm_gemm_args g = qkv;
+    g.N = g.ldc = 2 * D;
+    if (c.S) {
+        g.C = QK;
+        TRY(gemm(c, g, true));
+    } else {  // exact-fp32 mode: the projection is fp32 (into ws.HID), the kernel's operands are its F16X2 split
+        g.C = ws.HID;
+        TRY(gemm(c, g));
+        TRY(sm_split_f16x2(ws.HID, 2 * D, QK, 2 * D, s.M, 2 * D, c.st));
+    }
+    sm_attn_probs_args a = {};
+    a.Q = QK; a.K = QK + D;
+    a.sQb = a.sKb = (int64_t)s.N * 2 * D; a.sQr = a.sKr = 2 * D;
+    a.batch = s.B; a.heads = SM_HEADS; a.n_q = s.N; a.n_k = s.N; a.scale = 0.125f;
+    for (int pass = 0; pass < 2; ++pass) {
+        a.P = pass ? io->last_attn_cls : io->last_attn;
+        if (!a.P) continue;
+        a.q0 = 0; a.nq = pass ? 1 : s.N;
+        // both walks over the keys count: 2 x (2 nq n_k 64) per head; bytes: Q, K once + P
+        TapGuard tap(c.st, "attention_probs_f16x2_kernel", 4.0 * s.B * SM_HEADS * a.nq * (double)s.N * SM_HEAD_DIM,
+                     4.0 * s.B * SM_HEADS * (SM_HEAD_DIM * ((double)a.nq + s.N) + (double)a.nq * s.N));
+        TRY(sm_attention_probs_f16x2(&a, c.st));
+    }
+    return SM_OK;
+}
+
+// ---- 12 pre-norm blocks (vision_transformer.py:164-170), then the final norm ------------------------------------
+int Fwd::encoder() const {
+    const bool S = c.S;
     // (Split mode could carry the two pre-norms of a block on the GEMM that produces their input, on the 64 x 384 full-row tile
     // of SM_EPI_RESIDUAL_LN.  Measured with three batches in flight: 17.3k images/s against 18.0k unfused - the full-row tile
     // needs 112 KiB of LDS (one workgroup per CU, 197 of them).)
@@ -327,8 +336,6 @@ static int forward(const sm_weights* w, const sm_forward_io* io, float* wsbase, 
     // 1.40 vs 1.96, B = 8: 1.53 vs 2.10, B = 16: 1.94 vs 1.93; profiles/r03_fused_vs_unfused_by_batch.log)
     const bool fused_qkv = c.W16 && fused_qkv_env != 0 && s.N <= sm_qkv_attention_max_tokens() && io->attn_path != 2 &&
                            (io->attn_path == 1 || s.B * SM_HEADS >= 96);
-    LnOpt xs;
-    xs.ys = S ? ws.Xn : nullptr;  // LN output only feeds a GEMM: F16X2 in split mode
     // sm_weights.ln_fold: norm2 rides on proj -> fc1 and the next block's norm1 on fc2 -> qkv: the residual epilogues also write the
     // raw stream as F16X2 (into Xn) with its row statistics, the consuming GEMM carries the gain in its weights and applies
     // r (x W'^T - mu c) + b' in its epilogue.  Block 0's norm1 (its input comes from the patch embedding) stays a launch.
@@ -337,219 +344,193 @@ static int forward(const sm_weights* w, const sm_forward_io* io, float* wsbase, 
     // epilogues and the statistics cost more than 23 co-resident LayerNorm launches) - so it follows the same batch rule and the same
     // pin as the attention path (sm_forward_io.attn_path: 2 = the small-batch kernels, 1 = the large-batch ones).
     const bool lnf = c.W16 && w->ln_fold != 0 && io->attn_path != 1 && (io->attn_path == 2 || s.B * SM_HEADS < 96);
-    const bool split_fc2 = c.W16 && S && io->attn_path == 0 && s.M <= SM_SPLIT_FC2_ROWS;
+    const bool split_fc2 = c.W16 && S && io->attn_path == 0 && s.M <= SM_SPLIT_FC2_ROWS;  // see SM_SPLIT_FC2_ROWS
+
+    auto pre_norm = [&](const float* gamma, const float* beta) {  // X -> Xn; the LN output only feeds a GEMM: F16X2 in split mode
+        sm_ln_args a = ln_args(ws.X, gamma, beta, S ? nullptr : ws.Xn, s.M, 1e-6f);
+        a.ys = S ? ws.Xn : nullptr;
+        return ln(c, a);
+    };
     for (int i = 0; i < SM_ENC_DEPTH; ++i) {
         const sm_enc_layer& e = w->enc[i];
+        const bool last = i + 1 == SM_ENC_DEPTH;
         const bool n1_done = split_fc2 && i > 0;  // the previous block's split fc2 ended in this block's norm1
         const bool f1 = lnf && i > 0 && !n1_done;  // this block's norm1 is folded into its qkv projection
-        if (!f1 && !n1_done) TRY(ln(c, ws.X, e.norm1_w, e.norm1_b, S ? nullptr : ws.Xn, s.M, 1e-6f, xs));
-        Fold fq;
-        if (f1) { fq.stats = ws.ST; fq.cvec = e.qkv_c; fq.eps = 1e-6f; }
-        const float* qkv_w = f1 ? e.qkv_fw : e.qkv_w;
-        const float* qkv_b = f1 ? e.qkv_fb : e.qkv_b;
-        const float qkv_s = f1 ? e.qkv_fs : e.qkv_s;
-        if (i == SM_ENC_DEPTH - 1 && (io->last_attn || io->last_attn_cls)) {
+        if (!f1 && !n1_done) TRY(pre_norm(e.norm1_w, e.norm1_b));
+        sm_gemm_args qkv = linear_args(ws.Xn, D, f1 ? e.qkv_fw : e.qkv_w, f1 ? e.qkv_fs : e.qkv_s, f1 ? e.qkv_fb : e.qkv_b, ws.QKV,
+                                       3 * D, s.M, 3 * D, D, SM_EPI_BIAS);
+        if (f1) { qkv.ln_stats = ws.ST; qkv.ln_c = e.qkv_c; qkv.ln_eps = 1e-6f; }
+        if (last && (io->last_attn || io->last_attn_cls)) {
             // ws.HID is free here (block 11's fc2 has consumed it), ws.QKV is rewritten by this block's own projection below
-            TRY(last_attention(c, io, s.B, s.N, s.M, ws.Xn, qkv_w, qkv_s, qkv_b, fq, ws.QKV, ws.HID));
+            TRY(last_attention(qkv));
             if (io->attn_only) return SM_OK;
         }
         if (fused_qkv) {
             sm_qkv_attn_args q = {};
-            q.Xn = ws.Xn; q.Wqkv = qkv_w; q.bias = qkv_b; q.O = ws.AO; q.ldx = D; q.ldo = D;
-            q.B = s.B; q.N = s.N; q.w_scale = qkv_s; q.scale = 0.125f; q.out_f16x2 = 1; q.mfma_terms = c.terms;
-            q.ln_stats = fq.stats; q.ln_c = fq.cvec; q.ln_eps = fq.eps;
+            q.Xn = qkv.A; q.Wqkv = qkv.W; q.bias = qkv.bias; q.O = ws.AO; q.ldx = D; q.ldo = D;
+            q.B = s.B; q.N = s.N; q.w_scale = qkv.w_scale; q.scale = 0.125f; q.out_f16x2 = 1; q.mfma_terms = c.terms;
+            q.ln_stats = qkv.ln_stats; q.ln_c = qkv.ln_c; q.ln_eps = qkv.ln_eps;
             // algorithmic work of SURVEY.md 8d: 2 N 384 1152 + 4 N^2 384 FLOPs, x in + o out bytes per image
-            TapScope tap(c.st, sm_qkv_attention_kernel_name(c.terms), (double)s.B * (2.0 * s.N * D * 3 * D + 4.0 * s.N * s.N * D),
+            TapGuard tap(c.st, sm_qkv_attention_kernel_name(c.terms), (double)s.B * (2.0 * s.N * D * 3 * D + 4.0 * s.N * s.N * D),
                          2.0 * s.M * D * 4);
             TRY(sm_qkv_attention_w16(&q, c.st));
         } else {
-            TRY(linear(c, ws.Xn, D, qkv_w, qkv_s, qkv_b, ws.QKV, 3 * D, s.M, 3 * D, D, SM_EPI_BIAS, nullptr, 0, S, fq));
-            sm_attn_args a = {};
-            a.Q = ws.QKV; a.K = ws.QKV + D; a.V = ws.QKV + 2 * D; a.O = ws.AO;
-            a.sQb = a.sKb = a.sVb = (int64_t)s.N * 3 * D; a.sQr = a.sKr = a.sVr = 3 * D;
-            a.sOb = (int64_t)s.N * D; a.sOr = D;
-            a.batch = s.B; a.heads = SM_HEADS; a.n_q = s.N; a.n_k = s.N; a.scale = 0.125f;
-            TRY(attn(c, a));
+            TRY(gemm(c, qkv, S));
+            TRY(attn(c, self_attn_args(ws.QKV, s.B, s.N, ws.AO)));
         }
-        Fold fp;
-        if (lnf) { fp.xs = ws.Xn; fp.stats_out = ws.ST; }
-        TRY(linear(c, ws.AO, D, e.proj_w, e.proj_s, e.proj_b, ws.X, D, s.M, D, D, SM_EPI_RESIDUAL, ws.X, D, false, fp));
-        if (!lnf) TRY(ln(c, ws.X, e.norm2_w, e.norm2_b, S ? nullptr : ws.Xn, s.M, 1e-6f, xs));
-        Fold f2;
-        if (lnf) { f2.stats = ws.ST; f2.cvec = e.fc1_c; f2.eps = 1e-6f; }
-        TRY(linear(c, ws.Xn, D, lnf ? e.fc1_fw : e.fc1_w, lnf ? e.fc1_fs : e.fc1_s, lnf ? e.fc1_fb : e.fc1_b, ws.HID, SM_MLP, s.M, SM_MLP, D,
-                   SM_EPI_GELU, nullptr, 0, S, f2));
-        if (split_fc2 && i + 1 < SM_ENC_DEPTH) {
+        sm_gemm_args proj = linear_args(ws.AO, D, e.proj_w, e.proj_s, e.proj_b, ws.X, D, s.M, D, D, SM_EPI_RESIDUAL, ws.X, D);
+        if (lnf) { proj.C2 = ws.Xn; proj.ln_stats_out = ws.ST; }
+        TRY(gemm(c, proj));
+        if (!lnf) TRY(pre_norm(e.norm2_w, e.norm2_b));
+        sm_gemm_args fc1 = linear_args(ws.Xn, D, lnf ? e.fc1_fw : e.fc1_w, lnf ? e.fc1_fs : e.fc1_s, lnf ? e.fc1_fb : e.fc1_b, ws.HID,
+                                       SM_MLP, s.M, SM_MLP, D, SM_EPI_GELU);
+        if (lnf) { fc1.ln_stats = ws.ST; fc1.ln_c = e.fc1_c; fc1.ln_eps = 1e-6f; }
+        TRY(gemm(c, fc1, S));
+        if (split_fc2 && !last) {
             const sm_enc_layer& nx = w->enc[i + 1];
-            sm_gemm_args g = {};
-            g.A = ws.HID; g.W = e.fc2_w; g.C = ws.PART; g.M = (int)s.M; g.N = D; g.K = SM_MLP; g.lda = SM_MLP;
-            g.ldw = SM_MLP; g.ldc = D; g.batch = 1; g.epilogue = SM_EPI_BIAS; g.split_k = 4; g.strideC = s.M * D;
-            g.w_scale = e.fc2_s;
-            TRY(gemm(c, g));
-            LnOpt o;  // x += fc2 (slices + bias + residual, written back as the stream) and the next block's norm1 of it
-            o.ys = ws.Xn; o.n_partials = 4; o.partial_stride = s.M * D; o.pre_bias = e.fc2_b; o.residual = ws.X; o.raw = ws.X;
-            TRY(ln(c, ws.PART, nx.norm1_w, nx.norm1_b, nullptr, s.M, 1e-6f, o));
+            TRY(gemm(c, split_k4_args(ws.HID, e.fc2_w, e.fc2_s, ws.PART, s.M)));
+            // x += fc2 (slices + bias + residual, written back as the stream) and the next block's norm1 of it
+            sm_ln_args a = split_k4_ln_args(ws.PART, e.fc2_b, ws.X, nx.norm1_w, nx.norm1_b, nullptr, s.M, 1e-6f);
+            a.ys = ws.Xn; a.raw = ws.X;
+            TRY(ln(c, a));
         } else {
-            Fold fo;
-            if (lnf && i + 1 < SM_ENC_DEPTH) { fo.xs = ws.Xn; fo.stats_out = ws.ST; }
-            TRY(linear(c, ws.HID, SM_MLP, e.fc2_w, e.fc2_s, e.fc2_b, ws.X, D, s.M, D, SM_MLP, SM_EPI_RESIDUAL, ws.X, D, false, fo));
+            sm_gemm_args fc2 = linear_args(ws.HID, SM_MLP, e.fc2_w, e.fc2_s, e.fc2_b, ws.X, D, s.M, D, SM_MLP, SM_EPI_RESIDUAL, ws.X, D);
+            if (lnf && !last) { fc2.C2 = ws.Xn; fc2.ln_stats_out = ws.ST; }
+            TRY(gemm(c, fc2));
         }
     }
     // final norm on the last layer only (the other 11 per-layer norms of :299 are dead work when
     // lateral_connection=False), dropping the cls row on the way (maskformer.py:107-108,177)
-    float* tok = io->patch_tokens ? io->patch_tokens : ws.TOK;
-    {
-        LnOpt o;
-        o.in_map = {s.n, s.N, 1};
-        o.ys = S ? ws.TOKs : nullptr;
-        TRY(ln(c, ws.X, w->enc_norm_w, w->enc_norm_b, tok, s.Mp, 1e-6f, o));
-    }
-    if (io->encoder_only) return SM_OK;
-    const float* tok_a = S ? ws.TOKs : tok;  // GEMM-operand view of the tokens
+    sm_ln_args a = ln_args(ws.X, w->enc_norm_w, w->enc_norm_b, tok, s.Mp, 1e-6f);
+    a.in_map = {s.n, s.N, 1};
+    a.ys = S ? ws.TOKs : nullptr;
+    return ln(c, a);
+}
 
-    // ---- 6 post-norm decoder layers (transformer_decoder.py:260-297, :112-150) ----------------------------------
-    float* QD = io->queries ? io->queries : ws.QD;
-    const float* qpos = w->query_embed;
-    {
-        const int64_t total4 = s.Md * D / 4;
-        const int grid = (int)((total4 + 255) / 256 < 2048 ? (total4 + 255) / 256 : 2048);
-        if (S)
-            hipLaunchKernelGGL(decoder_init_kernel<true>, dim3(grid), dim3(256), 0, st, qpos, ws.TGT, ws.TGTs, ws.TGTQ, s.nq, total4);
-        else
-            hipLaunchKernelGGL(decoder_init_kernel<false>, dim3(grid), dim3(256), 0, st, qpos, ws.TGT, ws.TGTs, ws.TGTQ, s.nq, total4);
-        TRY(check_launch("decoder_init"));
-    }
+// ---- decoder layers (transformer_decoder.py:260-327) -----------------------------------------------------------------
+// out = tgt + self_attn(q = k = tgt + query_pos, v = `value`)  ->  the in-projection is ONE launch: columns [0,768) read TGTQ,
+// [768,1152) the value operand
+int Fwd::self_attention_block(const sm_dec_layer& d, const float* value, const float* tgt, float* out) const {
+    sm_gemm_args g = linear_args(ws.TGTQ, D, d.sa_in_w, d.sa_in_s, d.sa_in_b, ws.QK, 3 * D, s.Md, 3 * D, D, SM_EPI_BIAS);
+    g.A_alt = value; g.alt_from_n = 2 * D;
+    TRY(gemm(c, g, c.S));
+    TRY(attn(c, self_attn_args(ws.QK, s.B, s.nq, ws.AOd)));
+    return gemm(c, linear_args(ws.AOd, D, d.sa_out_w, d.sa_out_s, d.sa_out_b, out, D, s.Md, D, D, SM_EPI_RESIDUAL, tgt, D));
+}
+// out = tgt + cross_attn(q = tgt + query_pos, k = v = memory (pos = None)); K | V of layer l: columns [l*768, (l+1)*768) of ws.KV
+int Fwd::cross_attention_block(const sm_dec_layer& d, int l, const float* tgt, float* out) const {
+    TRY(gemm(c, linear_args(ws.TGTQ, D, d.ca_in_w, d.ca_in_s, d.ca_in_b, ws.Qc, D, s.Md, D, D, SM_EPI_BIAS), c.S));
+    sm_attn_args a = {};
+    a.Q = ws.Qc; a.K = ws.KV + (int64_t)l * 2 * D; a.V = a.K + D; a.O = ws.AOd;
+    a.sQb = (int64_t)s.nq * D; a.sQr = D; a.sKb = a.sVb = (int64_t)s.n * s.KVW; a.sKr = a.sVr = s.KVW;
+    a.sOb = (int64_t)s.nq * D; a.sOr = D;
+    a.batch = s.B; a.heads = SM_HEADS; a.n_q = s.nq; a.n_k = s.n; a.scale = 0.125f;
+    TRY(attn(c, a));
+    return gemm(c, linear_args(ws.AOd, D, d.ca_out_w, d.ca_out_s, d.ca_out_b, out, D, s.Md, D, D, SM_EPI_RESIDUAL, tgt, D));
+}
+
+// forward_pre (transformer_decoder.py:299-327): tgt2 = norm_k(tgt) feeds the sub-block, tgt += sub-block(tgt2); the
+// residual stream ws.TGT (fp32) is updated in place by the RESIDUAL epilogues and never normalised in the layer
+int Fwd::decoder_layer_pre(int l) const {
+    const sm_dec_layer& d = w->dec[l];
+    const bool S = c.S;
+    float* tgt = ws.TGT;
+    const float* nrm_a = S ? ws.TGTs : ws.T2;  // GEMM-operand view of the normed tgt: F16X2, or the fp32 copy (fp32 mode only)
+    auto norm = [&](const float* gamma, const float* beta, bool plus_query_pos) {
+        sm_ln_args a = ln_args(tgt, gamma, beta, S ? nullptr : ws.T2, s.Md, 1e-5f);
+        a.ys = S ? ws.TGTs : nullptr;
+        if (plus_query_pos) also_plus_query_pos(a);
+        return ln(c, a);
+    };
+    TRY(norm(d.norm1_w, d.norm1_b, true));  // norm1 -> tgt2 (value operand) and tgt2 + query_pos (q = k operand)
+    TRY(self_attention_block(d, nrm_a, tgt, tgt));
+    TRY(norm(d.norm2_w, d.norm2_b, true));  // norm2 -> only tgt2 + query_pos is needed (cross-attention query; key = value = memory)
+    TRY(cross_attention_block(d, l, tgt, tgt));
+    TRY(norm(d.norm3_w, d.norm3_b, false));  // norm3 -> operand of linear1
+    TRY(gemm(c, linear_args(nrm_a, D, d.lin1_w, d.lin1_s, d.lin1_b, ws.HIDd, SM_MLP, s.Md, SM_MLP, D, SM_EPI_RELU), S));
+    TRY(gemm(c, linear_args(ws.HIDd, SM_MLP, d.lin2_w, d.lin2_s, d.lin2_b, tgt, D, s.Md, D, SM_MLP, SM_EPI_RESIDUAL, tgt, D)));
+    // intermediate.append(self.norm(output)) (:138-139), scattered into (B, L, nq, 384) (+ F16X2 copy)
+    sm_ln_args fin = ln_args(tgt, w->dec_norm_w, w->dec_norm_b, QD, s.Md, 1e-5f);
+    fin.out_map = layer_rows(l);
+    fin.ys = S ? ws.QDs : nullptr;
+    return ln(c, fin);
+}
+
+// forward_post (transformer_decoder.py:260-297): tgt = norm_k(tgt + sub-block(tgt)).  The residual epilogues write the sums into
+// `t2` and the norms the new tgt back into `tgt` - except norm3, which leaves the layer's output in `t2`: the caller swaps the two
+int Fwd::decoder_layer_post(int l, float* tgt, float* t2) const {
+    const sm_dec_layer& d = w->dec[l];
+    const bool S = c.S;
+    const float* tgt_a = S ? ws.TGTs : tgt;  // GEMM-operand view of tgt
+    TRY(self_attention_block(d, tgt_a, tgt, t2));
+    sm_ln_args n1 = ln_args(t2, d.norm1_w, d.norm1_b, tgt, s.Md, 1e-5f);  // norm1 -> tgt (fp32: residual of the next block) + tgt + query_pos (cross-attention query operand)
+    also_plus_query_pos(n1);
+    TRY(ln(c, n1));
+    TRY(cross_attention_block(d, l, tgt, t2));
+    sm_ln_args n2 = ln_args(t2, d.norm2_w, d.norm2_b, tgt, s.Md, 1e-5f);  // norm2 -> tgt (residual of the FFN) (+ F16X2 copy: operand of linear1)
+    n2.ys = S ? ws.TGTs : nullptr;
+    TRY(ln(c, n2));
+    // FFN: linear2 (K = 1536, only M/64 x 6 tiles) is split 4-way along K; norm3 sums the slices + bias + residual
+    TRY(gemm(c, linear_args(tgt_a, D, d.lin1_w, d.lin1_s, d.lin1_b, ws.HIDd, SM_MLP, s.Md, SM_MLP, D, SM_EPI_RELU), S));
+    TRY(gemm(c, split_k4_args(ws.HIDd, d.lin2_w, d.lin2_s, ws.PART, s.Md)));
+    // norm3(sum of slices + bias + tgt) -> new tgt (fp32 + F16X2) and tgt + query_pos
+    sm_ln_args n3 = split_k4_ln_args(ws.PART, d.lin2_b, tgt, d.norm3_w, d.norm3_b, t2, s.Md, 1e-5f);
+    n3.ys = S ? ws.TGTs : nullptr;
+    also_plus_query_pos(n3);
+    // ... and, chained in the same launch, the shared final norm on this layer's output, scattered into (B, L, nq, 384)
+    // (+ F16X2 copy): transformer_decoder.py:138-139.  Six launches fewer on the critical chain of a forward (serving).
+    n3.chain_gamma = w->dec_norm_w; n3.chain_beta = w->dec_norm_b; n3.chain_y = QD; n3.chain_ys = S ? ws.QDs : nullptr;
+    n3.chain_map = layer_rows(l); n3.chain_eps = 1e-5f;
+    return ln(c, n3);
+}
+
+// ---- 6 decoder layers, post-norm as shipped (transformer_decoder.py:112-150) -----------------------------------------
+int Fwd::decoder() const {
+    const int64_t total4 = s.Md * D / 4;
+    const int grid = (int)((total4 + 255) / 256 < 2048 ? (total4 + 255) / 256 : 2048);
+    if (c.S)
+        hipLaunchKernelGGL(decoder_init_kernel<true>, dim3(grid), dim3(256), 0, c.st, w->query_embed, ws.TGT, ws.TGTs, ws.TGTQ, s.nq, total4);
+    else
+        hipLaunchKernelGGL(decoder_init_kernel<false>, dim3(grid), dim3(256), 0, c.st, w->query_embed, ws.TGT, ws.TGTs, ws.TGTQ, s.nq, total4);
+    TRY(check_launch("decoder_init"));
     // cross-attention keys/values of every layer depend only on the encoder memory: one large GEMM
     // (B*n x 384) x (384 x L*768) instead of L small ones on the critical chain
-    const int KVW = s.L * 2 * D;
-    TRY(linear(c, tok_a, D, w->dec_kv_w, w->dec_kv_s, w->dec_kv_b, ws.KV, KVW, s.Mp, KVW, D, SM_EPI_BIAS, nullptr, 0, S));
-    for (int l = 0; l < s.L && w->normalize_before; ++l) {
-        // forward_pre (transformer_decoder.py:299-327): tgt2 = norm_k(tgt) feeds the sub-block, tgt += sub-block(tgt2); the
-        // residual stream ws.TGT (fp32) is updated in place by the RESIDUAL epilogues and never normalised in the layer
-        const sm_dec_layer& d = w->dec[l];
-        float* nrm = S ? nullptr : ws.T2;                 // fp32 copy of the normed tgt (fp32 mode only)
-        const float* nrm_a = S ? ws.TGTs : ws.T2;         // its GEMM-operand view
-        {
-            LnOpt o;  // norm1 -> tgt2 (value operand) and tgt2 + query_pos (q = k operand)
-            o.ys = S ? ws.TGTs : nullptr; o.y2 = ws.TGTQ; o.y2_s = S; o.add = qpos; o.add_rows = s.nq;
-            TRY(ln(c, ws.TGT, d.norm1_w, d.norm1_b, nrm, s.Md, 1e-5f, o));
-        }
-        {
-            sm_gemm_args g = {};
-            g.A = ws.TGTQ; g.A_alt = nrm_a; g.alt_from_n = 2 * D; g.W = d.sa_in_w; g.bias = d.sa_in_b; g.C = ws.QK;
-            g.M = (int)s.Md; g.N = 3 * D; g.K = D; g.lda = D; g.ldw = D; g.ldc = 3 * D; g.batch = 1; g.epilogue = SM_EPI_BIAS;
-            g.w_scale = d.sa_in_s;
-            TRY(gemm(c, g, S));
-        }
-        sm_attn_args a = {};
-        a.Q = ws.QK; a.K = ws.QK + D; a.V = ws.QK + 2 * D; a.O = ws.AOd;
-        a.sQb = a.sKb = a.sVb = (int64_t)s.nq * 3 * D; a.sQr = a.sKr = a.sVr = 3 * D;
-        a.sOb = (int64_t)s.nq * D; a.sOr = D;
-        a.batch = s.B; a.heads = SM_HEADS; a.n_q = s.nq; a.n_k = s.nq; a.scale = 0.125f;
-        TRY(attn(c, a));
-        TRY(linear(c, ws.AOd, D, d.sa_out_w, d.sa_out_s, d.sa_out_b, ws.TGT, D, s.Md, D, D, SM_EPI_RESIDUAL, ws.TGT, D));
-        {
-            LnOpt o;  // norm2 -> only tgt2 + query_pos is needed (cross-attention query; key = value = memory)
-            o.ys = S ? ws.TGTs : nullptr; o.y2 = ws.TGTQ; o.y2_s = S; o.add = qpos; o.add_rows = s.nq;
-            TRY(ln(c, ws.TGT, d.norm2_w, d.norm2_b, nrm, s.Md, 1e-5f, o));
-        }
-        TRY(linear(c, ws.TGTQ, D, d.ca_in_w, d.ca_in_s, d.ca_in_b, ws.Qc, D, s.Md, D, D, SM_EPI_BIAS, nullptr, 0, S));
-        a = {};
-        a.Q = ws.Qc; a.K = ws.KV + (int64_t)l * 2 * D; a.V = a.K + D; a.O = ws.AOd;
-        a.sQb = (int64_t)s.nq * D; a.sQr = D; a.sKb = a.sVb = (int64_t)s.n * KVW; a.sKr = a.sVr = KVW;
-        a.sOb = (int64_t)s.nq * D; a.sOr = D;
-        a.batch = s.B; a.heads = SM_HEADS; a.n_q = s.nq; a.n_k = s.n; a.scale = 0.125f;
-        TRY(attn(c, a));
-        TRY(linear(c, ws.AOd, D, d.ca_out_w, d.ca_out_s, d.ca_out_b, ws.TGT, D, s.Md, D, D, SM_EPI_RESIDUAL, ws.TGT, D));
-        {
-            LnOpt o;  // norm3 -> operand of linear1
-            o.ys = S ? ws.TGTs : nullptr;
-            TRY(ln(c, ws.TGT, d.norm3_w, d.norm3_b, nrm, s.Md, 1e-5f, o));
-        }
-        TRY(linear(c, nrm_a, D, d.lin1_w, d.lin1_s, d.lin1_b, ws.HIDd, SM_MLP, s.Md, SM_MLP, D, SM_EPI_RELU, nullptr, 0, S));
-        TRY(linear(c, ws.HIDd, SM_MLP, d.lin2_w, d.lin2_s, d.lin2_b, ws.TGT, D, s.Md, D, SM_MLP, SM_EPI_RESIDUAL, ws.TGT, D));
-        {
-            LnOpt o;  // intermediate.append(self.norm(output)) (:138-139), scattered into (B, L, nq, 384) (+ F16X2 copy)
-            o.out_map = {s.nq, s.L * s.nq, l * s.nq};
-            o.ys = S ? ws.QDs : nullptr;
-            TRY(ln(c, ws.TGT, w->dec_norm_w, w->dec_norm_b, QD, s.Md, 1e-5f, o));
+    TRY(gemm(c, linear_args(tok_a, D, w->dec_kv_w, w->dec_kv_s, w->dec_kv_b, ws.KV, s.KVW, s.Mp, s.KVW, D, SM_EPI_BIAS), c.S));
+    float *tgt = ws.TGT, *t2 = ws.T2;
+    for (int l = 0; l < s.L; ++l) {
+        if (w->normalize_before) {
+            TRY(decoder_layer_pre(l));
+        } else {
+            TRY(decoder_layer_post(l, tgt, t2));
+            std::swap(tgt, t2);  // norm3 wrote the new tgt into t2: TGT / T2 swap roles every layer
         }
     }
-    for (int l = 0; l < s.L && !w->normalize_before; ++l) {
-        const sm_dec_layer& d = w->dec[l];
-        const float* tgt_a = S ? ws.TGTs : ws.TGT;  // GEMM-operand view of tgt (TGT / T2 swap roles every layer)
-        // self-attention: q = k = tgt + query_pos, v = tgt  ->  ONE launch: columns [0,768) read TGTQ, [768,1152) TGT
-        {
-            sm_gemm_args g = {};
-            g.A = ws.TGTQ; g.A_alt = tgt_a; g.alt_from_n = 2 * D; g.W = d.sa_in_w; g.bias = d.sa_in_b; g.C = ws.QK;
-            g.M = (int)s.Md; g.N = 3 * D; g.K = D; g.lda = D; g.ldw = D; g.ldc = 3 * D; g.batch = 1; g.epilogue = SM_EPI_BIAS;
-            g.w_scale = d.sa_in_s;
-            TRY(gemm(c, g, S));
-        }
-        sm_attn_args a = {};
-        a.Q = ws.QK; a.K = ws.QK + D; a.V = ws.QK + 2 * D; a.O = ws.AOd;
-        a.sQb = a.sKb = a.sVb = (int64_t)s.nq * 3 * D; a.sQr = a.sKr = a.sVr = 3 * D;
-        a.sOb = (int64_t)s.nq * D; a.sOr = D;
-        a.batch = s.B; a.heads = SM_HEADS; a.n_q = s.nq; a.n_k = s.nq; a.scale = 0.125f;
-        TRY(attn(c, a));
-        TRY(linear(c, ws.AOd, D, d.sa_out_w, d.sa_out_s, d.sa_out_b, ws.T2, D, s.Md, D, D, SM_EPI_RESIDUAL, ws.TGT, D));
-        {
-            LnOpt o;  // norm1 -> tgt (fp32: residual of the next block) + tgt + query_pos (cross-attention query operand)
-            o.y2 = ws.TGTQ; o.y2_s = S; o.add = qpos; o.add_rows = s.nq;
-            TRY(ln(c, ws.T2, d.norm1_w, d.norm1_b, ws.TGT, s.Md, 1e-5f, o));
-        }
-        // cross-attention: q = tgt + query_pos, k = v = memory (pos = None)
-        TRY(linear(c, ws.TGTQ, D, d.ca_in_w, d.ca_in_s, d.ca_in_b, ws.Qc, D, s.Md, D, D, SM_EPI_BIAS, nullptr, 0, S));
-        a = {};
-        a.Q = ws.Qc; a.K = ws.KV + (int64_t)l * 2 * D; a.V = a.K + D; a.O = ws.AOd;
-        a.sQb = (int64_t)s.nq * D; a.sQr = D; a.sKb = a.sVb = (int64_t)s.n * KVW; a.sKr = a.sVr = KVW;
-        a.sOb = (int64_t)s.nq * D; a.sOr = D;
-        a.batch = s.B; a.heads = SM_HEADS; a.n_q = s.nq; a.n_k = s.n; a.scale = 0.125f;
-        TRY(attn(c, a));
-        TRY(linear(c, ws.AOd, D, d.ca_out_w, d.ca_out_s, d.ca_out_b, ws.T2, D, s.Md, D, D, SM_EPI_RESIDUAL, ws.TGT, D));
-        {
-            LnOpt o;  // norm2 -> tgt (residual of the FFN) (+ F16X2 copy: operand of linear1)
-            o.ys = S ? ws.TGTs : nullptr;
-            TRY(ln(c, ws.T2, d.norm2_w, d.norm2_b, ws.TGT, s.Md, 1e-5f, o));
-        }
-        // FFN: linear2 (K = 1536, only M/64 x 6 tiles) is split 4-way along K; norm3 sums the slices + bias + residual
-        TRY(linear(c, tgt_a, D, d.lin1_w, d.lin1_s, d.lin1_b, ws.HIDd, SM_MLP, s.Md, SM_MLP, D, SM_EPI_RELU, nullptr, 0, S));
-        {
-            sm_gemm_args g = {};
-            g.A = ws.HIDd; g.W = d.lin2_w; g.C = ws.PART; g.M = (int)s.Md; g.N = D; g.K = SM_MLP; g.lda = SM_MLP;
-            g.ldw = SM_MLP; g.ldc = D; g.batch = 1; g.epilogue = SM_EPI_BIAS; g.split_k = 4; g.strideC = s.Md * D;
-            g.w_scale = d.lin2_s;
-            TRY(gemm(c, g));
-        }
-        {
-            LnOpt o;  // norm3(sum of slices + bias + tgt) -> new tgt (fp32 + F16X2) and tgt + query_pos
-            o.ys = S ? ws.TGTs : nullptr;
-            o.y2 = ws.TGTQ; o.y2_s = S; o.add = qpos; o.add_rows = s.nq;
-            o.n_partials = 4; o.partial_stride = s.Md * D; o.pre_bias = d.lin2_b; o.residual = ws.TGT;
-            // ... and, chained in the same launch, the shared final norm on this layer's output, scattered into (B, L, nq, 384)
-            // (+ F16X2 copy): transformer_decoder.py:138-139.  Six launches fewer on the critical chain of a forward (serving).
-            o.chain_w = w->dec_norm_w; o.chain_b = w->dec_norm_b; o.chain_y = QD; o.chain_ys = S ? ws.QDs : nullptr;
-            o.chain_map = {s.nq, s.L * s.nq, l * s.nq}; o.chain_eps = 1e-5f;
-            TRY(ln(c, ws.PART, d.norm3_w, d.norm3_b, ws.T2, s.Md, 1e-5f, o));
-        }
-        { float* t = ws.TGT; ws.TGT = ws.T2; ws.T2 = t; }  // norm3 wrote the new tgt into T2
-    }
-    const float* qd_a = S ? ws.QDs : QD;
+    return SM_OK;
+}
 
-    // ---- heads --------------------------------------------------------------------------------------------------
-    TRY(sm_query_mean_f32(QD, io->features, s.B, s.L, s.nq, st));
+// ---- heads --------------------------------------------------------------------------------------------------
+// relu(ffn1(relu(ffn0(A)))) into ws.O2 (through ws.O1): the first two layers of the 3-layer MLP `ffn` (MLP.forward :265-268), shared
+// by the mask head and the objectness head; `out_s`: O2 in F16X2 (it feeds another GEMM) or in fp32 (it feeds the row dot product)
+int Fwd::ffn01(const float* A, bool out_s) const {
+    TRY(gemm(c, linear_args(A, D, w->ffn0_w, w->ffn0_s, w->ffn0_b, ws.O1, D, s.Mo, D, D, SM_EPI_RELU), c.S));
+    return gemm(c, linear_args(ws.O1, D, w->ffn1_w, w->ffn1_s, w->ffn1_b, ws.O2, D, s.Mo, D, D, SM_EPI_RELU), out_s);
+}
+
+int Fwd::heads() const {
+    const bool S = c.S;
+    const float* q_a = qd_a;
+    TRY(sm_query_mean_f32(QD, io->features, s.B, s.L, s.nq, c.st));
     if (w->mask_head_ffn) {
         // return_intermediate=True with use_binary_classifier=False (maskformer.py:225): the mask einsum takes
         // ffn(queries), a 384->384->384->384 MLP with ReLU between the layers (MLP.forward :265-268), not the queries
-        TRY(linear(c, qd_a, D, w->ffn0_w, w->ffn0_s, w->ffn0_b, ws.O1, D, s.Mo, D, D, SM_EPI_RELU, nullptr, 0, S));
-        TRY(linear(c, ws.O1, D, w->ffn1_w, w->ffn1_s, w->ffn1_b, ws.O2, D, s.Mo, D, D, SM_EPI_RELU, nullptr, 0, S));
-        TRY(linear(c, ws.O2, D, w->ffn2_w, w->ffn2_s, w->ffn2_b, ws.O1, D, s.Mo, D, D, SM_EPI_BIAS, nullptr, 0, S));
-        qd_a = ws.O1;
+        TRY(ffn01(q_a, S));
+        TRY(gemm(c, linear_args(ws.O2, D, w->ffn2_w, w->ffn2_s, w->ffn2_b, ws.O1, D, s.Mo, D, D, SM_EPI_BIAS), S));
+        q_a = ws.O1;
     }
     // return_intermediate=False (the 3-D path, maskformer.py:219-220): the decoder hands back its last layer only, so only that
     // layer's queries reach the mask einsum; the outputs are then (B, 1, nq, 2gh, 2gw)
     const int Lm = io->last_layer_only ? 1 : s.L;
-    const float* qm_a = qd_a + (io->last_layer_only ? (int64_t)(s.L - 1) * s.nq * D : 0);
+    const float* qm_a = q_a + (io->last_layer_only ? (int64_t)(s.L - 1) * s.nq * D : 0);
     if (s.n % 4 == 0) {
         // mask_pred = sigmoid(up(Q . tok^T)): the einsum of maskformer.py:223 commutes with the bilinear x2 of the pixel
         // decoder (:144-162) - both linear - so the GEMM runs on the token grid (N = n instead of 4n) and the (B, 4n,
@@ -560,10 +541,10 @@ static int forward(const sm_weights* w, const sm_forward_io* io, float* wsbase, 
         g.strideA = (int64_t)s.L * s.nq * D; g.strideW = (int64_t)s.n * D; g.strideC = (int64_t)Lm * s.nq * s.n;
         g.batch = s.B; g.epilogue = SM_EPI_BIAS;
         TRY(gemm(c, g));
-        TRY(sm_upsample_logits_sigmoid_f32(ws.LOG, io->mask_logits, io->mask_pred, (int64_t)s.B * Lm * s.nq, s.gh, s.gw, s.sf, st));
+        TRY(sm_upsample_logits_sigmoid_f32(ws.LOG, io->mask_logits, io->mask_pred, (int64_t)s.B * Lm * s.nq, s.gh, s.gw, s.sf, c.st));
     } else {  // token counts that are not a multiple of 4 (float4 rows of the GEMM output): the literal order
-        TRY(S ? sm_upsample_tokens_f16x2(tok, (int64_t)s.n * D, ws.UP, s.B, s.gh, s.gw, s.sf, st)
-              : sm_upsample_tokens_f32(tok, (int64_t)s.n * D, ws.UP, s.B, s.gh, s.gw, s.sf, st));
+        TRY(S ? sm_upsample_tokens_f16x2(tok, (int64_t)s.n * D, ws.UP, s.B, s.gh, s.gw, s.sf, c.st)
+              : sm_upsample_tokens_f32(tok, (int64_t)s.n * D, ws.UP, s.B, s.gh, s.gw, s.sf, c.st));
         // mask_pred[b] = sigmoid(Q[b] (L*nq x 384) . up[b]^T (384 x 4n))   (maskformer.py:223)
         sm_gemm_args g = {};
         g.A = qm_a; g.W = ws.UP; g.C = io->mask_logits ? io->mask_logits : ws.LOG; g.C2 = io->mask_pred;
@@ -574,10 +555,24 @@ static int forward(const sm_weights* w, const sm_forward_io* io, float* wsbase, 
         TRY(gemm(c, g));
     }
     if (w->mask_head_ffn || w->no_objectness) return SM_OK;  // no objectness on these paths (maskformer.py:246-249, :219-220)
-    TRY(linear(c, qd_a, D, w->ffn0_w, w->ffn0_s, w->ffn0_b, ws.O1, D, s.Mo, D, D, SM_EPI_RELU, nullptr, 0, S));
-    TRY(linear(c, ws.O1, D, w->ffn1_w, w->ffn1_s, w->ffn1_b, ws.O2, D, s.Mo, D, D, SM_EPI_RELU, nullptr, 0));
-    TRY(sm_rowdot_sigmoid_f32(ws.O2, w->ffn2_w, w->ffn2_b, io->objectness, (int)s.Mo, st));
-    return SM_OK;
+    TRY(ffn01(q_a, false));
+    return sm_rowdot_sigmoid_f32(ws.O2, w->ffn2_w, w->ffn2_b, io->objectness, (int)s.Mo, c.st);
+}
+
+}  // namespace
+
+static int forward(const sm_weights* w, const sm_forward_io* io, float* wsbase, hipStream_t st) {
+    const Shape s = make_shape(w, io->B, io->H, io->W);
+    const Ws ws = carve(s, wsbase);
+    const Ctx c = {w->gemm_mode >= 1, w->gemm_mode >= 2, st, w->gemm_mode == 3 ? 1 : 3};
+    float* tok = io->patch_tokens ? io->patch_tokens : ws.TOK;
+    float* QD = io->queries ? io->queries : ws.QD;
+    const Fwd f = {w, io, s, ws, c, tok, c.S ? ws.TOKs : tok, QD, c.S ? ws.QDs : QD};
+    TRY(f.tokens());
+    TRY(f.encoder());
+    if (io->attn_only || io->encoder_only) return SM_OK;  // attn_only: the encoder returned inside block 12
+    TRY(f.decoder());
+    return f.heads();
 }
 
 static int validate(const sm_weights* w, const sm_forward_io* io) {

@@ -293,30 +293,59 @@ def test_hip_graph_follows_new_weights():
     assert g.captures == 2 and g.failed is None
 
 
-@pytest.mark.parametrize("patch,B,H,W,nq,L,seed", [
-    (16, 1, 224, 224, 100, 3, 1),   # the reference's default n_queries, fewer decoder layers, 4 query blocks in cross-attention
-    (16, 5, 97, 211, 7, 1, 2),      # ragged image (zero-padded to 112 x 224), odd batch, single decoder layer
-    (8, 3, 72, 88, 20, 6, 3),       # ViT-S/8, 99 tokens (not a multiple of 4: literal up-sample + einsum order)
-    (16, 2, 32, 32, 20, 2, 4),      # four tokens per image: every GEMM / attention tile is mostly padding
-    (8, 1, 250, 130, 33, 4, 5),     # off-grid position embedding (bicubic), 33 queries = two query blocks
-])
-def test_forward_other_shapes_and_model_sizes_vs_oracle(patch, B, H, W, nq, L, seed):
+# (variant, gemm_mode, patch, B, H, W, nq, L, seed).  The decoder's two norm orders and the three heads have branches of their own;
+# the rows after the first five reach them at the smallest shapes where tiles are mostly padding or the token count is no multiple
+# of 4.  Every row's fp32 oracle is within 5e-5 of its fp64 evaluation and has |logit| <= 16 (pre-norm at 99 tokens: seed 3 gives
+# |logit| 19, hence seed 5).  Pre-norm runs in "w16" and "fp32": the two sides of every split-mode choice in the decoder.
+_EDGE_ROWS = [
+    ("post", None, 16, 1, 224, 224, 100, 3, 1),   # the reference's default n_queries, fewer decoder layers, 4 query blocks in cross-attention
+    ("post", None, 16, 5, 97, 211, 7, 1, 2),      # ragged image (zero-padded to 112 x 224), odd batch, single decoder layer
+    ("post", None, 8, 3, 72, 88, 20, 6, 3),       # ViT-S/8, 99 tokens (not a multiple of 4: literal up-sample + einsum order)
+    ("post", None, 16, 2, 32, 32, 20, 2, 4),      # four tokens per image: every GEMM / attention tile is mostly padding
+    ("post", None, 8, 1, 250, 130, 33, 4, 5),     # off-grid position embedding (bicubic), 33 queries = two query blocks
+] + [("pre", mode, *shape) for shape in [(16, 2, 32, 32, 20, 2, 4), (8, 3, 72, 88, 20, 3, 5), (16, 5, 97, 211, 7, 1, 2)]
+     for mode in ("w16", "fp32")] + [
+    ("ffn", None, 8, 3, 72, 88, 20, 2, 3),        # return_intermediate=True, use_binary_classifier=False: the ffn mask head
+    ("ffn", None, 16, 2, 32, 32, 20, 2, 4),
+    ("3d", None, 8, 3, 72, 88, 20, 2, 3),         # return_intermediate=False, use_binary_classifier=False: last layer, no sigmoid
+    ("3d", None, 16, 2, 32, 32, 20, 2, 4),
+]
+
+
+def _edge_id(row):  # the first five rows keep the ids they had before the variants existed
+    variant, mode, *shape = row
+    tag = "-".join(str(v) for v in shape)
+    return tag if variant == "post" else f"{variant}-{mode or 'default'}-{tag}"
+
+
+@pytest.mark.parametrize("variant,mode,patch,B,H,W,nq,L,seed", _EDGE_ROWS, ids=[_edge_id(r) for r in _EDGE_ROWS])
+def test_forward_other_shapes_and_model_sizes_vs_oracle(variant, mode, patch, B, H, W, nq, L, seed):
     """Edge shapes the bench never sees, calib weights, strict 1e-4 against the CPU oracle (fp32) on this box."""
-    sd = synthetic_state_dict(seed, "calib", n_queries=nq, patch_size=patch, n_decoder_layers=L)
-    m = MaskFormer(n_queries=nq, patch_size=patch, n_decoder_layers=L, return_intermediate=True, use_binary_classifier=True)
+    binary = variant in ("post", "pre")
+    sd = synthetic_state_dict(seed, "calib", n_queries=nq, patch_size=patch, n_decoder_layers=L, use_binary_classifier=binary)
+    m = MaskFormer(n_queries=nq, patch_size=patch, n_decoder_layers=L, normalize_before=variant == "pre",
+                   return_intermediate=variant != "3d", use_binary_classifier=binary, gemm_mode=mode)
     m.load_state_dict(sd, strict=True)
     m = m.to(DEV)
     x = torch.from_numpy(synthetic_images(900 + seed, (B, 3, H, W)))
     out = m(x.to(DEV), return_logits=True)
-    ref = O.forward(x, sd, patch, n_layers=L)
-    scale = ref["mask_logits"].abs().max().item()
-    d = (out["mask_logits"].cpu() - ref["mask_logits"]).abs().max().item()
-    print(f"\n P{patch} B={B} {H}x{W} nq={nq} L={L}: |logit|max={scale:.1f} hip-oracle32={d:.2e}")
-    ledger.record("forward_edge_shapes_calib", f"P{patch}_B{B}_{H}x{W}_nq{nq}_L{L}", {"logit_absmax": scale, "hip_minus_ref32": d,
-                                                                                   "rule": "hip-ref32 <= 1e-4"})
+    if variant == "3d":  # the 3-D path's mask_pred is the un-sigmoided einsum of the last layer
+        ref = O.forward_3d(x, sd, patch, n_layers=L)
+        got_logits, ref_logits = out["mask_pred"], ref["mask_pred"]
+    else:
+        ref = (O.forward_ffn_head(x, sd, patch, n_layers=L) if variant == "ffn"
+               else O.forward(x, sd, patch, n_layers=L, normalize_before=variant == "pre"))
+        got_logits, ref_logits = out["mask_logits"], ref["mask_logits"]
+    scale = ref_logits.abs().max().item()
+    d = (got_logits.cpu() - ref_logits).abs().max().item()
+    print(f"\n {variant}/{mode or 'default'} P{patch} B={B} {H}x{W} nq={nq} L={L}: |logit|max={scale:.2f} hip-oracle32={d:.2e}")
+    key = f"P{patch}_B{B}_{H}x{W}_nq{nq}_L{L}" + ("" if variant == "post" else f"_{variant}_{mode or 'default'}")
+    ledger.record("forward_edge_shapes_calib", key, {"logit_absmax": scale, "hip_minus_ref32": d, "rule": "hip-ref32 <= 1e-4"})
     assert out["mask_pred"].shape == ref["mask_pred"].shape
     assert scale <= 16.0 and d <= ABS_TOL
-    assert (out["objectness"].cpu() - ref["objectness"]).abs().max().item() <= 2e-5
+    assert ("objectness" in out) == binary
+    if binary:
+        assert (out["objectness"].cpu() - ref["objectness"]).abs().max().item() <= 2e-5
     assert (out["features"].cpu() - ref["features"]).abs().max().item() <= 5e-5
 
 
