@@ -519,6 +519,44 @@ int sm_predict_masks_f32(const sm_predict_args* args, const sm_bilateral_image* 
 int sm_rle_runs_packed_u8(const uint8_t* planes, const sm_bilateral_image* images_dev, const sm_bilateral_image* images_host,
                           int32_t B, int32_t* starts, int32_t cap, int32_t* info, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- salient objects: connected components of a run-coded mask (csrc/objects.hip) ------------------------------------------ */
+/* From the run boundaries the three functions above leave on the device (starts / info, positions q = x*H_b + y) to the objects of
+ * the mask: a foreground run is cut at the column ends it crosses, the vertical segments of neighbouring columns whose rows overlap
+ * (widened by one row at connectivity 8) are joined, and per component the area, the inclusive box, the coordinate sums and - when
+ * the low-resolution mask is given - the sum of the 8-bit soft values of its pixels are accumulated with integer atomics: no pixel
+ * plane is read or written and the output depends on the input alone.  Components of at least min_area pixels are ranked by (area
+ * descending, first ascending) and the first max_objects are written.  An image whose run list was truncated (info.count > cap) sets
+ * its overflow flag and reports no objects.  Nothing is allocated, copied or synchronised. */
+typedef struct sm_object {
+    int64_t sum_x, sum_y;            /* over the component's pixels: centroid = sum / area                                        */
+    int64_t mass;                    /* sum of (uint8)(clip(v,0,1)*255) over its pixels, v as sm_predict_masks_f32's soft plane;  */
+                                     /* 0 without args->masks                                                                     */
+    int32_t area, first;             /* first = the smallest y*W_b + x: the component's first pixel in row-major raster order     */
+    int32_t x0, y0, x1, y1;          /* inclusive box                                                                             */
+    int32_t flags, reserved;         /* bit 0: the box spans top to bottom row; bit 1: left to right column                       */
+} sm_object;
+#define SM_OBJ_SUMMARY_INTS 10 /* per image: components before filtering, objects written, segments, overflow flag, the whole mask's
+                                * box x0 y0 x1 y1 (x1 = -1: empty mask), its flags as sm_object.flags, its area */
+typedef struct sm_objects_args {
+    const int32_t* starts; const int32_t* info; int32_t cap; /* in: (B, cap) and (B, 2), as sm_predict_args                       */
+    const sm_bilateral_image* images;             /* DEVICE table: H and W are read                                               */
+    const float* masks; int64_t mask_stride_b;    /* the masks sm_predict_masks_f32 took, for mass; NULL: no mass (packed planes) */
+    const int32_t* best;                          /* (B) the picked query, with masks                                             */
+    sm_object* objects;                           /* out (B, max_objects), in rank order; unused slots are zero                   */
+    int32_t* summary;                             /* out (B, SM_OBJ_SUMMARY_INTS)                                                 */
+    int32_t* segments;                            /* out, or NULL: (B, seg_cap, 3) {start q, length, rank}, rank -1 = not kept;   */
+                                                  /* seg_cap = sm_mask_objects_seg_cap; image b's first summary[b][2] rows are    */
+                                                  /* written, the rows after them are left untouched                              */
+    void* workspace; size_t workspace_bytes;      /* sm_mask_objects_workspace_bytes, 256-B aligned                               */
+    int32_t B, mh, mw;
+    int32_t max_width;                            /* >= every W_b, <= 16384                                                       */
+    int32_t connectivity, min_area, max_objects;  /* 4 or 8; >= 0; 1 .. 64                                                        */
+    float scale;                                  /* as sm_predict_args                                                           */
+} sm_objects_args;
+int32_t sm_mask_objects_seg_cap(int32_t cap, int32_t max_width); /* rows per image of `segments`; 0: an argument out of range */
+size_t sm_mask_objects_workspace_bytes(int32_t B, int32_t cap, int32_t max_width); /* 0: an argument out of range */
+int sm_mask_objects(const sm_objects_args* args, const sm_bilateral_image* images_host, void* stream);
+
 /* ---- baseline JPEG decode, bit-identical to Pillow (libjpeg-turbo: JDCT_ISLOW, fancy up-sampling): host entropy decode + device
  * dequantise / IDCT / chroma up-sampling / YCbCr -> RGB (csrc/jpeg.hip, csrc/jpeg_host.h) ------------------------------------- */
 #define SM_JPEG_UNSUPPORTED 1 /* not an error: the file (or something inside it) is not for this decoder - decode it with Pillow */

@@ -46,19 +46,7 @@ __device__ __forceinline__ void split_pos(int q, int H, float inv_h, int& x, int
 }
 
 // ---- pixel sources: value of pixel (y, x) as 0 / 1 -------------------------------------------------------------------------
-template <typename Ptr>
-struct MaskSrc {  // the selected query's mask, up-sampled (Ptr: LDS or global floats)
-    Ptr m;
-    int mh, mw;
-    float sy, sx;
-    __device__ __forceinline__ float value(int y, int x) const {
-        const UpIdx uy = up_index(y, sy, mh), ux = up_index(x, sx, mw);
-        // a pixel outside the up-sampled plane (H_b > scale * mh) is 0, as in eval_upsample_selected_native_kernel
-        return uy.i0 < mh && ux.i0 < mw ? up_sample(m, mw, uy, ux) : 0.f;
-    }
-    __device__ __forceinline__ bool operator()(int y, int x) const { return value(y, x) > 0.5f; }
-};
-
+// (MaskSrc, the selected query's mask up-sampled, comes from upsample.h)
 struct ByteSrc {  // a packed row-major 0 / non-zero plane
     const unsigned char* __restrict__ p;
     int W;
@@ -213,8 +201,7 @@ __global__ __launch_bounds__(PR_THREADS) void predict_planes_kernel(sm_predict_a
             if (p >= 0 && p < npx) {
                 const float v = src.value(y, x);
                 bin |= (v > 0.5f ? 1u : 0u) << (8 * e);
-                // (mask * 255).astype(np.uint8) after clip(0, 1): truncation
-                sft |= (unsigned)(int)(fminf(fmaxf(v, 0.f), 1.f) * 255.0f) << (8 * e);
+                sft |= up_soft_u8(v) << (8 * e);
                 if (++x == im.W) { x = 0; ++y; }
             }
         }

@@ -35,4 +35,21 @@ __device__ __forceinline__ float up_sample(const float* __restrict__ m, int mw, 
     return __builtin_fmaf(top, uy.l0, bot * uy.l1);
 }
 
+// the selected query's mask, up-sampled: value of pixel (y, x) (Ptr: LDS or global floats)
+template <typename Ptr>
+struct MaskSrc {
+    Ptr m;
+    int mh, mw;
+    float sy, sx;
+    __device__ __forceinline__ float value(int y, int x) const {
+        const UpIdx uy = up_index(y, sy, mh), ux = up_index(x, sx, mw);
+        // a pixel outside the up-sampled plane (H_b > scale * mh) is 0, as in eval_upsample_selected_native_kernel
+        return uy.i0 < mh && ux.i0 < mw ? up_sample(m, mw, uy, ux) : 0.f;
+    }
+    __device__ __forceinline__ bool operator()(int y, int x) const { return value(y, x) > 0.5f; }
+};
+
+// the 8-bit soft value of a pixel: (mask * 255).astype(np.uint8) after clip(0, 1), truncating
+__device__ __forceinline__ unsigned up_soft_u8(float v) { return (unsigned)(int)(fminf(fmaxf(v, 0.f), 1.f) * 255.0f); }
+
 }  // namespace sm

@@ -135,6 +135,22 @@ class PredictArgs(C.Structure):
                 ("max_pixels", C.c_int32), ("scale", C.c_float)]
 
 
+class Object(C.Structure):
+    _fields_ = [("sum_x", C.c_int64), ("sum_y", C.c_int64), ("mass", C.c_int64), ("area", C.c_int32), ("first", C.c_int32),
+                ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+OBJ_SUMMARY_INTS = 10
+OBJ_MAX_OBJECTS, OBJ_MAX_WIDTH = 64, 16384
+
+
+class ObjectsArgs(C.Structure):
+    _fields_ = [("starts", fp), ("info", fp), ("cap", C.c_int32), ("images", fp), ("masks", fp), ("mask_stride_b", C.c_int64),
+                ("best", fp), ("objects", fp), ("summary", fp), ("segments", fp), ("workspace", fp), ("workspace_bytes", C.c_size_t),
+                ("B", C.c_int32), ("mh", C.c_int32), ("mw", C.c_int32), ("max_width", C.c_int32), ("connectivity", C.c_int32),
+                ("min_area", C.c_int32), ("max_objects", C.c_int32), ("scale", C.c_float)]
+
+
 class JpegInfo(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("components", C.c_int32), ("h_samp", C.c_int32 * 4),
                 ("v_samp", C.c_int32 * 4), ("supported", C.c_int32), ("sampling", C.c_int32), ("mcus_x", C.c_int32),
@@ -225,6 +241,9 @@ SYMBOLS = {
     "sm_predict_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "sm_predict_masks_f32": (C.c_int, [C.POINTER(PredictArgs), fp, fp]),
     "sm_rle_runs_packed_u8": (C.c_int, [fp, fp, fp, C.c_int32, fp, C.c_int32, fp, fp, C.c_size_t, fp]),
+    "sm_mask_objects_seg_cap": (C.c_int32, [C.c_int32, C.c_int32]),
+    "sm_mask_objects_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "sm_mask_objects": (C.c_int, [C.POINTER(ObjectsArgs), fp, fp]),
     "sm_jpeg_probe": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(JpegInfo)]),
     "sm_jpeg_entropy_decode": (C.c_int, [C.c_char_p, C.c_size_t, fp, C.c_size_t, fp, C.POINTER(JpegInfo)]),
     "sm_jpeg_decode_batch_u8": (C.c_int, [fp, fp, C.c_int32, fp, fp, fp, fp]),

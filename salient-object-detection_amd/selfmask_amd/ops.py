@@ -511,12 +511,147 @@ def _runs_to_rle(info, starts, shapes):
     return out
 
 
+class ObjectOptions:
+    """what ``predict_masks(..., objects=)`` / ``rle_runs_packed_async(..., objects=)`` take (or a dict of the same keys):
+    ``connectivity`` 4 or 8, ``min_area`` drops smaller components, the ``max_objects`` (1 .. 64) largest are returned, ``masks``:
+    one COCO uncompressed RLE per returned object"""
+
+    def __init__(self, connectivity: int = 8, min_area: int = 0, max_objects: int = 16, masks: bool = True):
+        self.connectivity, self.min_area, self.max_objects, self.masks = int(connectivity), int(min_area), int(max_objects), bool(masks)
+        if self.connectivity not in (4, 8):
+            raise ValueError(f"objects: connectivity={connectivity!r} (4 or 8)")
+        if not 1 <= self.max_objects <= N.OBJ_MAX_OBJECTS:
+            raise ValueError(f"objects: max_objects={max_objects!r} (1 .. {N.OBJ_MAX_OBJECTS})")
+        if self.min_area < 0:
+            raise ValueError(f"objects: min_area={min_area!r}")
+
+    @staticmethod
+    def of(o):
+        if o is None or isinstance(o, ObjectOptions):
+            return o
+        return ObjectOptions(**dict(o))
+
+
+def _spans(flags: int):
+    """the two ``remove_long_masks`` tests of the reference's ``filter_masks`` on a box"""
+    return {"top_bottom": bool(flags & 1), "left_right": bool(flags & 2)}
+
+
+def batch_segments_to_rles(seg, n_segments, n_objects, shapes):
+    """seg (B, >= max n_segments, 3) rows {start q, length, rank} ascending in q, the first n_segments[b] of image b used -> per image
+    one COCO uncompressed RLE per rank 0 .. n_objects[b] - 1; segments of one object that abut (across a column end) merge into one
+    run.  One pass over the tables of the whole batch."""
+    import numpy as np
+    B, K = len(shapes), max(max(n_objects, default=0), 1)
+    used = (np.arange(seg.shape[1])[None, :] < np.asarray(n_segments)[:, None]) & (seg[:, :, 2] >= 0)
+    image = np.nonzero(used)[0]
+    rows = seg[used]
+    key = image * K + rows[:, 2]
+    order = np.argsort(key, kind="stable")  # by image and rank, ascending in q inside an object
+    rows, key = rows[order], key[order]
+    s = rows[:, 0].astype(np.int64)
+    e = s + rows[:, 1]
+    if not len(rows):
+        return [[] for _ in shapes]
+    joined = (s[1:] == e[:-1]) & (key[1:] == key[:-1])
+    opens, closes = np.concatenate([[True], ~joined]), np.concatenate([~joined, [True]])
+    bounds = np.stack([s[opens], e[closes]], axis=1).reshape(-1)  # run starts and ends, interleaved
+    counts = np.diff(bounds, prepend=0)
+    at = 2 * np.searchsorted(key[opens], np.arange(B * K + 1))  # where each object's bounds begin
+    first = at[:-1][at[:-1] < at[1:]]  # (slots without an object are empty)
+    counts[first] = bounds[first]  # an object's first count is its first start
+    counts, bounds, at = counts.tolist(), bounds.tolist(), at.tolist()
+    out = []
+    for b, (H, W) in enumerate(shapes):
+        rles = []
+        for k in range(n_objects[b]):
+            lo, hi = at[b * K + k], at[b * K + k + 1]
+            c = counts[lo:hi]
+            if bounds[hi - 1] != H * W:  # unless the object holds the last pixel, zeros close the code
+                c.append(H * W - bounds[hi - 1])
+            rles.append({"size": [int(H), int(W)], "counts": c})
+        out.append(rles)
+    return out
+
+
+def segments_to_rles(seg, n_objects: int, size):
+    """``batch_segments_to_rles`` for one image: seg (n, 3)"""
+    return batch_segments_to_rles(seg[None], [len(seg)], [n_objects], [size])[0]
+
+
+class _PendingObjects:
+    """sm_mask_objects queued behind the kernels that wrote ``starts`` / ``info``, its small outputs on their way into page-locked
+    memory; ``result()`` waits for those copies alone"""
+
+    def __init__(self, table, opts, starts, info, cap, mask_src=None):
+        import ctypes
+        import numpy as np
+        self.table, self.opts = table, opts
+        dev = starts.device
+        lib = N.load()
+        B, K = table.B, opts.max_objects
+        max_width = max(w for _, w in table.shapes)
+        wsb = lib.sm_mask_objects_workspace_bytes(B, cap, max_width)
+        if wsb == 0:
+            raise ValueError(f"objects: unsupported shape (an image wider than {N.OBJ_MAX_WIDTH} pixels?)")
+        self._ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        self._objects = torch.empty(B * K * ctypes.sizeof(N.Object), dtype=torch.uint8, device=dev)
+        self._summary = torch.empty((B, N.OBJ_SUMMARY_INTS), dtype=torch.int32, device=dev)
+        self._segments = torch.empty((B, lib.sm_mask_objects_seg_cap(cap, max_width), 3), dtype=torch.int32, device=dev) if opts.masks else None
+        a = N.ObjectsArgs()
+        a.starts, a.info, a.cap, a.images = starts.data_ptr(), info.data_ptr(), cap, table.dev.data_ptr()
+        self.scored = mask_src is not None
+        if self.scored:
+            masks, best, scale = mask_src
+            a.masks, a.mask_stride_b, a.best = masks.data_ptr(), masks.stride(0), best.data_ptr()
+            a.mh, a.mw, a.scale = masks.shape[2], masks.shape[3], scale
+        a.objects, a.summary, a.segments = self._objects.data_ptr(), self._summary.data_ptr(), _ptr(self._segments)
+        a.workspace, a.workspace_bytes = self._ws.data_ptr(), wsb
+        a.B, a.max_width = B, max_width
+        a.connectivity, a.min_area, a.max_objects = opts.connectivity, opts.min_area, K
+        N.check(lib.sm_mask_objects(a, ctypes.addressof(table.host), torch.cuda.current_stream(dev).cuda_stream), "sm_mask_objects")
+        self._objects_h = torch.empty(self._objects.shape, dtype=torch.uint8, pin_memory=True)
+        self._objects_h.copy_(self._objects, non_blocking=True)
+        self._summary_h = torch.empty(self._summary.shape, dtype=torch.int32, pin_memory=True)
+        self._summary_h.copy_(self._summary, non_blocking=True)
+        self._done = torch.cuda.Event()
+        self._done.record(torch.cuda.current_stream(dev))
+        self._dtype = np.dtype([(n, np.int64 if t is ctypes.c_int64 else np.int32) for n, t in N.Object._fields_])
+
+    def result(self):
+        """-> per image {"size", "n_components", "bbox", "spans", "objects": [...]} (boxes [x, y, w, h])"""
+        self._done.synchronize()
+        K = self.opts.max_objects
+        objs = self._objects_h.numpy().view(self._dtype).reshape(self.table.B, K)
+        f = {n: objs[n].tolist() for n in self._dtype.names}  # plain ints from here on
+        summ = self._summary_h.numpy()
+        assert not summ[:, 3].any(), "objects of a truncated run list (the caller finds the runs again first)"
+        all_rles, most = None, int(summ[:, 2].max(initial=0))
+        if self._segments is not None and most:
+            seg = _used_columns_host(self._segments.view(self.table.B, -1), 3 * most)
+            all_rles = batch_segments_to_rles(seg.reshape(self.table.B, most, 3), summ[:, 2], summ[:, 1].tolist(), self.table.shapes)
+        out = []
+        for b, ((H, W), row) in enumerate(zip(self.table.shapes, summ.tolist())):
+            ncomp, kept, nseg, _, x0, y0, x1, y1, flags, _area = row
+            rles = all_rles[b] if all_rles else [None] * kept
+            items = []
+            for k in range(kept):
+                area = f["area"][b][k]
+                items.append({"bbox": [f["x0"][b][k], f["y0"][b][k], f["x1"][b][k] - f["x0"][b][k] + 1, f["y1"][b][k] - f["y0"][b][k] + 1],
+                              "area": area, "centroid": (f["sum_x"][b][k] / area, f["sum_y"][b][k] / area),
+                              "score": f["mass"][b][k] / (255 * area) if self.scored else None,
+                              "first": f["first"][b][k], "spans": _spans(f["flags"][b][k]), "rle": rles[k]})
+            out.append({"size": [H, W], "n_components": ncomp, "bbox": [x0, y0, x1 - x0 + 1, y1 - y0 + 1] if x1 >= 0 else None,
+                        "spans": _spans(flags), "objects": items})
+        return out
+
+
 class PendingPredictions:
     """The finish of one batch (``predict_masks``), queued on the current stream: ``result()`` waits for THAT batch's copies only.
     The inputs are kept until then - on overflow of ``cap`` the runs are found once more with room for the longest code - so the
     caller must not let the stream overwrite them (a replayed graph's static outputs) before asking."""
 
-    def __init__(self, mask_pred_last, objectness_last, table, scale, rle, binary, soft, cap):
+    def __init__(self, mask_pred_last, objectness_last, table, scale, rle, binary, soft, cap, objects=None):
         B, nq, mh, mw = mask_pred_last.shape
         dev = mask_pred_last.device
         self._in = (mask_pred_last, objectness_last, table, float(scale))
@@ -524,13 +659,16 @@ class PendingPredictions:
         self.best = torch.empty(B, dtype=torch.int32, device=dev)
         self.binary = torch.empty(table.n_pixels, dtype=torch.uint8, device=dev) if binary else None
         self.soft = torch.empty(table.n_pixels, dtype=torch.uint8, device=dev) if soft else None
-        self._starts = self._info = self._ws = None
-        if rle:
+        self._starts = self._info = self._ws = self._objects = None
+        self._opts, self._rle = objects, rle
+        if rle or objects is not None:  # the objects are found on the runs
             self._starts = torch.empty((B, self.cap), dtype=torch.int32, device=dev)
             self._info = torch.empty((B, 2), dtype=torch.int32, device=dev)
         self._launch(self._starts, self._info, self.cap, self.binary, self.soft)
         # best | info in one page-locked row per image; the planes in one buffer each
-        small = self.best[:, None] if not rle else torch.cat([self.best[:, None], self._info], dim=1)
+        small = self.best[:, None] if self._starts is None else torch.cat([self.best[:, None], self._info], dim=1)
+        if objects is not None:
+            self._objects = _PendingObjects(table, objects, self._starts, self._info, self.cap, (mask_pred_last, self.best, float(scale)))
         self._small_h = torch.empty(small.shape, dtype=torch.int32, pin_memory=True)
         self._small_h.copy_(small, non_blocking=True)
         self._planes_h = {}
@@ -565,8 +703,8 @@ class PendingPredictions:
                 "sm_predict_masks_f32")
 
     def result(self) -> dict:
-        """-> {"best": [query index], "rle": [COCO uncompressed RLE dict], "binary" / "soft": [(H_b, W_b) uint8 array]} (the keys
-        asked for)"""
+        """-> {"best": [query index], "rle": [COCO uncompressed RLE dict], "binary" / "soft": [(H_b, W_b) uint8 array], "objects":
+        [the dict of ``_PendingObjects.result``]} (the keys asked for)"""
         self._done.synchronize()
         small = self._small_h.numpy()
         out = {"best": small[:, 0].tolist()}
@@ -577,7 +715,12 @@ class PendingPredictions:
             if longest > self.cap:  # noise-like masks: once more, with room for the longest code
                 starts = torch.empty((info.shape[0], longest), dtype=torch.int32, device=starts.device)
                 self._launch(starts, self._info, longest, None, None)
-            out["rle"] = _runs_to_rle(info, _used_columns_host(starts, longest), self.table.shapes)
+                if self._objects is not None:  # and the objects with them
+                    self._objects = _PendingObjects(self.table, self._opts, starts, self._info, longest, (self._in[0], self.best, self._in[3]))
+            if self._rle:
+                out["rle"] = _runs_to_rle(info, _used_columns_host(starts, longest), self.table.shapes)
+            if self._objects is not None:
+                out["objects"] = self._objects.result()
         for name, h in self._planes_h.items():
             flat = h.numpy()
             out[name] = [flat[o:o + hh * ww].reshape(hh, ww) for o, (hh, ww) in zip(self.table.px_off, self.table.shapes)]
@@ -586,27 +729,32 @@ class PendingPredictions:
 
 
 def predict_masks(mask_pred_last: torch.Tensor, objectness_last: torch.Tensor, table, scale: float = 0.0, rle: bool = True,
-                  binary: bool = False, soft: bool = False, cap: int = 8192) -> PendingPredictions:
+                  binary: bool = False, soft: bool = False, cap: int = 8192, objects=None) -> PendingPredictions:
     """The predictor's fused finish (sm_predict_masks_f32), without waiting: mask_pred_last (B, nq, mh, mw) probabilities (any batch
     stride), objectness_last (B, nq), ``table`` a PackedImages / MixedBatch with the output size of every image.  The arg-max query's
     mask, up-sampled as ``evaluate_masks`` up-samples it (``scale`` as there), thresholded at 0.5: ``rle`` its COCO run-length code,
-    ``binary`` / ``soft`` packed uint8 planes (0/1; clip(v, 0, 1) * 255 truncated).  ``.best`` (B,) int32 stays on the device."""
+    ``binary`` / ``soft`` packed uint8 planes (0/1; clip(v, 0, 1) * 255 truncated).  ``.best`` (B,) int32 stays on the device.
+    ``objects`` (an ``ObjectOptions`` or a dict of its keys): sm_mask_objects is queued right behind the runs and ``result()`` gains
+    "objects" - per image the mask's connected components with box, area, centroid, score = the mean of the soft values, first raster
+    pixel and, on request, an RLE each; ``None``: nothing more is launched."""
     _dev(mask_pred_last, objectness_last)
     B, nq, mh, mw = mask_pred_last.shape
     assert mask_pred_last.stride(3) == 1 and mask_pred_last.stride(2) == mw and mask_pred_last.stride(1) == mh * mw
     assert objectness_last.shape == (B, nq) and objectness_last.stride(1) == 1 and table.B == B
-    return PendingPredictions(mask_pred_last, objectness_last, table, scale, rle, binary, soft, max(1, min(int(cap), table.max_pixels)))
+    return PendingPredictions(mask_pred_last, objectness_last, table, scale, rle, binary, soft, max(1, min(int(cap), table.max_pixels)),
+                              ObjectOptions.of(objects))
 
 
 class PendingPackedRuns:
     """Run-length codes of packed 0/1 planes of different sizes (``rle_runs_packed_async``): ``result()`` -> one dict per image."""
 
-    def __init__(self, planes: torch.Tensor, table, cap: int):
-        self.planes, self.table, self.cap = planes, table, int(cap)
+    def __init__(self, planes: torch.Tensor, table, cap: int, objects=None):
+        self.planes, self.table, self.cap, self._opts = planes, table, int(cap), objects
         dev = planes.device
         self._info = torch.empty((table.B, 2), dtype=torch.int32, device=dev)
         self._ws = None
         self._starts = self._launch(self.cap)
+        self._objects = _PendingObjects(table, objects, self._starts, self._info, self.cap) if objects is not None else None
         self._info_h = torch.empty((table.B, 2), dtype=torch.int32, pin_memory=True)
         self._info_h.copy_(self._info, non_blocking=True)
         self._done = torch.cuda.Event()
@@ -631,13 +779,19 @@ class PendingPackedRuns:
         self._done.synchronize()
         info = self._info_h.numpy()
         longest = int(info[:, 0].max(initial=0))
-        starts = self._launch(longest) if longest > self.cap else self._starts
-        return _runs_to_rle(info, _used_columns_host(starts, longest), self.table.shapes)
+        starts = self._starts
+        if longest > self.cap:
+            starts = self._launch(longest)
+            if self._objects is not None:
+                self._objects = _PendingObjects(self.table, self._opts, starts, self._info, longest)
+        rles = _runs_to_rle(info, _used_columns_host(starts, longest), self.table.shapes)
+        return rles if self._objects is None else (rles, self._objects.result())
 
 
-def rle_runs_packed_async(planes: torch.Tensor, table, cap: int = 8192) -> PendingPackedRuns:
+def rle_runs_packed_async(planes: torch.Tensor, table, cap: int = 8192, objects=None) -> PendingPackedRuns:
     """Packed 0/1 uint8 planes (image b's H_b x W_b bytes at ``table.px_off[b]`` - the mixed bilateral solver's binary output) ->
-    their run-length codes, without waiting (``.result()``): ``voting.rle_runs_async`` for images of different sizes."""
+    their run-length codes, without waiting (``.result()``): ``voting.rle_runs_async`` for images of different sizes.  With
+    ``objects`` (as ``predict_masks``) ``result()`` is (codes, objects per image); a plane has no soft values, so ``score`` is None."""
     if not planes.is_cuda or planes.dtype != torch.uint8 or not planes.is_contiguous() or planes.numel() < table.n_pixels:
         raise RuntimeError("rle_runs_packed_async takes the packed uint8 planes of the batch on a HIP device (no CPU fallback)")
-    return PendingPackedRuns(planes, table, max(1, min(int(cap), table.max_pixels)))
+    return PendingPackedRuns(planes, table, max(1, min(int(cap), table.max_pixels)), ObjectOptions.of(objects))

@@ -2,6 +2,7 @@
 file's own size and at device throughput.
 
     SaliencyPredictor(network)(p_images, output="rle")  -> {file name: COCO uncompressed RLE dict}
+    SaliencyPredictor(network)(p_images, output="objects", objects={"min_area": 64})  -> {file name: the mask's objects}
 
 The sibling of ``Evaluator.__call__`` (which needs a ground truth per image and returns metrics, not masks) and of
 ``MaskGenerator.__call__`` (pseudo-masks from clustering, not from the decoder): headers probed and checked before anything is
@@ -20,9 +21,10 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 import torch
 
-OUTPUTS = ("rle", "binary", "soft")
+OUTPUTS = ("rle", "binary", "soft", "objects")
 DEFAULT_CAP = 8192       # run boundaries stored per image before the retry, as voting.rle_runs_async
 MAX_PIXELS = 1 << 22     # sm_predict_masks_f32's largest image
+MAX_OBJECTS_WIDTH = 16384  # sm_mask_objects' widest image
 DECODES = ("host", "device")
 
 
@@ -131,6 +133,9 @@ class SaliencyPredictor:
                 raise ValueError(f"SaliencyPredictor: {p} is not a readable image ({type(e).__name__}: {e}); nothing was run") from e
             if hw[0] < 1 or hw[1] < 1 or hw[0] * hw[1] > MAX_PIXELS:
                 raise ValueError(f"SaliencyPredictor: {p} is {hw[0]} x {hw[1]}: 1 .. {MAX_PIXELS} pixels per image; nothing was run")
+            if "objects" in outputs and hw[1] > MAX_OBJECTS_WIDTH:
+                raise ValueError(f"SaliencyPredictor: {p} is {hw[1]} pixels wide: objects are found in images of at most "
+                                 f"{MAX_OBJECTS_WIDTH} columns; nothing was run")
             sizes.append((int(hw[0]), int(hw[1])))
         return self._batches(p_images, names, sizes, img_size)
 
@@ -145,9 +150,11 @@ class SaliencyPredictor:
 
     @torch.no_grad()
     def __call__(self, p_images: Sequence[str], img_size: Optional[int] = None, scale_factor: int = 2, output: str = "rle",
-                 refine: Optional[str] = None, comm=None) -> Dict[str, object]:
+                 refine: Optional[str] = None, comm=None, objects=None) -> Dict[str, object]:
         """-> {file name: COCO uncompressed RLE dict (``output="rle"``) | (H, W) uint8 array: 0/1 (``"binary"``) or
-        clip(p, 0, 1) * 255 truncated (``"soft"``)}, in list order; ``.last_best`` {file name: query index}.
+        clip(p, 0, 1) * 255 truncated (``"soft"``) | the mask's connected components (``"objects"``: the dict of
+        ``ops.predict_masks(objects=)`` + "best"; ``objects``: an ``ops.ObjectOptions`` or a dict of its keys)}, in list order;
+        ``.last_best`` {file name: query index}.
         ``img_size=None``: native resolution in token-grid buckets, the mask up-sampled by ``patch // scale_factor`` and cropped -
         the evaluator's reference mode; ``img_size=S``: inputs resized to S x S, the mask resized to the file's own size.
         ``refine="bilateral"``: the mask the metrics would score goes through the bilateral solver against the decoded pixels (native:
@@ -167,17 +174,19 @@ class SaliencyPredictor:
             merged = gather_dicts(mine["rle"], comm, self.device)
             self.last_best = {n: best[n] for n in names}
             return {n: merged[n] for n in names}  # the list's order, whatever the sharding
+        if output == "objects":
+            return self._run(plan[0], img_size, scale_factor, (output,), refine, plan=plan, objects=objects)[output]
         return self._run(plan[0], img_size, scale_factor, (output,), refine, plan=plan)[output]
 
     # ---- one rank's files -----------------------------------------------------------------------------------------------------
-    def _finish(self, out, shapes, u8, scale, img_size, outputs, refine):
+    def _finish(self, out, shapes, u8, scale, img_size, outputs, refine, objects=None):
         """the forward's outputs of one batch -> a pending result (``.result()`` -> {"best", "rle" / "binary" / "soft"})"""
         from . import ops
         mask_pred, obj = out["mask_pred"], out["objectness"]
         if mask_pred.dim() == 5:  # last decoder layer
             mask_pred, obj = mask_pred[:, -1], obj[:, -1]
         obj = obj.squeeze(-1)
-        want = dict(rle="rle" in outputs, binary="binary" in outputs, soft="soft" in outputs, cap=self.cap)
+        want = dict(rle="rle" in outputs, binary="binary" in outputs, soft="soft" in outputs, cap=self.cap, objects=objects)
         if not refine:
             return ops.predict_masks(mask_pred, obj, ops.PackedImages(shapes, self.device), scale, **want)
         B = mask_pred.shape[0]
@@ -190,7 +199,7 @@ class SaliencyPredictor:
             rows[:, 14] = head.best.float()
             target = ops.upsample_selected_native(mask_pred, rows, mb, scale, "pick")
             _, binary, _ = bilateral_solver_mixed_packed(u8, target, mb)
-            return _Refined(head, ops.rle_runs_packed_async(binary, mb, self.cap) if want["rle"] else None,
+            return _Refined(head, ops.rle_runs_packed_async(binary, mb, self.cap, objects) if want["rle"] or objects is not None else None,
                             binary if want["binary"] else None, mb)
         from .bilateral_solver import bilateral_solver_batch_device
         head = ops.predict_masks(mask_pred, obj, ops.PackedImages([(img_size, img_size)] * B, self.device), 0.0, rle=False)
@@ -203,11 +212,13 @@ class SaliencyPredictor:
                                  ops.PackedImages(shapes, self.device), 0.0, **want)
         return _Refined(head, tail, None, None)
 
-    def _run(self, p_images, img_size, scale_factor, outputs, refine, plan=None) -> Dict[str, Dict[str, object]]:
+    def _run(self, p_images, img_size, scale_factor, outputs, refine, plan=None, objects=None) -> Dict[str, Dict[str, object]]:
         from .graphs import GraphedForward
         from .pipeline import PrefetchingLoader, preprocess_on_device
         from .streams import StreamRing
         p_images, names, sizes, batches = plan if plan is not None else self._plan(p_images, img_size, outputs, refine)
+        from .ops import ObjectOptions
+        objects = (ObjectOptions.of(objects) or ObjectOptions()) if "objects" in outputs else None
         results = {o: {} for o in outputs}
         best: Dict[str, int] = {}
         self.last_best = best
@@ -238,8 +249,8 @@ class SaliencyPredictor:
             res = pend.result()
             best.update(zip(bnames, res["best"]))
             for o in outputs:
-                for n, v in zip(bnames, res[o]):
-                    results[o][n] = v if o == "rle" else v.copy()
+                for n, v, q in zip(bnames, res[o], res["best"]):
+                    results[o][n] = v if o == "rle" else {**v, "best": q} if o == "objects" else v.copy()
 
         from .decode_pool import default_workers
         avg = max(1, len(p_images) // len(batches))  # buckets are often smaller than batch_size: keep every decode worker busy
@@ -265,7 +276,7 @@ class SaliencyPredictor:
                         x = preprocess_on_device(shapes, img_size, device, packed=packed, return_u8=bool(refine))
                     x, u8 = x if refine else (x, None)
                     assert [sizes[i] for i in idx] == [tuple(s) for s in shapes], "a file's header and its decoded size differ"
-                    pending.append(([names[i] for i in idx], self._finish(graphed(x), shapes, u8, scale, img_size, outputs, refine)))
+                    pending.append(([names[i] for i in idx], self._finish(graphed(x), shapes, u8, scale, img_size, outputs, refine, objects)))
                 if len(pending) >= len(ring.streams):
                     settle()
             while pending:
@@ -296,9 +307,16 @@ class _Refined:
         out = {"best": self.head.result()["best"]}
         if self.table is None:  # resized mode: ``runs`` is the second finish, with whatever was asked for
             out.update({k: v for k, v in self.runs.result().items() if k != "best"})
+            for im in out.get("objects", ()):  # a solver's binary mask has no soft values to score
+                for o in im["objects"]:
+                    o["score"] = None
             return out
         if self.runs is not None:
-            out["rle"] = self.runs.result()
+            res = self.runs.result()
+            if isinstance(res, tuple):  # the packed planes' codes and their objects
+                out["rle"], out["objects"] = res
+            else:
+                out["rle"] = res
         if self._binary_h is not None:
             self._done.synchronize()
             flat = self._binary_h.numpy()
@@ -344,6 +362,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--batch_size", type=int, default=64)
     ap.add_argument("--refine", type=str, default=None, choices=["bilateral"])
     ap.add_argument("--png_dir", type=str, default=None, help="also write the soft maps as 8-bit PNGs into this directory")
+    ap.add_argument("--objects_out", type=str, default=None, help="also write the masks' objects (boxes, areas, centroids, scores, "
+                    "per-object RLE) as JSON: {file name: {...}}")
+    ap.add_argument("--connectivity", type=int, default=8, choices=[4, 8])
+    ap.add_argument("--min_area", type=int, default=0, help="objects of fewer pixels are dropped")
+    ap.add_argument("--max_objects", type=int, default=16, help="the largest objects kept per image (1 .. 64)")
     ap.add_argument("--decode", type=str, default="host", choices=list(DECODES),
                     help="device: baseline JPEGs are entropy-decoded on host threads and finished on the GPU (same pixels as Pillow)")
     ap.add_argument("--gpu_id", type=int, default=0)
@@ -364,13 +387,18 @@ def main(argv=None):
     load_checkpoint(model, args.p_state_dict)
     model = model.to(device).eval()
     pred = SaliencyPredictor(model, device=device, batch_size=args.batch_size, decode=args.decode)
-    outputs = ("rle", "soft") if args.png_dir else ("rle",)
-    res = pred._run(list_images(args.images), args.img_size, getattr(cfg, "scale_factor", 2), outputs, args.refine)
+    outputs = ("rle",) + (("soft",) if args.png_dir else ()) + (("objects",) if args.objects_out else ())
+    objects = dict(connectivity=args.connectivity, min_area=args.min_area, max_objects=args.max_objects) if args.objects_out else None
+    res = pred._run(list_images(args.images), args.img_size, getattr(cfg, "scale_factor", 2), outputs, args.refine, objects=objects)
     with open(args.out, "w") as f:
         json.dump(res["rle"], f, separators=(",", ":"))
+    if args.objects_out:
+        with open(args.objects_out, "w") as f:
+            json.dump(res["objects"], f, separators=(",", ":"))
     if args.png_dir:
         write_pngs(res["soft"], args.png_dir)
-    print(f"{len(res['rle'])} masks -> {args.out}" + (f", PNGs -> {args.png_dir}" if args.png_dir else ""))
+    print(f"{len(res['rle'])} masks -> {args.out}" + (f", PNGs -> {args.png_dir}" if args.png_dir else "") +
+          (f", objects -> {args.objects_out}" if args.objects_out else ""))
     return res
 
 
