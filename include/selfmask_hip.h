@@ -557,6 +557,35 @@ int32_t sm_mask_objects_seg_cap(int32_t cap, int32_t max_width); /* rows per ima
 size_t sm_mask_objects_workspace_bytes(int32_t B, int32_t cap, int32_t max_width); /* 0: an argument out of range */
 int sm_mask_objects(const sm_objects_args* args, const sm_bilateral_image* images_host, void* stream);
 
+/* ---- the serving response's images (SelfMaskInference.predict, app.py:296-311; csrc/present.hip): the selected low-resolution mask ->
+ * 8 bits -> Pillow's LANCZOS resize to the upload's size (mask_out), and that through a 256-entry RGBA colour table, Image.blend with
+ * the upload and ImageEnhance.Brightness (heat_out) - bit-identical to Pillow.  Per image b:
+ *   m8    = (uint8)(m * 255.0f), truncating, NaN -> 0 (masks hold values in [0, 1]: what the serving selection leaves)
+ *   pass  = clip8((sum m8 * tap + 2^21) >> 22): horizontal mw -> W_b into a uint8 intermediate, then vertical mh -> H_b on it; a pass
+ *           whose lengths agree is skipped (ks = 0), as Pillow skips it.  Taps: Pillow's precompute_coeffs + normalize_coeffs_8bpc
+ *           for the Lanczos-3 filter, computed by the host (selfmask_amd/present.py: pil_lanczos_coeffs)
+ *   heat  = per channel of (R, G, B, 255) of the upload against lut_rgba[mask byte]: blend = (uint8)(o + alpha * (l - o)), then
+ *           t = d + brightness * (blend - d) with d = 0 (R, G, B) / the blend's alpha (A), t <= 0 -> 0, t >= 255 -> 255, else
+ *           truncated; every fp32 multiply and add rounded on its own, as Pillow's Blend.c
+ * mask_out: image b's H_b x W_b bytes at + px_off; heat_out: its RGBA pixels at + 4*px_off bytes; either may be NULL and is then neither
+ * computed nor stored (rgb and lut_rgba are needed with heat_out only).  mask_out is 4-byte, heat_out 16-byte aligned.
+ * Nothing is allocated, copied or synchronised; the grids are sized from images_host (the same table on the host), the kernels read
+ * images_dev; images of different sizes go in one call and every image's bytes are those of its own single call.  Limits: B <= 65535,
+ * 1 <= mh, mw <= 512, H_b * W_b <= 2^24, 0 <= blend_alpha <= 1. */
+typedef struct sm_present_image {
+    int64_t img_off;   /* bytes: this image's (H, W, 3) uint8 RGB inside `rgb` (sm_pre_image.off fits as it is)                    */
+    int64_t px_off;    /* elements: this image's H*W block inside mask_out; heat_out uses 4*px_off bytes                           */
+    int32_t H, W;
+    int32_t coef_x, coef_y;  /* int32 offsets into `coef`: [out][2] (first input index, tap count), then [out][ks] taps             */
+    int32_t ksx, ksy;        /* 0 = that pass is skipped (W == mw / H == mh), as Pillow skips it                                    */
+} sm_present_image;
+size_t sm_present_workspace_bytes(int32_t B, int32_t mh, int32_t max_w); /* max_w >= every W_b; 0: an argument out of range */
+int sm_present_masks_u8(const float* masks, int64_t mask_stride_b, int32_t mh, int32_t mw, /* (B, mh, mw), image b at + b*stride */
+                        const uint8_t* rgb, const sm_present_image* images_host, const sm_present_image* images_dev,
+                        const int32_t* coef, const uint8_t* lut_rgba /* 256*4 */, float blend_alpha, float brightness,
+                        uint8_t* mask_out /* or NULL */, uint8_t* heat_out /* or NULL */,
+                        void* workspace, size_t workspace_bytes, int32_t B, void* stream);
+
 /* ---- baseline JPEG decode, bit-identical to Pillow (libjpeg-turbo: JDCT_ISLOW, fancy up-sampling): host entropy decode + device
  * dequantise / IDCT / chroma up-sampling / YCbCr -> RGB (csrc/jpeg.hip, csrc/jpeg_host.h) ------------------------------------- */
 #define SM_JPEG_UNSUPPORTED 1 /* not an error: the file (or something inside it) is not for this decoder - decode it with Pillow */

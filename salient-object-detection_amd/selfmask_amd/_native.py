@@ -151,6 +151,14 @@ class ObjectsArgs(C.Structure):
                 ("min_area", C.c_int32), ("max_objects", C.c_int32), ("scale", C.c_float)]
 
 
+class PresentImage(C.Structure):
+    _fields_ = [("img_off", C.c_int64), ("px_off", C.c_int64), ("H", C.c_int32), ("W", C.c_int32), ("coef_x", C.c_int32),
+                ("coef_y", C.c_int32), ("ksx", C.c_int32), ("ksy", C.c_int32)]
+
+
+PRESENT_MAX_MASK, PRESENT_MAX_PIXELS = 512, 1 << 24
+
+
 class JpegInfo(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("components", C.c_int32), ("h_samp", C.c_int32 * 4),
                 ("v_samp", C.c_int32 * 4), ("supported", C.c_int32), ("sampling", C.c_int32), ("mcus_x", C.c_int32),
@@ -244,6 +252,9 @@ SYMBOLS = {
     "sm_mask_objects_seg_cap": (C.c_int32, [C.c_int32, C.c_int32]),
     "sm_mask_objects_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "sm_mask_objects": (C.c_int, [C.POINTER(ObjectsArgs), fp, fp]),
+    "sm_present_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "sm_present_masks_u8": (C.c_int, [fp, C.c_int64, C.c_int32, C.c_int32, fp, fp, fp, fp, fp, C.c_float, C.c_float, fp, fp, fp, C.c_size_t,
+                                      C.c_int32, fp]),
     "sm_jpeg_probe": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(JpegInfo)]),
     "sm_jpeg_entropy_decode": (C.c_int, [C.c_char_p, C.c_size_t, fp, C.c_size_t, fp, C.POINTER(JpegInfo)]),
     "sm_jpeg_decode_batch_u8": (C.c_int, [fp, fp, C.c_int32, fp, fp, fp, fp]),

@@ -4,9 +4,11 @@ clip(mask, 0, 1)`` at batch 1.
 
 On the MI355X the whole of it after the image decode is device work: the Pillow-exact resize + normalisation kernels
 (pipeline.py), the forward replayed from ONE captured hipGraph (batch 1 is launch-bound: ~170 kernels of a few
-microseconds), and a selection kernel - one small D2H copy of (index, 20 scores, mask) leaves the GPU.  The web shell
-around it (Flask, base64 PNG encoding, LANCZOS resize to the upload's size, jet heat map) is product code outside the hot
-path: ``predict()`` still returns the reference's response keys, built on the host from ``predict_tensors()``.
+microseconds), and a selection kernel - one small D2H copy of (index, 20 scores, mask) leaves the GPU.  The response's two
+images are device work as well (``predict_images()``, csrc/present.hip): the mask's LANCZOS resize to the upload's size and the jet
+heat map blended over the upload, bit-identical to the reference's Pillow + matplotlib chain and computed from the RGB bytes the input
+pipeline uploaded already.  What stays on the host is the web shell (Flask) and the base64 PNG encoding: ``predict()`` returns the
+reference's response keys, encoded from ``predict_images()``.
 """
 import base64
 import threading
@@ -19,11 +21,12 @@ import torch
 from PIL import Image
 
 from . import _native as N
+from . import ops
 from .base_structure import BaseStructure
 from .graphs import GraphedForward
 from .maskformer import load_checkpoint
 from .misc import get_model
-from .pipeline import preprocess_on_device
+from .pipeline import _POOL, pack_images, preprocess_on_device
 
 
 class SelfMaskInference:
@@ -83,8 +86,17 @@ class SelfMaskInference:
         with self._lock:
             return self._predict_locked(rgb)
 
-    def _predict_locked(self, rgb: np.ndarray) -> dict:
-        x = self.preprocess_image(rgb)
+    def _select_locked(self, rgb: np.ndarray, keep_pixels: bool = False):
+        """Input pipeline, forward and selection queued on the current stream -> (device result buffer [best index | nq scores |
+        h*w mask], its page-locked host copy's buffer, nq, h, w, the uploaded RGB bytes on the device when ``keep_pixels``)."""
+        pixels = None
+        if keep_pixels:  # as preprocess_image, with the one upload of the RGB bytes kept for the response's heat map
+            staged = pack_images([rgb], self.input_size, pinned=True)
+            pixels = staged[0].to(self.device, non_blocking=True)
+            _POOL.release_after((staged[0],), torch.cuda.current_stream(self.device))
+            x = preprocess_on_device([rgb], self.input_size, self.device, packed=(pixels,) + tuple(staged[1:]))
+        else:
+            x = self.preprocess_image(rgb)
         out = self.base_structure._forward({"x": x})
         mask_pred, obj = out["mask_pred"], out.get("objectness")
         if obj is None:
@@ -102,37 +114,47 @@ class SelfMaskInference:
                                           dev_buf[1 + nq:].data_ptr(), dev_buf[:1].data_ptr(), 1, nq, h * w,
                                           torch.cuda.current_stream(self.device).cuda_stream), "sm_pick_mask_f32")
         dev_buf[1:1 + nq].copy_(last_obj[0])
+        return dev_buf, host_buf, nq, h, w, pixels
+
+    def _predict_locked(self, rgb: np.ndarray) -> dict:
+        dev_buf, host_buf, nq, h, w, _ = self._select_locked(rgb)
         host_buf.copy_(dev_buf, non_blocking=True)
         torch.cuda.current_stream(self.device).synchronize()  # the request is done
         out_h = host_buf.numpy()
         return {"best_idx": int(out_h[:1].view(np.int32)[0]), "objectness_scores": out_h[1:1 + nq].copy(),
                 "mask": out_h[1 + nq:].reshape(h, w).copy()}
 
+    @torch.no_grad()
+    def predict_images(self, image) -> dict:
+        """The response's arrays (app.py:241-311): {"mask" (H, W) uint8: the selected mask, 8 bits, LANCZOS-resized to the upload's
+        size; "heatmap" (H, W, 4) uint8: jet of it blended over the upload and brightened; "objectness_scores" (nq,); "best_idx"} -
+        the bytes the reference's Pillow + matplotlib chain gives, computed on the device behind the selection, on the same stream
+        and under the same lock, from the RGB bytes the input pipeline uploaded.  One stream synchronisation ends the request."""
+        rgb = self._to_rgb_array(image)
+        with self._lock:
+            dev_buf, host_buf, nq, h, w, pixels = self._select_locked(rgb, keep_pixels=True)
+            host_buf[:1 + nq].copy_(dev_buf[:1 + nq], non_blocking=True)
+            pending = ops.present_masks_async(dev_buf[1 + nq:].view(1, h, w), [rgb.shape[:2]], packed=(pixels, [0]))
+            (mask, heat), = pending.result()  # waits for the last copy queued on the stream: the request is done
+            out_h = host_buf.numpy()
+            return {"mask": mask, "heatmap": heat, "objectness_scores": out_h[1:1 + nq].copy(),
+                    "best_idx": int(out_h[:1].view(np.int32)[0])}
+
     # ---- host: the reference's response ---------------------------------------------------------------------------------------
     def predict(self, image) -> dict:
-        """app.py:241-347: same keys ('original', 'mask', 'heatmap' as base64 PNG data URLs, 'objectness_scores')."""
+        """app.py:241-347: same keys ('original', 'mask', 'heatmap' as base64 PNG data URLs, 'objectness_scores').  The mask and the
+        heat map come from ``predict_images()``: the reference's pixels and modes ('L', 'RGBA') through the same encoder, so the
+        strings are its own.  One intended difference from the reference's code: the jet table is part of this package
+        (present.JET_RGBA), so the heat map is there whether matplotlib is installed or not, where it used to be None without it."""
         rgb = self._to_rgb_array(image)
         if hasattr(image, "stream"):
             image.stream.seek(0)
-        t = self.predict_tensors(rgb)
-        original = Image.fromarray(rgb)
-        mask_img = Image.fromarray((t["mask"] * 255).astype(np.uint8)).resize(original.size, Image.Resampling.LANCZOS)
-        heat = None
-        try:  # the jet colour map comes from matplotlib in the reference (app.py:296-304); optional here
-            import matplotlib.pyplot as plt
-            from PIL import ImageEnhance
-            rgba = (plt.get_cmap("jet")(np.array(mask_img) / 255.0) * 255).astype(np.uint8)
-            heat_img = Image.fromarray(rgba).convert("RGBA").resize(original.size, Image.Resampling.LANCZOS)
-            heat = ImageEnhance.Brightness(Image.blend(original.convert("RGBA"), heat_img, alpha=0.5)).enhance(1.1)
-        except ImportError:
-            pass
+        t = self.predict_images(rgb)
 
         def url(img):
-            if img is None:
-                return None
             buf = BytesIO()
             img.save(buf, format="PNG")
             return "data:image/png;base64," + base64.b64encode(buf.getvalue()).decode()
 
-        return {"original": url(original), "mask": url(mask_img), "heatmap": url(heat),
+        return {"original": url(Image.fromarray(rgb)), "mask": url(Image.fromarray(t["mask"])), "heatmap": url(Image.fromarray(t["heatmap"])),
                 "objectness_scores": t["objectness_scores"], "best_idx": t["best_idx"]}

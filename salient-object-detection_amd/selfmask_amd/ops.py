@@ -795,3 +795,162 @@ def rle_runs_packed_async(planes: torch.Tensor, table, cap: int = 8192, objects=
     if not planes.is_cuda or planes.dtype != torch.uint8 or not planes.is_contiguous() or planes.numel() < table.n_pixels:
         raise RuntimeError("rle_runs_packed_async takes the packed uint8 planes of the batch on a HIP device (no CPU fallback)")
     return PendingPackedRuns(planes, table, max(1, min(int(cap), table.max_pixels)), ObjectOptions.of(objects))
+
+
+# ---- the serving response's images: resized 8-bit mask + heat map (csrc/present.hip) ---------------------------------------------------
+_PRESENT_TABLES = {}   # (device, mh, mw, ((H, W, img_off), ...)) -> _PresentTables, the most recent _PRESENT_TABLES_MAX kept
+_PRESENT_TABLES_MAX = 64
+_PRESENT_LUT = {}
+
+
+class _PresentTables:
+    """Descriptor and tap tables of one batch of sizes, on the host and on the device (uploaded once through the pinned pool; ``ready``
+    orders another stream's first use behind that upload).  Image b's pixels start at ``px_off[b]``, a multiple of 4."""
+
+    def __init__(self, mh, mw, items, device):
+        import ctypes
+        import numpy as np
+        from .pipeline import _POOL
+        from .present import pil_lanczos_coeffs
+        B = len(items)
+        self.host = (N.PresentImage * B)()
+        parts, index, ci, po, self.px_off = [], {}, 0, 0, []
+        for b, (h, w, img_off) in enumerate(items):
+            if h < 1 or w < 1 or h * w > N.PRESENT_MAX_PIXELS:
+                raise ValueError(f"image {b} is {h} x {w} (1 .. {N.PRESENT_MAX_PIXELS} pixels)")
+            d = self.host[b]
+            d.img_off, d.px_off, d.H, d.W = img_off, po, h, w
+            self.px_off.append(po)
+            po += (h * w + 3) & ~3
+            for n_in, n_out, key in ((mw, w, "x"), (mh, h, "y")):
+                o, ks = 0, 0  # a pass between equal lengths is skipped
+                if n_in != n_out:
+                    if (n_in, n_out) not in index:
+                        bounds, taps, ks = pil_lanczos_coeffs(n_in, n_out)
+                        index[(n_in, n_out)] = (ci, ks)
+                        parts += [bounds.reshape(-1), taps.reshape(-1)]
+                        ci += bounds.size + taps.size
+                    o, ks = index[(n_in, n_out)]
+                if key == "x":
+                    d.coef_x, d.ksx = o, ks
+                else:
+                    d.coef_y, d.ksy = o, ks
+        self.B, self.n_pixels, self.max_w = B, po, max(w for _, w, _ in items)
+        self.shapes = [(h, w) for h, w, _ in items]
+        coef = _POOL.get(max(ci, 1), torch.int32)
+        coef.numpy()[:ci] = np.concatenate(parts) if parts else 0
+        descr = _POOL.get(ctypes.sizeof(self.host), torch.uint8)
+        descr.numpy()[:] = np.frombuffer(bytes(self.host), np.uint8)
+        self.coef, self.dev = coef.to(device, non_blocking=True), descr.to(device, non_blocking=True)
+        st = torch.cuda.current_stream(device)
+        _POOL.release_after((coef, descr), st)
+        self.ready = torch.cuda.Event()
+        self.ready.record(st)
+
+
+def _present_tables(mh, mw, items, device) -> _PresentTables:
+    key = (device, mh, mw, tuple(items))
+    t = _PRESENT_TABLES.pop(key, None)
+    if t is None:
+        t = _PresentTables(mh, mw, items, device)
+    _PRESENT_TABLES[key] = t  # most recently used last
+    while len(_PRESENT_TABLES) > _PRESENT_TABLES_MAX:
+        _PRESENT_TABLES.pop(next(iter(_PRESENT_TABLES)))
+    return t
+
+
+def _present_lut(device) -> torch.Tensor:
+    t = _PRESENT_LUT.get(device)
+    if t is None:
+        from .present import JET_RGBA
+        t = _PRESENT_LUT[device] = torch.from_numpy(JET_RGBA.copy()).to(device)
+    return t
+
+
+class PendingPresent:
+    """``present_masks_async``'s launches and (``host=True``) their one device-to-host copy, queued on the current stream;
+    ``result()`` waits for that copy alone and hands out per image ``(mask (H, W) uint8 | None, heat map (H, W, 4) uint8 | None)`` -
+    numpy views of one page-locked buffer, or views of the device buffer."""
+
+    def __init__(self, tables, dev_buf, host_buf, heat_at, want_mask, want_heat, keep):
+        self.tables, self.dev_buf, self.host_buf, self.heat_at = tables, dev_buf, host_buf, heat_at
+        self.want_mask, self.want_heat = want_mask, want_heat
+        self._keep = keep  # inputs of the queued kernels
+        self.done = None
+        if host_buf is not None:
+            self.done = torch.cuda.Event()
+            self.done.record(torch.cuda.current_stream(dev_buf.device))
+
+    def result(self):
+        if self.done is not None:
+            self.done.synchronize()
+            self._keep = None
+        buf = self.host_buf.numpy() if self.host_buf is not None else self.dev_buf
+        out = []
+        for (h, w), po in zip(self.tables.shapes, self.tables.px_off):
+            m = buf[po:po + h * w].reshape(h, w) if self.want_mask else None
+            a = self.heat_at + 4 * po
+            out.append((m, buf[a:a + 4 * h * w].reshape(h, w, 4) if self.want_heat else None))
+        return out
+
+
+def present_masks_async(masks: torch.Tensor, images, packed=None, want_mask: bool = True, want_heat: bool = True, host: bool = True,
+                        alpha: float = 0.5, brightness: float = 1.1, lut: Optional[torch.Tensor] = None) -> PendingPresent:
+    """The response's two images for B selected masks: ``masks`` (B, mh, mw) float32 in [0, 1] on the device; ``images`` a list of
+    (H, W, 3) uint8 arrays (packed and uploaded here through the pinned pool), or - ``packed=(pixel buffer on the device, byte offset of
+    every image in it)``, what the input pipeline uploaded already - anything that carries their (H, W).  Image b's mask is resized to
+    its (H, W) as Pillow's LANCZOS does; the heat map is ``lut`` (256 x 4 uint8 on the device; default: jet) of it, blended with the
+    upload and brightened.  ``host``: one device-to-host copy of both outputs into page-locked memory.  Sizes seen before reuse their
+    descriptor and tap tables on the device."""
+    import numpy as np
+    from .pipeline import _POOL, packed_pixel_offsets
+    if not masks.is_cuda or masks.dtype != torch.float32 or masks.dim() != 3 or masks[0].numel() and not masks[0].is_contiguous():
+        raise RuntimeError("present_masks needs a (B, mh, mw) float32 tensor on a HIP device whose masks are contiguous (no CPU fallback)")
+    if not (want_mask or want_heat):
+        raise ValueError("present_masks: neither the mask nor the heat map asked for")
+    device, (B, mh, mw) = masks.device, masks.shape
+    shapes = [tuple(int(v) for v in (im.shape[:2] if hasattr(im, "shape") else im[:2])) for im in images]
+    if len(shapes) != B:
+        raise ValueError(f"{B} masks for {len(shapes)} images")
+    st = torch.cuda.current_stream(device)
+    keep = [masks]
+    if packed is not None:
+        pixels, offs = packed
+        if not pixels.is_cuda or pixels.dtype != torch.uint8:
+            raise RuntimeError("present_masks: packed pixels are a uint8 buffer on the HIP device")
+    elif want_heat:
+        offs = packed_pixel_offsets(shapes)
+        staging = _POOL.get(offs[-1] + shapes[-1][0] * shapes[-1][1] * 3, torch.uint8)
+        sv = staging.numpy()
+        for im, (h, w), o in zip(images, shapes, offs):
+            assert im.dtype == np.uint8 and im.shape == (h, w, 3), "uploads must be (H, W, 3) uint8"
+            sv[o:o + h * w * 3] = im.reshape(-1)
+        pixels = staging.to(device, non_blocking=True)
+        _POOL.release_after((staging,), st)
+    else:
+        pixels, offs = None, [0] * B
+    for (h, w), o in zip(shapes, offs):
+        if want_heat and (o < 0 or o + h * w * 3 > pixels.numel()):
+            raise ValueError("present_masks: an image lies outside the pixel buffer")
+    t = _present_tables(mh, mw, tuple((h, w, int(o)) for (h, w), o in zip(shapes, offs)), device)
+    st.wait_event(t.ready)
+    heat_at = (t.n_pixels + 15) & ~15 if want_mask else 0
+    dev_buf = torch.empty(heat_at + (4 * t.n_pixels if want_heat else 0), dtype=torch.uint8, device=device)
+    lib = N.load()
+    ws_bytes = lib.sm_present_workspace_bytes(B, mh, t.max_w)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=device)
+    lut = _present_lut(device) if lut is None else lut
+    N.check(lib.sm_present_masks_u8(masks.data_ptr(), masks.stride(0), mh, mw, _ptr(pixels), t.host, t.dev.data_ptr(), t.coef.data_ptr(),
+                                    lut.data_ptr(), alpha, brightness, dev_buf.data_ptr() if want_mask else None,
+                                    dev_buf[heat_at:].data_ptr() if want_heat else None, ws.data_ptr(), ws_bytes, B, st.cuda_stream),
+            "sm_present_masks_u8")
+    host_buf = None
+    if host:
+        host_buf = torch.empty(dev_buf.numel(), dtype=torch.uint8, pin_memory=True)
+        host_buf.copy_(dev_buf, non_blocking=True)
+    return PendingPresent(t, dev_buf, host_buf, heat_at, want_mask, want_heat, keep + [pixels, ws, lut])
+
+
+def present_masks(masks: torch.Tensor, images, **kw):
+    """``present_masks_async(...).result()``: per image ``(mask (H, W) uint8, heat map (H, W, 4) uint8)``."""
+    return present_masks_async(masks, images, **kw).result()

@@ -1,0 +1,137 @@
+"""CPU-only checks of the response's images (selfmask_amd/present.py, csrc/present.hip): the integer restatement equals Pillow and
+matplotlib bit for bit, the colour table is pinned, and the new C ABI is exported, laid out as its ctypes mirror and validated on the
+host before any launch."""
+import ctypes
+import hashlib
+import os
+
+import numpy as np
+import pytest
+
+from selfmask_amd import _native as N
+from selfmask_amd import present as P
+from _present_cases import KINDS, SHAPES, make_case, pil_heat, pil_mask
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CASES = [(i, k) for i in range(len(SHAPES)) for k in KINDS]
+
+
+@pytest.mark.parametrize("i,kind", CASES)
+def test_mask_resize_equals_pillow_lanczos(i, kind):
+    mask, rgb = make_case(i, kind)
+    H, W = rgb.shape[:2]
+    got, _ = P.present_reference_numpy(mask, rgb)
+    want = np.array(pil_mask(mask, H, W))
+    assert got.dtype == np.uint8 and got.shape == (H, W)
+    assert np.array_equal(got, want)
+    if kind == "hard" and min(H, W) > 56:
+        assert got.min() == 0 and got.max() == 255
+
+
+def test_lanczos_tap_counts():
+    assert P.pil_lanczos_coeffs(28, 300)[2] == 7 and P.pil_lanczos_coeffs(28, 17)[2] == 11
+    assert P.pil_lanczos_coeffs(56, 1)[2] == 337 and P.pil_lanczos_coeffs(448, 1)[2] == 2689
+    bounds, taps, ks = P.pil_lanczos_coeffs(28, 17)
+    assert bounds.shape == (17, 2) and taps.shape == (17, ks) and bounds.dtype == np.int32 and taps.dtype == np.int32
+    assert (bounds[:, 0] >= 0).all() and (bounds[:, 0] + bounds[:, 1] <= 28).all() and (bounds[:, 1] <= ks).all()
+
+
+@pytest.mark.parametrize("i,kind", CASES)
+def test_heatmap_equals_the_reference_chain(i, kind):
+    pytest.importorskip("matplotlib")
+    mask, rgb = make_case(i, kind)
+    H, W = rgb.shape[:2]
+    got_mask, got_heat = P.present_reference_numpy(mask, rgb)
+    want = pil_heat(pil_mask(mask, H, W), rgb)
+    assert want.mode == "RGBA"
+    assert np.array_equal(got_heat, np.array(want))
+
+
+def test_pinned_table_equals_matplotlib_jet():
+    plt = pytest.importorskip("matplotlib.pyplot")
+    cm = plt.get_cmap("jet")
+    assert cm.N == 256
+    assert np.array_equal(P.JET_RGBA, (cm(np.arange(256)) * 255).astype(np.uint8))
+    assert np.array_equal(P.JET_RGBA, (cm(np.arange(256) / 255.0) * 255).astype(np.uint8))  # cmap(v / 255.0) is entry v
+
+
+def test_pinned_table_digest():
+    assert P.JET_RGBA.shape == (256, 4) and P.JET_RGBA.dtype == np.uint8
+    assert hashlib.sha256(P.JET_RGBA.tobytes()).hexdigest() == P.JET_RGBA_SHA256 == \
+        "878b65944cde43dd8015035710be8c53357a64fa2fbc6eae358ee5257a876b8e"
+
+
+def test_library_exports_the_present_symbols():
+    lib = N.load()
+    for name in ("sm_present_masks_u8", "sm_present_workspace_bytes"):
+        assert hasattr(lib, name) and name in N.SYMBOLS
+    assert lib.sm_present_workspace_bytes(1, 28, 400) >= 28 * 400
+    assert lib.sm_present_workspace_bytes(3, 56, 1920) >= 3 * 56 * 1920
+    for bad in ((0, 28, 400), (1, 0, 400), (1, 513, 400), (1, 28, 0), (65536, 28, 400)):
+        assert lib.sm_present_workspace_bytes(*bad) == 0
+
+
+def test_present_image_layout_matches_header(tmp_path):
+    import shutil
+    import subprocess
+    cc = shutil.which("gcc") or shutil.which("cc")
+    if cc is None:
+        pytest.skip("no C compiler")
+    fields = [f for f, _ in N.PresentImage._fields_]
+    src = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{os.path.join(REPO, "include", "selfmask_hip.h")}"', 'int main(void){',
+           'printf("sizeof %zu\\n", sizeof(sm_present_image));']
+    src += [f'printf("{f} %zu\\n", offsetof(sm_present_image, {f}));' for f in fields]
+    src.append('return 0;}')
+    c = tmp_path / "present_layout.c"
+    c.write_text("\n".join(src))
+    exe = tmp_path / "present_layout"
+    subprocess.run([cc, "-o", str(exe), str(c)], check=True)
+    out = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    assert int(out["sizeof"]) == ctypes.sizeof(N.PresentImage) == 40
+    for f in fields:
+        assert int(out[f]) == getattr(N.PresentImage, f).offset, f
+
+
+def _valid_call():
+    """arguments that pass every check (the pointers are never followed: each test breaks one argument, and validation returns
+    before any launch)"""
+    mh = mw = 28
+    H, W = 30, 40
+    table = (N.PresentImage * 1)()
+    d = table[0]
+    d.img_off, d.px_off, d.H, d.W, d.coef_x, d.coef_y, d.ksx, d.ksy = 0, 0, H, W, 0, 1000, 7, 7
+    ws = N.load().sm_present_workspace_bytes(1, mh, W)
+    fake = 0x10000  # non-null, 16-byte aligned
+    return dict(masks=fake, stride=mh * mw, mh=mh, mw=mw, rgb=fake, host=table, dev=fake, coef=fake, lut=fake, alpha=0.5, brightness=1.1,
+                mask_out=fake, heat_out=fake, ws=fake, ws_bytes=ws, B=1)
+
+
+def _call(a):
+    return N.load().sm_present_masks_u8(a["masks"], a["stride"], a["mh"], a["mw"], a["rgb"], a["host"], a["dev"], a["coef"], a["lut"],
+                                        a["alpha"], a["brightness"], a["mask_out"], a["heat_out"], a["ws"], a["ws_bytes"], a["B"], None)
+
+
+@pytest.mark.parametrize("change,message", [
+    (dict(masks=None), b"null pointer"),
+    (dict(B=0), b"B=0"),
+    (dict(mh=513), b"mask 513 x 28"),
+    (dict(ws_short=1), b"workspace"),
+    (dict(mask_out=None, heat_out=None), b"null pointer"),
+    (dict(heat_out=0x10004), b"misaligned"),
+])
+def test_argument_validation_without_gpu(change, message):
+    a = _valid_call()
+    if "ws_short" in change:
+        a["ws_bytes"] -= change["ws_short"]  # one byte short
+    else:
+        a.update(change)
+    assert _call(a) == -1
+    assert message in N.load().sm_last_error(), N.load().sm_last_error()
+
+
+def test_image_table_validation_without_gpu():
+    lib = N.load()
+    for field, value, message in (("H", 0, b"image 0 is 0 x 40"), ("W", 1 << 24, b"at most"), ("ksx", 0, b"skipped pass"), ("px_off", -4, b"negative")):
+        a = _valid_call()
+        setattr(a["host"][0], field, value)
+        assert _call(a) == -1 and message in lib.sm_last_error(), (field, lib.sm_last_error())
