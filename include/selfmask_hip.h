@@ -631,6 +631,31 @@ typedef struct sm_jpeg_image {
 int sm_jpeg_decode_batch_u8(const sm_jpeg_image* descr_host, const sm_jpeg_image* descr_dev, int32_t B, int16_t* coef,
                             const uint16_t* qt, uint8_t* pixels_out, void* stream);
 
+/* ---- PNG encoding on the device (csrc/png.hip): 8-bit grey / RGB / RGBA images that are in device memory -> PNG files in device memory,
+ * so that the serving response's three pictures leave the GPU compressed.  The bytes are DEFINED by selfmask_amd/png.py
+ * (encode_reference) and are a function of the image and filter_mode alone: per-row adaptive filter (smallest sum of |signed byte|, ties
+ * to the lowest id), the filtered stream cut every 16 KiB, each chunk one deflate block (run matches at distance 1 in closed form; the
+ * smallest of stored / fixed / dynamic Huffman, code lengths limited to 15 / 7 bits) ended by an empty stored block, one IDAT per chunk,
+ * zlib header and Adler-32, CRC-32 on every chunk.  Any PNG reader decodes them to the input's pixels; they are NOT the bytes zlib or
+ * Pillow would write.  Four launches (workspace plan, filter, deflate, gather); nothing is allocated, copied or synchronised; the grids
+ * are sized from images_host (validated before any launch), the kernels read images_dev (the same table in device memory) and skip an
+ * image whose entry is out of range there; images of different sizes and channel counts go in one call and every image's bytes are those
+ * of its own single call.  Image b's file is written at out + out_off, its size to sizes_out[b]; bytes behind the file are left alone.
+ * Limits: B <= 65535, H * W <= 2^24, channels 1, 3 or 4, out_cap >= sm_png_bound (else SM_ENOSPACE), workspace 16-byte aligned and of
+ * sm_png_workspace_bytes (else SM_ENOSPACE). */
+typedef struct sm_png_image {
+    int64_t pix_off;      /* bytes: this image's (H, W, channels) uint8 pixels inside `pixels`                                       */
+    int64_t out_off;      /* bytes: where its file begins inside `out`                                                               */
+    int64_t out_cap;      /* bytes of room there, >= sm_png_bound(H, W, channels)                                                    */
+    int32_t H, W, channels;
+    int32_t filter_mode;  /* -1: adaptive per row; 0 .. 4: that PNG filter for every row                                             */
+    int32_t reserved[2];
+} sm_png_image;
+size_t sm_png_bound(int32_t H, int32_t W, int32_t channels); /* HOST: no file of such an image is larger; 0: out of range */
+size_t sm_png_workspace_bytes(const sm_png_image* images_host, int32_t B); /* HOST; 0: an argument out of range */
+int sm_png_encode_batch_u8(const uint8_t* pixels, const sm_png_image* images_host, const sm_png_image* images_dev, int32_t B,
+                           uint8_t* out, int64_t* sizes_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- whole forward --------------------------------------------------------------------------------------------- */
 typedef struct sm_enc_layer {
     const float *norm1_w, *norm1_b, *qkv_w, *qkv_b, *proj_w, *proj_b, *norm2_w, *norm2_b, *fc1_w, *fc1_b, *fc2_w,

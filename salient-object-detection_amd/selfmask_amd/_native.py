@@ -159,6 +159,11 @@ class PresentImage(C.Structure):
 PRESENT_MAX_MASK, PRESENT_MAX_PIXELS = 512, 1 << 24
 
 
+class PngImage(C.Structure):
+    _fields_ = [("pix_off", C.c_int64), ("out_off", C.c_int64), ("out_cap", C.c_int64), ("H", C.c_int32), ("W", C.c_int32),
+                ("channels", C.c_int32), ("filter_mode", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class JpegInfo(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("components", C.c_int32), ("h_samp", C.c_int32 * 4),
                 ("v_samp", C.c_int32 * 4), ("supported", C.c_int32), ("sampling", C.c_int32), ("mcus_x", C.c_int32),
@@ -255,6 +260,9 @@ SYMBOLS = {
     "sm_present_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "sm_present_masks_u8": (C.c_int, [fp, C.c_int64, C.c_int32, C.c_int32, fp, fp, fp, fp, fp, C.c_float, C.c_float, fp, fp, fp, C.c_size_t,
                                       C.c_int32, fp]),
+    "sm_png_bound": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "sm_png_workspace_bytes": (C.c_size_t, [fp, C.c_int32]),
+    "sm_png_encode_batch_u8": (C.c_int, [fp, fp, fp, C.c_int32, fp, fp, fp, C.c_size_t, fp]),
     "sm_jpeg_probe": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(JpegInfo)]),
     "sm_jpeg_entropy_decode": (C.c_int, [C.c_char_p, C.c_size_t, fp, C.c_size_t, fp, C.POINTER(JpegInfo)]),
     "sm_jpeg_decode_batch_u8": (C.c_int, [fp, fp, C.c_int32, fp, fp, fp, fp]),

@@ -8,7 +8,8 @@ microseconds), and a selection kernel - one small D2H copy of (index, 20 scores,
 images are device work as well (``predict_images()``, csrc/present.hip): the mask's LANCZOS resize to the upload's size and the jet
 heat map blended over the upload, bit-identical to the reference's Pillow + matplotlib chain and computed from the RGB bytes the input
 pipeline uploaded already.  What stays on the host is the web shell (Flask) and the base64 PNG encoding: ``predict()`` returns the
-reference's response keys, encoded from ``predict_images()``.
+reference's response keys, encoded from ``predict_images()``.  ``predict(image, encoder="device")`` and ``predict_png()`` (opt-in) encode
+the three PNG files on the device as well (csrc/png.hip): the same pixels for whoever decodes them, other bytes than Pillow's.
 """
 import base64
 import threading
@@ -27,6 +28,10 @@ from .graphs import GraphedForward
 from .maskformer import load_checkpoint
 from .misc import get_model
 from .pipeline import _POOL, pack_images, preprocess_on_device
+
+
+def _data_url(png: bytes) -> str:
+    return "data:image/png;base64," + base64.b64encode(png).decode()
 
 
 class SelfMaskInference:
@@ -141,11 +146,40 @@ class SelfMaskInference:
                     "best_idx": int(out_h[:1].view(np.int32)[0])}
 
     # ---- host: the reference's response ---------------------------------------------------------------------------------------
-    def predict(self, image) -> dict:
+    @torch.no_grad()
+    def predict_png(self, image) -> dict:
+        """The response's three pictures as PNG files, encoded on the device (csrc/png.hip): {"original", "mask", "heatmap": bytes;
+        "objectness_scores" (nq,); "best_idx"}.  The mask and the heat map stay where ``present_masks_async`` wrote them, the original is
+        the upload the input pipeline kept: one ``png_encode`` of the three on the same stream under the same lock, and only compressed
+        bytes cross to the host.  The files decode to ``predict_images()``'s arrays; their bytes are ``png.encode_reference``'s, not
+        Pillow's."""
+        rgb = self._to_rgb_array(image)
+        H, W = rgb.shape[:2]
+        with self._lock:
+            dev_buf, host_buf, nq, h, w, pixels = self._select_locked(rgb, keep_pixels=True)
+            host_buf[:1 + nq].copy_(dev_buf[:1 + nq], non_blocking=True)
+            pending = ops.present_masks_async(dev_buf[1 + nq:].view(1, h, w), [(H, W)], packed=(pixels, [0]), host=False)
+            (mask, heat), = pending.result()  # views of the device buffer: nothing waited for
+            files = ops.png_encode([pixels[:H * W * 3].view(H, W, 3), mask, heat])  # ends the request: its last copy is the stream's last
+            out_h = host_buf.numpy()
+            return {"original": files[0], "mask": files[1], "heatmap": files[2], "objectness_scores": out_h[1:1 + nq].copy(),
+                    "best_idx": int(out_h[:1].view(np.int32)[0])}
+
+    def predict(self, image, encoder: str = "host") -> dict:
         """app.py:241-347: same keys ('original', 'mask', 'heatmap' as base64 PNG data URLs, 'objectness_scores').  The mask and the
         heat map come from ``predict_images()``: the reference's pixels and modes ('L', 'RGBA') through the same encoder, so the
         strings are its own.  One intended difference from the reference's code: the jet table is part of this package
-        (present.JET_RGBA), so the heat map is there whether matplotlib is installed or not, where it used to be None without it."""
+        (present.JET_RGBA), so the heat map is there whether matplotlib is installed or not, where it used to be None without it.
+        ``encoder="device"`` (opt-in): the three files come from ``predict_png()`` - the same pixels for whoever decodes them, other
+        bytes in the strings - and base64 is the host's only work on them."""
+        if encoder == "device":
+            t = self.predict_png(image)
+            if hasattr(image, "stream"):
+                image.stream.seek(0)
+            return {"original": _data_url(t["original"]), "mask": _data_url(t["mask"]), "heatmap": _data_url(t["heatmap"]),
+                    "objectness_scores": t["objectness_scores"], "best_idx": t["best_idx"]}
+        if encoder != "host":
+            raise ValueError(f"encoder={encoder!r}: 'host' or 'device'")
         rgb = self._to_rgb_array(image)
         if hasattr(image, "stream"):
             image.stream.seek(0)

@@ -651,14 +651,14 @@ class PendingPredictions:
     The inputs are kept until then - on overflow of ``cap`` the runs are found once more with room for the longest code - so the
     caller must not let the stream overwrite them (a replayed graph's static outputs) before asking."""
 
-    def __init__(self, mask_pred_last, objectness_last, table, scale, rle, binary, soft, cap, objects=None):
+    def __init__(self, mask_pred_last, objectness_last, table, scale, rle, binary, soft, cap, objects=None, soft_png=False):
         B, nq, mh, mw = mask_pred_last.shape
         dev = mask_pred_last.device
         self._in = (mask_pred_last, objectness_last, table, float(scale))
         self.table, self.cap = table, int(cap)
         self.best = torch.empty(B, dtype=torch.int32, device=dev)
         self.binary = torch.empty(table.n_pixels, dtype=torch.uint8, device=dev) if binary else None
-        self.soft = torch.empty(table.n_pixels, dtype=torch.uint8, device=dev) if soft else None
+        self.soft = torch.empty(table.n_pixels, dtype=torch.uint8, device=dev) if soft or soft_png else None
         self._starts = self._info = self._ws = self._objects = None
         self._opts, self._rle = objects, rle
         if rle or objects is not None:  # the objects are found on the runs
@@ -672,12 +672,14 @@ class PendingPredictions:
         self._small_h = torch.empty(small.shape, dtype=torch.int32, pin_memory=True)
         self._small_h.copy_(small, non_blocking=True)
         self._planes_h = {}
-        for name, t in (("binary", self.binary), ("soft", self.soft)):
+        for name, t in (("binary", self.binary), ("soft", self.soft if soft else None)):
             if t is not None:
                 self._planes_h[name] = torch.empty(t.shape, dtype=torch.uint8, pin_memory=True)
                 self._planes_h[name].copy_(t, non_blocking=True)
         self._done = torch.cuda.Event()
         self._done.record(torch.cuda.current_stream(dev))
+        # the soft maps as PNG files, encoded where they lie: their raw pixels stay on the device
+        self._png = png_encode_async(packed=(self.soft, table.px_off, [(h, w, 1) for h, w in table.shapes])) if soft_png else None
 
     def _launch(self, starts, info, cap, binary, soft):
         import ctypes
@@ -703,8 +705,8 @@ class PendingPredictions:
                 "sm_predict_masks_f32")
 
     def result(self) -> dict:
-        """-> {"best": [query index], "rle": [COCO uncompressed RLE dict], "binary" / "soft": [(H_b, W_b) uint8 array], "objects":
-        [the dict of ``_PendingObjects.result``]} (the keys asked for)"""
+        """-> {"best": [query index], "rle": [COCO uncompressed RLE dict], "binary" / "soft": [(H_b, W_b) uint8 array], "soft_png":
+        [the soft map as a PNG file, bytes], "objects": [the dict of ``_PendingObjects.result``]} (the keys asked for)"""
         self._done.synchronize()
         small = self._small_h.numpy()
         out = {"best": small[:, 0].tolist()}
@@ -724,25 +726,28 @@ class PendingPredictions:
         for name, h in self._planes_h.items():
             flat = h.numpy()
             out[name] = [flat[o:o + hh * ww].reshape(hh, ww) for o, (hh, ww) in zip(self.table.px_off, self.table.shapes)]
+        if self._png is not None:
+            out["soft_png"] = self._png.result()
         self._in = None
         return out
 
 
 def predict_masks(mask_pred_last: torch.Tensor, objectness_last: torch.Tensor, table, scale: float = 0.0, rle: bool = True,
-                  binary: bool = False, soft: bool = False, cap: int = 8192, objects=None) -> PendingPredictions:
+                  binary: bool = False, soft: bool = False, cap: int = 8192, objects=None, soft_png: bool = False) -> PendingPredictions:
     """The predictor's fused finish (sm_predict_masks_f32), without waiting: mask_pred_last (B, nq, mh, mw) probabilities (any batch
     stride), objectness_last (B, nq), ``table`` a PackedImages / MixedBatch with the output size of every image.  The arg-max query's
     mask, up-sampled as ``evaluate_masks`` up-samples it (``scale`` as there), thresholded at 0.5: ``rle`` its COCO run-length code,
     ``binary`` / ``soft`` packed uint8 planes (0/1; clip(v, 0, 1) * 255 truncated).  ``.best`` (B,) int32 stays on the device.
     ``objects`` (an ``ObjectOptions`` or a dict of its keys): sm_mask_objects is queued right behind the runs and ``result()`` gains
     "objects" - per image the mask's connected components with box, area, centroid, score = the mean of the soft values, first raster
-    pixel and, on request, an RLE each; ``None``: nothing more is launched."""
+    pixel and, on request, an RLE each; ``None``: nothing more is launched.  ``soft_png``: the soft planes are encoded as 8-bit grey
+    PNG files on the device (``png_encode_async`` on the packed planes) and ``result()`` gains "soft_png": one ``bytes`` per image."""
     _dev(mask_pred_last, objectness_last)
     B, nq, mh, mw = mask_pred_last.shape
     assert mask_pred_last.stride(3) == 1 and mask_pred_last.stride(2) == mw and mask_pred_last.stride(1) == mh * mw
     assert objectness_last.shape == (B, nq) and objectness_last.stride(1) == 1 and table.B == B
     return PendingPredictions(mask_pred_last, objectness_last, table, scale, rle, binary, soft, max(1, min(int(cap), table.max_pixels)),
-                              ObjectOptions.of(objects))
+                              ObjectOptions.of(objects), soft_png)
 
 
 class PendingPackedRuns:
@@ -954,3 +959,129 @@ def present_masks_async(masks: torch.Tensor, images, packed=None, want_mask: boo
 def present_masks(masks: torch.Tensor, images, **kw):
     """``present_masks_async(...).result()``: per image ``(mask (H, W) uint8, heat map (H, W, 4) uint8)``."""
     return present_masks_async(masks, images, **kw).result()
+
+
+# ---- PNG files of images that are on the device (csrc/png.hip; the format: selfmask_amd/png.py) ---------------------------------------
+_PNG_TABLES = {}   # (device, ((H, W, C, pix_off), ...), filter_mode) -> _PngTables, the most recent _PNG_TABLES_MAX kept
+_PNG_TABLES_MAX = 64
+
+
+class _PngTables:
+    """Descriptor table of one batch of shapes on the host and on the device (uploaded once through the pinned pool; ``ready`` orders
+    another stream's first use behind that upload).  Image b's file goes to ``out_off[b]`` (a multiple of 16) with ``cap[b]`` =
+    ``sm_png_bound`` bytes of room."""
+
+    def __init__(self, items, filter_mode, device):
+        import ctypes
+        import numpy as np
+        from .pipeline import _POOL
+        lib = N.load()
+        B = len(items)
+        self.host = (N.PngImage * B)()
+        self.out_off, self.cap, oo = [], [], 0
+        for b, (h, w, c, pix_off) in enumerate(items):
+            cap = lib.sm_png_bound(h, w, c)
+            if not cap:
+                raise ValueError(f"png_encode: image {b} is {h} x {w} x {c} (1, 3 or 4 channels, at most 2^24 pixels)")
+            d = self.host[b]
+            d.pix_off, d.out_off, d.out_cap, d.H, d.W, d.channels, d.filter_mode = pix_off, oo, cap, h, w, c, filter_mode
+            self.out_off.append(oo)
+            self.cap.append(cap)
+            oo += (cap + 15) & ~15
+        self.B, self.out_bytes = B, oo
+        self.ws_bytes = lib.sm_png_workspace_bytes(self.host, B)
+        descr = _POOL.get(ctypes.sizeof(self.host), torch.uint8)
+        descr.numpy()[:] = np.frombuffer(bytes(self.host), np.uint8)
+        self.dev = descr.to(device, non_blocking=True)
+        st = torch.cuda.current_stream(device)
+        _POOL.release_after((descr,), st)
+        self.ready = torch.cuda.Event()
+        self.ready.record(st)
+
+
+def _png_tables(items, filter_mode, device) -> _PngTables:
+    key = (device, tuple(items), filter_mode)
+    t = _PNG_TABLES.pop(key, None)
+    if t is None:
+        t = _PngTables(items, filter_mode, device)
+    _PNG_TABLES[key] = t  # most recently used last
+    while len(_PNG_TABLES) > _PNG_TABLES_MAX:
+        _PNG_TABLES.pop(next(iter(_PNG_TABLES)))
+    return t
+
+
+class PendingPng:
+    """``png_encode_async``'s launches and the copy of the files' sizes, queued on the current stream.  ``result()`` waits for the sizes,
+    copies exactly the used bytes of every file into page-locked memory on the same stream and hands out one ``bytes`` per image."""
+
+    def __init__(self, tables, out, sizes, stream, keep):
+        self.tables, self.out, self.stream, self._keep = tables, out, stream, keep
+        self.sizes_host = torch.empty(tables.B, dtype=torch.int64, pin_memory=True)
+        self.sizes_host.copy_(sizes, non_blocking=True)
+        self.done = torch.cuda.Event()
+        self.done.record(stream)
+
+    def result(self):
+        self.done.synchronize()
+        t = self.tables
+        sizes = [int(v) for v in self.sizes_host.tolist()]
+        for b, n in enumerate(sizes):
+            if not 0 < n <= t.cap[b]:
+                raise RuntimeError(f"png_encode: image {b} reports {n} bytes (bound {t.cap[b]})")
+        host = torch.empty(sum(sizes), dtype=torch.uint8, pin_memory=True)
+        at = 0
+        with torch.cuda.stream(self.stream):
+            for b, n in enumerate(sizes):
+                host[at:at + n].copy_(self.out[t.out_off[b]:t.out_off[b] + n], non_blocking=True)
+                at += n
+        self.stream.synchronize()
+        self._keep = None
+        flat, files, at = host.numpy(), [], 0
+        for n in sizes:
+            files.append(flat[at:at + n].tobytes())
+            at += n
+        return files
+
+
+def png_encode_async(buffers=None, packed=None, filter_mode: int = -1) -> PendingPng:
+    """PNG files of images in device memory: ``buffers`` a list of contiguous uint8 device tensors (H, W), (H, W, 3) or (H, W, 4) - packed
+    into one buffer here by one device-to-device copy - or ``packed=(uint8 device buffer, byte offset of every image in it, their
+    (H, W, C))``, which is used where it lies.  The bytes are those of ``png.encode_reference``; any PNG reader gives the pixels back.
+    Shape sets seen before reuse their descriptor table on the device."""
+    if packed is not None:
+        pixels, offs, shapes = packed
+        shapes = [tuple(int(v) for v in s) for s in shapes]
+    else:
+        if not buffers:
+            raise ValueError("png_encode: no images")
+        for tns in buffers:
+            if not (torch.is_tensor(tns) and tns.is_cuda and tns.dtype == torch.uint8 and tns.is_contiguous() and tns.dim() in (2, 3)):
+                raise RuntimeError("png_encode needs contiguous uint8 tensors on a HIP device (no CPU fallback)")
+        shapes = [(t.shape[0], t.shape[1], 1 if t.dim() == 2 else t.shape[2]) for t in buffers]
+        offs, o = [], 0
+        for h, w, c in shapes:
+            offs.append(o)
+            o += h * w * c
+        pixels = torch.cat([t.reshape(-1) for t in buffers]) if len(buffers) > 1 else buffers[0].reshape(-1)
+    if not pixels.is_cuda or pixels.dtype != torch.uint8 or not pixels.is_contiguous():
+        raise RuntimeError("png_encode: packed pixels are a contiguous uint8 buffer on the HIP device (no CPU fallback)")
+    if len(shapes) != len(offs):
+        raise ValueError(f"png_encode: {len(offs)} offsets for {len(shapes)} shapes")
+    for (h, w, c), o in zip(shapes, offs):
+        if o < 0 or o + h * w * c > pixels.numel():
+            raise ValueError("png_encode: an image lies outside the pixel buffer")
+    device = pixels.device
+    st = torch.cuda.current_stream(device)
+    t = _png_tables(tuple((h, w, c, int(o)) for (h, w, c), o in zip(shapes, offs)), int(filter_mode), device)
+    st.wait_event(t.ready)
+    out = torch.empty(t.out_bytes, dtype=torch.uint8, device=device)
+    sizes = torch.empty(t.B, dtype=torch.int64, device=device)
+    ws = torch.empty(max(t.ws_bytes, 1), dtype=torch.uint8, device=device)
+    N.check(N.load().sm_png_encode_batch_u8(pixels.data_ptr(), t.host, t.dev.data_ptr(), t.B, out.data_ptr(), sizes.data_ptr(), ws.data_ptr(),
+                                            t.ws_bytes, st.cuda_stream), "sm_png_encode_batch_u8")
+    return PendingPng(t, out, sizes, st, [pixels, ws, sizes])
+
+
+def png_encode(buffers=None, **kw):
+    """``png_encode_async(...).result()``: one ``bytes`` (a PNG file) per image."""
+    return png_encode_async(buffers, **kw).result()

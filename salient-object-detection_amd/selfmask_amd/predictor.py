@@ -21,7 +21,8 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 import torch
 
-OUTPUTS = ("rle", "binary", "soft", "objects")
+OUTPUTS = ("rle", "binary", "soft", "soft_png", "objects")
+PNG_ENCODERS = ("host", "device")
 DEFAULT_CAP = 8192       # run boundaries stored per image before the retry, as voting.rle_runs_async
 MAX_PIXELS = 1 << 22     # sm_predict_masks_f32's largest image
 MAX_OBJECTS_WIDTH = 16384  # sm_mask_objects' widest image
@@ -76,15 +77,19 @@ class _DeviceDecoded:
 
 class SaliencyPredictor:
     def __init__(self, network, device: torch.device = torch.device("cuda:0"), batch_size: int = 64, streams: int = 3,
-                 workers: Optional[int] = None, hip_graph: bool = True, cap: int = DEFAULT_CAP, decode: str = "host"):
+                 workers: Optional[int] = None, hip_graph: bool = True, cap: int = DEFAULT_CAP, decode: str = "host", png_encoder: str = "host"):
         """``network``: a ``selfmask_amd.MaskFormer`` with ``use_binary_classifier=True`` on ``device``; ``batch_size``: the most
         images per forward (of ONE token grid at native resolution); ``streams``: batches in flight; ``workers``: decode processes
         (default: this rank's share of the host cores); ``hip_graph``: replay recurring batch shapes as captured graphs;
         ``decode``: "host" = Pillow in the decode worker processes; "device" = ``selfmask_amd.jpeg.decode_jpeg_batch`` - baseline
         JPEGs entropy-decoded on at most 16 host THREADS (``workers`` caps them) and finished on the device, every other file by
-        Pillow on those threads: the same pixels, so the same results, without worker processes."""
+        Pillow on those threads: the same pixels, so the same results, without worker processes; ``png_encoder``: who writes the
+        soft maps' PNG files (output ``"soft_png"``, ``--png_dir``): "host" = Pillow from the soft maps copied to the host; "device" =
+        csrc/png.hip on the packed planes, only the files cross - other bytes, the same pixels for whoever reads them."""
         if decode not in DECODES:
             raise ValueError(f"decode={decode!r}: one of {DECODES}")
+        if png_encoder not in PNG_ENCODERS:
+            raise ValueError(f"png_encoder={png_encoder!r}: one of {PNG_ENCODERS}")
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError(f"SaliencyPredictor runs on a HIP device (got {device}); there is no CPU fallback")
@@ -99,7 +104,7 @@ class SaliencyPredictor:
                                f"fallback - call network.to(device)")
         self.network, self.device, self.batch_size = network, device, max(1, int(batch_size))
         self.streams, self.workers, self.hip_graph, self.cap = max(1, int(streams)), workers, bool(hip_graph), int(cap)
-        self.decode = decode
+        self.decode, self.png_encoder = decode, png_encoder
         self.last_best: Dict[str, int] = {}
         self._ring = None
 
@@ -111,7 +116,7 @@ class SaliencyPredictor:
                 raise ValueError(f"output={o!r}: one of {OUTPUTS}")
         if refine not in (None, "bilateral"):
             raise ValueError(f"refine={refine!r}: None or 'bilateral'")
-        if refine and "soft" in outputs:
+        if refine and ("soft" in outputs or "soft_png" in outputs):
             raise ValueError("output='soft' with refine='bilateral': the solver's soft output is not a [0, 1] sigmoid map; ask for "
                              "'rle' or 'binary'")
         if img_size is not None and int(img_size) < 1:
@@ -152,7 +157,8 @@ class SaliencyPredictor:
     def __call__(self, p_images: Sequence[str], img_size: Optional[int] = None, scale_factor: int = 2, output: str = "rle",
                  refine: Optional[str] = None, comm=None, objects=None) -> Dict[str, object]:
         """-> {file name: COCO uncompressed RLE dict (``output="rle"``) | (H, W) uint8 array: 0/1 (``"binary"``) or
-        clip(p, 0, 1) * 255 truncated (``"soft"``) | the mask's connected components (``"objects"``: the dict of
+        clip(p, 0, 1) * 255 truncated (``"soft"``) | that soft map as an 8-bit grey PNG file, bytes, encoded on the device
+        (``"soft_png"``) | the mask's connected components (``"objects"``: the dict of
         ``ops.predict_masks(objects=)`` + "best"; ``objects``: an ``ops.ObjectOptions`` or a dict of its keys)}, in list order;
         ``.last_best`` {file name: query index}.
         ``img_size=None``: native resolution in token-grid buckets, the mask up-sampled by ``patch // scale_factor`` and cropped -
@@ -186,7 +192,8 @@ class SaliencyPredictor:
         if mask_pred.dim() == 5:  # last decoder layer
             mask_pred, obj = mask_pred[:, -1], obj[:, -1]
         obj = obj.squeeze(-1)
-        want = dict(rle="rle" in outputs, binary="binary" in outputs, soft="soft" in outputs, cap=self.cap, objects=objects)
+        want = dict(rle="rle" in outputs, binary="binary" in outputs, soft="soft" in outputs, cap=self.cap, objects=objects,
+                    soft_png="soft_png" in outputs)
         if not refine:
             return ops.predict_masks(mask_pred, obj, ops.PackedImages(shapes, self.device), scale, **want)
         B = mask_pred.shape[0]
@@ -250,7 +257,7 @@ class SaliencyPredictor:
             best.update(zip(bnames, res["best"]))
             for o in outputs:
                 for n, v, q in zip(bnames, res[o], res["best"]):
-                    results[o][n] = v if o == "rle" else {**v, "best": q} if o == "objects" else v.copy()
+                    results[o][n] = v if o in ("rle", "soft_png") else {**v, "best": q} if o == "objects" else v.copy()
 
         from .decode_pool import default_workers
         avg = max(1, len(p_images) // len(batches))  # buckets are often smaller than batch_size: keep every decode worker busy
@@ -335,8 +342,9 @@ def list_images(src: str):
         return [ln.strip() for ln in f if ln.strip()]
 
 
-def write_pngs(soft: Dict[str, np.ndarray], png_dir: str, threads: int = 4) -> None:
-    """the soft maps as 8-bit greyscale PNGs (<file stem>.png: what the external SOD toolkits read), on a small host thread pool"""
+def write_pngs(soft: Dict[str, object], png_dir: str, threads: int = 4) -> None:
+    """the soft maps as 8-bit greyscale PNGs (<file stem>.png: what the external SOD toolkits read), on a small host thread pool: an
+    array is encoded by Pillow, ``bytes`` (a file the device encoded, output "soft_png") are written as they are"""
     from concurrent.futures import ThreadPoolExecutor
     from PIL import Image
     os.makedirs(png_dir, exist_ok=True)
@@ -345,7 +353,12 @@ def write_pngs(soft: Dict[str, np.ndarray], png_dir: str, threads: int = 4) -> N
 
     def one(item):
         name, arr = item
-        Image.fromarray(np.ascontiguousarray(arr, np.uint8)).save(os.path.join(png_dir, os.path.splitext(name)[0] + ".png"))
+        path = os.path.join(png_dir, os.path.splitext(name)[0] + ".png")
+        if isinstance(arr, bytes):
+            with open(path, "wb") as f:
+                f.write(arr)
+        else:
+            Image.fromarray(np.ascontiguousarray(arr, np.uint8)).save(path)
 
     with ThreadPoolExecutor(max_workers=max(1, threads)) as pool:
         list(pool.map(one, soft.items()))
@@ -362,6 +375,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--batch_size", type=int, default=64)
     ap.add_argument("--refine", type=str, default=None, choices=["bilateral"])
     ap.add_argument("--png_dir", type=str, default=None, help="also write the soft maps as 8-bit PNGs into this directory")
+    ap.add_argument("--png_encoder", type=str, default="host", choices=list(PNG_ENCODERS),
+                    help="device: the PNG files of --png_dir are encoded on the GPU (same pixels, other bytes than Pillow's)")
     ap.add_argument("--objects_out", type=str, default=None, help="also write the masks' objects (boxes, areas, centroids, scores, "
                     "per-object RLE) as JSON: {file name: {...}}")
     ap.add_argument("--connectivity", type=int, default=8, choices=[4, 8])
@@ -386,8 +401,9 @@ def main(argv=None):
     model = get_model("maskformer", configs=cfg)
     load_checkpoint(model, args.p_state_dict)
     model = model.to(device).eval()
-    pred = SaliencyPredictor(model, device=device, batch_size=args.batch_size, decode=args.decode)
-    outputs = ("rle",) + (("soft",) if args.png_dir else ()) + (("objects",) if args.objects_out else ())
+    pred = SaliencyPredictor(model, device=device, batch_size=args.batch_size, decode=args.decode, png_encoder=args.png_encoder)
+    soft = "soft_png" if pred.png_encoder == "device" else "soft"
+    outputs = ("rle",) + ((soft,) if args.png_dir else ()) + (("objects",) if args.objects_out else ())
     objects = dict(connectivity=args.connectivity, min_area=args.min_area, max_objects=args.max_objects) if args.objects_out else None
     res = pred._run(list_images(args.images), args.img_size, getattr(cfg, "scale_factor", 2), outputs, args.refine, objects=objects)
     with open(args.out, "w") as f:
@@ -396,7 +412,7 @@ def main(argv=None):
         with open(args.objects_out, "w") as f:
             json.dump(res["objects"], f, separators=(",", ":"))
     if args.png_dir:
-        write_pngs(res["soft"], args.png_dir)
+        write_pngs(res[soft], args.png_dir)
     print(f"{len(res['rle'])} masks -> {args.out}" + (f", PNGs -> {args.png_dir}" if args.png_dir else "") +
           (f", objects -> {args.objects_out}" if args.objects_out else ""))
     return res
