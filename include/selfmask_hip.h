@@ -760,6 +760,59 @@ size_t sm_forward_workspace_bytes(const sm_weights* w, int32_t B, int32_t H, int
 int sm_maskformer_forward(const sm_weights* w, const sm_forward_io* io, void* workspace, size_t workspace_bytes,
                           void* stream);
 
+/* ---- dilated ResNet-50 backbone: the MoCo-v2 / SwAV feature branch of the pseudo-mask generator -------------------------------
+ * (mask_generator.pyc@L136-200 feature_types "mocov2" / "swav"; utils/misc.py:220-223 -> networks/resnet.py:8-56 ->
+ * resnet_backbone.py:42-105 "resnet50_dilated8" -> resnet_models.py:57-154).  Activations are NHWC, one row per pixel, fp32 or F16X2;
+ * every convolution is sm_gemm_w16 on rows that are read as they lie (1 x 1) or gathered tap by tap (3 x 3, strided 1 x 1). */
+
+/* im2col in the GEMM's operand format - nn.Conv2d(kernel_size=k, stride, dilation, padding) of resnet_models.py:64 (conv2) and :141-142
+ * (the strided 1 x 1 down-sample) as re-parameterised by resnet_backbone.py:72-85: in (B, H, W, Cin) F16X2 -> out (B, oh, ow, k*k*Cin)
+ * F16X2 with o = (n + 2 pad - dilation (k - 1) - 1) / stride + 1; row (b, oy, ox) = the k*k input rows (b, oy stride - pad + i dilation,
+ * ox stride - pad + j dilation), (i, j) row-major, end to end; taps outside image b are zeros.  k in {1, 3}, Cin % 8 == 0.  A copy of
+ * 16-byte vectors: bit-identical to the same gather on the host.  The matching weight is (Cout, kh, kw, Cin). */
+int sm_conv_gather_f16x2(const float* in, float* out, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t k, int32_t stride,
+                         int32_t dilation, int32_t pad, void* stream);
+/* the operand of prefix.conv1 (resnet_models.py:115: 7 x 7, stride 2, pad 3) from the normalised fp32 input x (B, 3, H, W):
+ * out (B, oh, ow, 160) F16X2, column c*49 + i*7 + j = x[b, c, 2 oy - 3 + i, 2 ox - 3 + j] - the (64, 3, 7, 7) weight flattened as it
+ * lies - zeros outside the image and in columns 147..159 (K padded to a multiple of 32) */
+int sm_resnet_stem_gather_f16x2(const float* x, float* out, int32_t B, int32_t H, int32_t W, void* stream);
+/* nn.MaxPool2d(kernel_size=3, stride=2, padding=1, ceil_mode=False) (resnet_models.py:120) on NHWC, C % 8 == 0: the padding never
+ * wins.  out (fp32) and out_f16x2 (the same values in F16X2): either may be NULL */
+int sm_maxpool3x3s2_nhwc_f32(const float* in, float* out, float* out_f16x2, int32_t B, int32_t H, int32_t W, int32_t C, void* stream);
+/* `out += residual; out = self.relu(out)` (resnet_models.py:90-91) behind a conv3 GEMM with the SM_EPI_RESIDUAL epilogue: src
+ * (rows, C) fp32 -> dst = relu(src) in fp32 (may be src itself) and dst_f16x2 = the same in F16X2; either may be NULL.  C % 8 == 0 */
+int sm_relu_split_f16x2(const float* src, float* dst, float* dst_f16x2, int64_t rows, int32_t C, void* stream);
+/* F.interpolate(scale_factor=scale, mode="bilinear", align_corners=True) of a channels-last map (mask_generator.pyc@L150-159 on the
+ * backbone's last map): in (B, gh, gw, C) -> up (B, scale gh, scale gw, C), C % 4 == 0 - sm_upsample_tokens_aligned_f32 with the
+ * channel count a parameter */
+int sm_upsample_nhwc_aligned_f32(const float* in, float* up, int32_t B, int32_t gh, int32_t gw, int32_t C, int32_t scale, void* stream);
+
+/* one convolution with its BatchNorm (eval, eps 1e-5) folded in on the host in fp64: w = W16 (sm_split_w16) of
+ * weight * gamma / sqrt(var + eps), rows (Cout, kh, kw, Cin) - the stem (64, 160): (Cin, kh, kw) as it lies, zero-padded -
+ * bias = beta - mean * gamma / sqrt(var + eps) (Cout floats), w_scale = the tensor's 2^-s */
+typedef struct sm_conv_weight {
+    const float* w;
+    const float* bias;
+    float w_scale;
+    int32_t reserved;
+} sm_conv_weight;
+typedef struct sm_resnet_block { /* Bottleneck, resnet_models.py:57-93; down.w == NULL where the block has no down-sample */
+    sm_conv_weight conv1, conv2, conv3, down;
+} sm_resnet_block;
+#define SM_RESNET50_BLOCKS 16 /* layers 1-4: 3 + 4 + 6 + 3 */
+typedef struct sm_resnet50_weights {
+    sm_conv_weight stem; /* prefix.conv1 + prefix.bn1 */
+    sm_resnet_block block[SM_RESNET50_BLOCKS];
+} sm_resnet50_weights;
+/* bytes of workspace sm_resnet50_forward needs (0: bad shape).  The largest region is the gathered operand of the widest 3 x 3
+ * convolution, B * oh * ow * 4608 * 4 bytes when dilated; it must stay below 4 GiB (sm_gemm_w16's operand limit) */
+size_t sm_resnet50_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t dilated);
+/* ResNet50.forward (networks/resnet.py:55-56 -> resnet_backbone.py:90-105, or :26-39 with dilated == 0): x (B, 3, H, W) fp32 -> the
+ * four feature maps, CHANNELS LAST: out1 (B, h1, w1, 256), out2 (.., 512), out3 (.., 1024), out4 (.., 2048), strides 4, 8, 8, 8
+ * (dilated) or 4, 8, 16, 32; any of them may be NULL.  Queues the whole sequence on `stream`; never synchronises or allocates. */
+int sm_resnet50_forward(const sm_resnet50_weights* w, const float* x, int32_t B, int32_t H, int32_t W, int32_t dilated, float* out1,
+                        float* out2, float* out3, float* out4, void* workspace, size_t workspace_bytes, void* stream);
+
 /* In-situ kernel timing of sm_maskformer_forward (measurement aid for bench.py; not part of the reference surface).
  * While enabled, every GEMM / attention / LayerNorm launch of a forward is bracketed by two HIP events recorded on the
  * forward's own stream; sm_forward_timing_read waits for them and returns one entry per kernel family (GEMMs by their

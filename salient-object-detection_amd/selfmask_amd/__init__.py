@@ -4,6 +4,7 @@ Host side mirrors the reference's Python surface; arithmetic runs in hand-writte
 ``include/selfmask_hip.h`` (``lib/libselfmask_hip.so``).
 """
 from .maskformer import MaskFormer, load_checkpoint  # noqa: F401
+from .resnet import ResNet50, resnet_features  # noqa: F401
 from .misc import get_model, set_seeds  # noqa: F401
 from .base_structure import BaseStructure  # noqa: F401
 from .streams import StreamRing  # noqa: F401

@@ -187,6 +187,21 @@ class SpectralArgs(C.Structure):
                 ("degree", C.c_int32), ("max_outer", C.c_int32), ("kmeans_max_iter", C.c_int32)]
 
 
+RESNET50_BLOCKS = 16
+
+
+class ConvWeight(C.Structure):
+    _fields_ = [("w", fp), ("bias", fp), ("w_scale", C.c_float), ("reserved", C.c_int32)]
+
+
+class ResnetBlock(C.Structure):
+    _fields_ = [("conv1", ConvWeight), ("conv2", ConvWeight), ("conv3", ConvWeight), ("down", ConvWeight)]
+
+
+class Resnet50Weights(C.Structure):
+    _fields_ = [("stem", ConvWeight), ("block", ResnetBlock * RESNET50_BLOCKS)]
+
+
 # every symbol include/selfmask_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "sm_version": (C.c_int, []),
@@ -266,6 +281,14 @@ SYMBOLS = {
     "sm_jpeg_probe": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(JpegInfo)]),
     "sm_jpeg_entropy_decode": (C.c_int, [C.c_char_p, C.c_size_t, fp, C.c_size_t, fp, C.POINTER(JpegInfo)]),
     "sm_jpeg_decode_batch_u8": (C.c_int, [fp, fp, C.c_int32, fp, fp, fp, fp]),
+    "sm_conv_gather_f16x2": (C.c_int, [fp, fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp]),
+    "sm_resnet_stem_gather_f16x2": (C.c_int, [fp, fp, C.c_int32, C.c_int32, C.c_int32, fp]),
+    "sm_maxpool3x3s2_nhwc_f32": (C.c_int, [fp, fp, fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp]),
+    "sm_relu_split_f16x2": (C.c_int, [fp, fp, fp, C.c_int64, C.c_int32, fp]),
+    "sm_upsample_nhwc_aligned_f32": (C.c_int, [fp, fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp]),
+    "sm_resnet50_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "sm_resnet50_forward": (C.c_int, [C.POINTER(Resnet50Weights), fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp, fp, fp, fp, fp,
+                                      C.c_size_t, fp]),
     "sm_forward_workspace_bytes": (C.c_size_t, [C.POINTER(Weights), C.c_int32, C.c_int32, C.c_int32]),
     "sm_maskformer_forward": (C.c_int, [C.POINTER(Weights), C.POINTER(ForwardIO), fp, C.c_size_t, fp]),
     "sm_forward_timing": (C.c_int, [C.c_int]),

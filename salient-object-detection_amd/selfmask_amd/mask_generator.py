@@ -12,8 +12,9 @@ one patch grid share a batch (the reference's DataLoader runs batch 1; images ar
 in a batch as alone): the crop to its own H x W happens inside the vote and the run-length kernels.  ``vote_mask`` (@L202-230) picks the candidate that
 agrees most with the others.  ``__call__`` (@L232-252) returns the winner per file name, run-length encoded.
 
-Differences kept on purpose: (1) only the ``"dino"`` feature type - the MoCo-v2 / SwAV ResNet-50 branches need backbones and weights that
-are absent from the reference repository, asking for them raises; (2) the encoder is the ``network`` handed in
+Differences kept on purpose: (1) only the ``"dino"`` feature type - the dilated ResNet-50 of the MoCo-v2 / SwAV branches is built
+(``selfmask_amd.resnet``: ``ResNet50``, ``resnet_features`` = what @L150-159 hands the clusterer), but the clusterers take 384-d points
+only and the checkpoints are absent from the reference repository, so asking for those types still raises; (2) the encoder is the ``network`` handed in
 (a ``selfmask_amd.MaskFormer`` whose encoder holds the DINO weights): the reference fetches them from the network at construction time
 (utils/misc.py:196,243), which must never happen here; (3) the reference encodes with ``pycocotools.mask.encode`` (absent from this
 image): ``rle_encode`` writes COCO's UNCOMPRESSED run-length form ({"size": [h, w], "counts": [n0, n1, ...]}, column-major, first run =

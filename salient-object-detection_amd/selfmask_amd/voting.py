@@ -9,7 +9,9 @@ in the shipped YAML: ``clustering_mode: "spectral"``, configs/duts-dino-k234-nq2
 csrc/spectral.hip: k-NN graph -> normalised Laplacian -> eigenvectors -> k-means, the algorithm scikit-learn's
 ``SpectralClustering(affinity="precomputed")`` evaluates, which is its third-party witness) and ``kmeans`` (the
 ``cluster_type="kmeans"`` option, csrc/cluster.hip); any other clusterer can be passed as a callable, as the reference's class
-takes one.  The ResNet-50 MoCo-v2 / SwAV feature branches are out of scope (SURVEY.md section 2 #11)."""
+takes one.  The MoCo-v2 / SwAV feature branches: their backbone and its features exist (``selfmask_amd.resnet``: ``ResNet50``,
+``resnet_features``: 2048-d points at stride 8), but both clusterers here are written for the DINO branch's 384-d points, so those
+branches are not wired in yet."""
 import ctypes as C
 from typing import Dict, Sequence, Tuple
 
