@@ -371,9 +371,11 @@ int sm_vote_masks_batch_u8(const uint8_t* masks, int32_t B, int32_t M, int32_t H
  * positions q = x * H + y (1 <= q < H W) whose pixel differs from the one before; info (B, 2) = {number of such positions (also when it
  * exceeds cap: only the first cap are stored), value of pixel 0}.  The counts of the uncompressed RLE are the differences of
  * [0, starts..., H W], with a leading 0 when pixel 0 is set.  sizes (device, (B, 2), or NULL): image b is the top-left sizes[b] = {H_b, W_b}
- * of its H x W plane, and its positions count in H_b. */
+ * of its H x W plane, and its positions count in H_b; an entry outside the plane leaves that image's outputs unwritten.  The chunked walk
+ * of sm_predict_masks_f32 (csrc/predict.hip) over a byte source: B <= 65535, H W <= 2^22, workspace: sm_predict_workspace_bytes(B, H W)
+ * bytes, 256-B aligned. */
 int sm_rle_runs_u8(const uint8_t* masks, int32_t B, int32_t H, int32_t W, const int32_t* sizes, int32_t* starts, int32_t cap, int32_t* info,
-                   void* stream);
+                   void* workspace, size_t workspace_bytes, void* stream);
 /* sm_vote_masks_batch_u8 for images of DIFFERENT sizes that share planes of H x W (images padded to one token grid, as
  * make_input_divisible pads each of them): sizes (device, (B, 2)) = {H_b, W_b} per image; candidates count only inside the top-left
  * H_b x W_b, and the filters use H_b, W_b - image b's results are those of sm_vote_masks_u8 on its cropped candidates.  NULL: as above. */

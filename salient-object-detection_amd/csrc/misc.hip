@@ -216,7 +216,7 @@ static inline int grid_for(int64_t work, int per_block = 256) {
 
 }  // namespace sm
 
-extern "C" int sm_version(void) { return 100; }
+extern "C" int sm_version(void) { return 101; }
 extern "C" const char* sm_last_error(void) { return sm::g_err; }
 
 static int im2col_impl(const float* img, float* cols, int32_t B, int32_t H, int32_t W, int32_t P, void* stream, bool split) {

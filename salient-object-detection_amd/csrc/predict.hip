@@ -13,7 +13,8 @@
 //   P3  predict_planes   row-major, four pixels per lane and one 4-byte store: the binary / soft planes, only when asked for
 // No workgroup waits on another and no atomic decides an order: the output is ascending by construction.  The selected mask is
 // staged in LDS once per workgroup when it has at most PR_LDS_FLOATS values and read through L2 otherwise.
-// sm_rle_runs_packed_u8 runs P1 / P2 with a byte load in place of the bilinear evaluation.
+// sm_rle_runs_packed_u8 and sm_rle_runs_u8 run P1 / P2 on byte planes (packed planes of different sizes; images in the top-left corner
+// of padded planes of one size), each workgroup's chunk of its plane staged in LDS in place of the bilinear evaluation.
 #include "common.h"
 
 // same discipline as eval.hip: no contraction, fused ops only where up_sample writes them
@@ -47,10 +48,10 @@ __device__ __forceinline__ void split_pos(int q, int H, float inv_h, int& x, int
 
 // ---- pixel sources: value of pixel (y, x) as 0 / 1 -------------------------------------------------------------------------
 // (MaskSrc, the selected query's mask up-sampled, comes from upsample.h)
-struct ByteSrc {  // a packed row-major 0 / non-zero plane
-    const unsigned char* __restrict__ p;
-    int W;
-    __device__ __forceinline__ bool operator()(int y, int x) const { return p[(int64_t)y * W + x] != 0; }
+struct TileSrc {  // a byte plane's column-major positions [base, ...) as a workgroup staged them in LDS (byte_runs_kernel)
+    const unsigned char* t;
+    int H, base;
+    __device__ __forceinline__ bool operator()(int y, int x) const { return t[x * H + y - base] != 0; }
 };
 
 // ---- the chunked walk --------------------------------------------------------------------------------------------------------
@@ -164,16 +165,40 @@ __global__ __launch_bounds__(PR_THREADS) void predict_runs_kernel(sm_predict_arg
     runs_chunk<EMIT>(src, im.H, npx, blockIdx.x, counts + (int64_t)b * units_max, a.starts + (int64_t)b * a.cap, a.cap, a.info + 2 * b);
 }
 
+// Both byte sources in one kernel.  images: packed planes, image b's H_b x W_b bytes at planes + px_off_b; null: padded planes of
+// Hp x Wp, image b the top-left sizes[b] = {H_b, W_b} (sizes null: all) of plane b.  A table or size entry that disagrees with what
+// the host sized the grid and the workspace from writes nothing.
+// Read where they lie, the 64 column-major positions of a step are bytes of 64 rows - 64 cache lines for 64 bytes.  So the workgroup
+// first copies its chunk (and the position before it) into LDS along the rows, where the chunk's columns of a row are neighbours: the
+// rows y0, y0 + 1, ... (wrapping at H) that the chunk touches, nc columns of each, and of those the positions inside the chunk.
 template <bool EMIT>
-__global__ __launch_bounds__(PR_THREADS) void packed_runs_kernel(const unsigned char* __restrict__ planes,
-                                                                 const sm_bilateral_image* __restrict__ images, int* __restrict__ counts,
-                                                                 int units_max, int* __restrict__ starts, int cap, int* __restrict__ info) {
+__global__ __launch_bounds__(PR_THREADS) void byte_runs_kernel(const unsigned char* __restrict__ planes, const sm_bilateral_image* __restrict__ images,
+                                                               int Hp, int Wp, const int* __restrict__ sizes, int* __restrict__ counts,
+                                                               int units_max, int* __restrict__ starts, int cap, int* __restrict__ info) {
+    __shared__ unsigned char tile[PR_CHUNK + 16];
     const int b = blockIdx.y;
-    const sm_bilateral_image im = images[b];
-    const int npx = im.H * im.W;
-    if (im.H <= 0 || im.W <= 0 || pr_units(npx) > units_max || (int64_t)blockIdx.x * PR_CHUNK >= npx) return;
-    const ByteSrc src{planes + im.px_off, im.W};
-    runs_chunk<EMIT>(src, im.H, npx, blockIdx.x, counts + (int64_t)b * units_max, starts + (int64_t)b * cap, cap, info + 2 * b);
+    int H = Hp, W = Wp, pitch = Wp;
+    const unsigned char* __restrict__ p = planes + (int64_t)b * Hp * Wp;
+    if (images) {
+        const sm_bilateral_image im = images[b];
+        H = im.H; W = pitch = im.W; p = planes + im.px_off;
+    } else if (sizes) {
+        H = sizes[2 * b]; W = sizes[2 * b + 1];
+        if (H > Hp || W > Wp) return;
+    }
+    const int npx = H * W;
+    if (H <= 0 || W <= 0 || pr_units(npx) > units_max || (int64_t)blockIdx.x * PR_CHUNK >= npx) return;
+    const int base = blockIdx.x ? blockIdx.x * PR_CHUNK - 1 : 0, end = base + PR_CHUNK + 1 < npx ? base + PR_CHUNK + 1 : npx;
+    const int x0 = base / H, y0 = base - x0 * H, nc = (end - 1) / H - x0 + 1, nr = end - base < H ? end - base : H;
+    const int dr = PR_THREADS / nc, dx = PR_THREADS - dr * nc;  // a thread's next (row, column): PR_THREADS further along the rows
+    for (int r = threadIdx.x / nc, xr = threadIdx.x - r * nc; r < nr;) {
+        const int y = y0 + r < H ? y0 + r : y0 + r - H, q = (x0 + xr) * H + y;
+        if (q >= base && q < end) tile[q - base] = p[(int64_t)y * pitch + x0 + xr];
+        r += dr; xr += dx;
+        if (xr >= nc) { xr -= nc; ++r; }
+    }
+    __syncthreads();
+    runs_chunk<EMIT>(TileSrc{tile, H, base}, H, npx, blockIdx.x, counts + (int64_t)b * units_max, starts + (int64_t)b * cap, cap, info + 2 * b);
 }
 
 // P3: groups of four packed bytes, aligned to 4 in the output buffer, one group per lane and pass: a wave writes 256 contiguous
@@ -297,7 +322,22 @@ extern "C" int sm_rle_runs_packed_u8(const uint8_t* planes, const sm_bilateral_i
     const int units_max = sm::pr_units(mx);
     const dim3 grid((mx + sm::PR_CHUNK - 1) / sm::PR_CHUNK, B);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(sm::packed_runs_kernel<false>, grid, dim3(sm::PR_THREADS), 0, st, planes, images_dev, (int*)workspace, units_max, starts, cap, info);
-    hipLaunchKernelGGL(sm::packed_runs_kernel<true>, grid, dim3(sm::PR_THREADS), 0, st, planes, images_dev, (int*)workspace, units_max, starts, cap, info);
+    hipLaunchKernelGGL(sm::byte_runs_kernel<false>, grid, dim3(sm::PR_THREADS), 0, st, planes, images_dev, 0, 0, nullptr, (int*)workspace, units_max, starts, cap, info);
+    hipLaunchKernelGGL(sm::byte_runs_kernel<true>, grid, dim3(sm::PR_THREADS), 0, st, planes, images_dev, 0, 0, nullptr, (int*)workspace, units_max, starts, cap, info);
     return sm::check_launch("sm_rle_runs_packed_u8");
+}
+
+extern "C" int sm_rle_runs_u8(const uint8_t* masks, int32_t B, int32_t H, int32_t W, const int32_t* sizes, int32_t* starts, int32_t cap,
+                              int32_t* info, void* workspace, size_t workspace_bytes, void* stream) {
+    SM_REQUIRE(masks && starts && info && workspace, "sm_rle_runs_u8: null pointer");
+    SM_REQUIRE(B > 0 && B <= 65535 && H > 0 && W > 0 && (int64_t)H * W <= sm::PR_MAX_PIXELS && cap > 0,
+               "sm_rle_runs_u8: %d masks of %dx%d, cap %d (at most 65535 masks of %d pixels)", B, H, W, cap, sm::PR_MAX_PIXELS);
+    SM_REQUIRE(((uintptr_t)workspace % 256) == 0 && workspace_bytes >= sm_predict_workspace_bytes(B, H * W),
+               "sm_rle_runs_u8: workspace too small or misaligned (sm_predict_workspace_bytes(B, H*W))");
+    const int units_max = sm::pr_units(H * W);
+    const dim3 grid((H * W + sm::PR_CHUNK - 1) / sm::PR_CHUNK, B);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(sm::byte_runs_kernel<false>, grid, dim3(sm::PR_THREADS), 0, st, masks, nullptr, H, W, sizes, (int*)workspace, units_max, starts, cap, info);
+    hipLaunchKernelGGL(sm::byte_runs_kernel<true>, grid, dim3(sm::PR_THREADS), 0, st, masks, nullptr, H, W, sizes, (int*)workspace, units_max, starts, cap, info);
+    return sm::check_launch("sm_rle_runs_u8");
 }

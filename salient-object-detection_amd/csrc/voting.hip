@@ -188,59 +188,7 @@ __global__ __launch_bounds__(64) void vote_finalize_kernel(const VoteBox* __rest
     }
 }
 
-// Run boundaries of a mask in column-major order (the order of COCO's run-length code): one workgroup per image, every lane a
-// contiguous stretch of positions q = x * H + y - count the changes, scan the counts over the workgroup, write the positions in place.
-__global__ __launch_bounds__(1024) void rle_runs_kernel(const unsigned char* __restrict__ masks, int Hp, int Wp, const int* __restrict__ sizes,
-                                                        int* __restrict__ starts, int cap, int* __restrict__ info) {
-    // the image's own H x W inside planes of Hp x Wp (sizes null: the whole plane); positions count in the image's H
-    const int H = sizes ? sizes[2 * blockIdx.x] : Hp, W = sizes ? sizes[2 * blockIdx.x + 1] : Wp;
-    const int64_t npx = (int64_t)H * W;
-    const unsigned char* m = masks + blockIdx.x * (int64_t)Hp * Wp;
-    int* out = starts + (int64_t)blockIdx.x * cap;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int np = (int)npx, per = (np + 1023) / 1024, q0 = tid * per, q1 = q0 + per < np ? q0 + per : np;
-    // the pixel before the stretch (pixel 0 itself for the first stretch: no change there)
-    const int qb = q0 > 0 ? q0 - 1 : 0;
-    const bool before = q0 < q1 ? m[(int64_t)(qb % H) * Wp + qb / H] != 0 : false;
-    auto walk = [&](auto&& on_change) {  // (y, x) advance with q: no division per pixel
-        int y = q0 % H, x = q0 / H;
-        bool prev = before;
-        for (int q = q0; q < q1; ++q) {
-            const bool v = m[(int64_t)y * Wp + x] != 0;
-            if (v != prev) on_change(q);
-            prev = v;
-            if (++y == H) { y = 0; ++x; }
-        }
-    };
-    int mine = 0;
-    walk([&](int) { ++mine; });
-    int inc = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += v;
-    }
-    __shared__ int wtot[16];
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    int at_out = inc - mine, total = 0;
-    for (int w = 0; w < 16; ++w) { at_out += w < wave ? wtot[w] : 0; total += wtot[w]; }
-    if (tid == 0) { info[2 * blockIdx.x] = total; info[2 * blockIdx.x + 1] = m[0] != 0 ? 1 : 0; }
-    walk([&](int q) {
-        if (at_out < cap) out[at_out] = q;
-        ++at_out;
-    });
-}
-
 }  // namespace sm
-
-extern "C" int sm_rle_runs_u8(const uint8_t* masks, int32_t B, int32_t H, int32_t W, const int32_t* sizes, int32_t* starts, int32_t cap,
-                              int32_t* info, void* stream) {
-    SM_REQUIRE(masks && starts && info, "sm_rle_runs_u8: null pointer");
-    SM_REQUIRE(B > 0 && H > 0 && W > 0 && cap > 0 && (int64_t)H * W < (int64_t)1 << 31, "sm_rle_runs_u8: %d masks of %dx%d, cap %d", B, H, W, cap);
-    hipLaunchKernelGGL(sm::rle_runs_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, masks, H, W, sizes, starts, cap, info);
-    return sm::check_launch("sm_rle_runs_u8");
-}
 
 extern "C" size_t sm_vote_workspace_bytes(int32_t M, int32_t H, int32_t W) {
     if (M <= 0 || M > 64 || H <= 0 || W <= 0) return 0;

@@ -8,6 +8,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _native as N
+from .runs import ObjectOptions, PendingRuns, batch_segments_to_rles, segments_to_rles  # noqa: F401  (part of this module's surface)
 
 
 def _stream() -> int:
@@ -459,9 +460,7 @@ class PackedImages:
     image b's H*W values at ``px_off[b]``.  ``bilateral_solver.MixedBatch`` is this table plus the solver's workspace layout."""
 
     def __init__(self, shapes, device, img_offsets=None):
-        import ctypes
-        import numpy as np
-        from .pipeline import _POOL
+        from .pipeline import upload_tables
         B = len(shapes)
         if B == 0:
             raise ValueError("an empty batch")
@@ -480,255 +479,75 @@ class PackedImages:
         self.B, self.n_pixels, self.max_pixels = B, po, max(h * w for h, w in self.shapes)
         self.img_bytes = max(self.host[b].img_off + h * w * 3 for b, (h, w) in enumerate(self.shapes))
         self._prepare()  # a subclass completes the host table (the solver's workspace offsets) before it is uploaded
-        staging = _POOL.get(ctypes.sizeof(self.host), torch.uint8)
-        staging.numpy()[:] = np.frombuffer(bytes(self.host), np.uint8)
-        self.dev = staging.to(device, non_blocking=True)
-        _POOL.release_after((staging,), torch.cuda.current_stream(device))
+        (self.dev,), _ = upload_tables([self.host], device)
 
     def _prepare(self) -> None:
         pass
 
 
-def _used_columns_host(starts: torch.Tensor, n: int):
-    """the first ``n`` columns of ``starts`` (device) as a numpy array: one asynchronous copy into page-locked memory on the
-    current stream and an event - the only wait is for that copy"""
-    host = torch.empty((starts.shape[0], max(n, 1)), dtype=torch.int32, pin_memory=True)
-    host.copy_(starts[:, :max(n, 1)], non_blocking=True)
-    done = torch.cuda.Event()
-    done.record(torch.cuda.current_stream(starts.device))
-    done.synchronize()
-    return host.numpy()
-
-
-def _runs_to_rle(info, starts, shapes):
-    """info (B, 2) {count, pixel 0}, starts (B, >= count) ascending column-major positions -> COCO uncompressed RLE dicts"""
-    import numpy as np
-    out = []
-    for b, (H, W) in enumerate(shapes):
-        n, first = int(info[b, 0]), int(info[b, 1])
-        counts = np.diff(np.concatenate([[0], starts[b, :n], [H * W]])).tolist()
-        out.append({"size": [H, W], "counts": ([0] + counts) if first else counts})
-    return out
-
-
-class ObjectOptions:
-    """what ``predict_masks(..., objects=)`` / ``rle_runs_packed_async(..., objects=)`` take (or a dict of the same keys):
-    ``connectivity`` 4 or 8, ``min_area`` drops smaller components, the ``max_objects`` (1 .. 64) largest are returned, ``masks``:
-    one COCO uncompressed RLE per returned object"""
-
-    def __init__(self, connectivity: int = 8, min_area: int = 0, max_objects: int = 16, masks: bool = True):
-        self.connectivity, self.min_area, self.max_objects, self.masks = int(connectivity), int(min_area), int(max_objects), bool(masks)
-        if self.connectivity not in (4, 8):
-            raise ValueError(f"objects: connectivity={connectivity!r} (4 or 8)")
-        if not 1 <= self.max_objects <= N.OBJ_MAX_OBJECTS:
-            raise ValueError(f"objects: max_objects={max_objects!r} (1 .. {N.OBJ_MAX_OBJECTS})")
-        if self.min_area < 0:
-            raise ValueError(f"objects: min_area={min_area!r}")
-
-    @staticmethod
-    def of(o):
-        if o is None or isinstance(o, ObjectOptions):
-            return o
-        return ObjectOptions(**dict(o))
-
-
-def _spans(flags: int):
-    """the two ``remove_long_masks`` tests of the reference's ``filter_masks`` on a box"""
-    return {"top_bottom": bool(flags & 1), "left_right": bool(flags & 2)}
-
-
-def batch_segments_to_rles(seg, n_segments, n_objects, shapes):
-    """seg (B, >= max n_segments, 3) rows {start q, length, rank} ascending in q, the first n_segments[b] of image b used -> per image
-    one COCO uncompressed RLE per rank 0 .. n_objects[b] - 1; segments of one object that abut (across a column end) merge into one
-    run.  One pass over the tables of the whole batch."""
-    import numpy as np
-    B, K = len(shapes), max(max(n_objects, default=0), 1)
-    used = (np.arange(seg.shape[1])[None, :] < np.asarray(n_segments)[:, None]) & (seg[:, :, 2] >= 0)
-    image = np.nonzero(used)[0]
-    rows = seg[used]
-    key = image * K + rows[:, 2]
-    order = np.argsort(key, kind="stable")  # by image and rank, ascending in q inside an object
-    rows, key = rows[order], key[order]
-    s = rows[:, 0].astype(np.int64)
-    e = s + rows[:, 1]
-    if not len(rows):
-        return [[] for _ in shapes]
-    joined = (s[1:] == e[:-1]) & (key[1:] == key[:-1])
-    opens, closes = np.concatenate([[True], ~joined]), np.concatenate([~joined, [True]])
-    bounds = np.stack([s[opens], e[closes]], axis=1).reshape(-1)  # run starts and ends, interleaved
-    counts = np.diff(bounds, prepend=0)
-    at = 2 * np.searchsorted(key[opens], np.arange(B * K + 1))  # where each object's bounds begin
-    first = at[:-1][at[:-1] < at[1:]]  # (slots without an object are empty)
-    counts[first] = bounds[first]  # an object's first count is its first start
-    counts, bounds, at = counts.tolist(), bounds.tolist(), at.tolist()
-    out = []
-    for b, (H, W) in enumerate(shapes):
-        rles = []
-        for k in range(n_objects[b]):
-            lo, hi = at[b * K + k], at[b * K + k + 1]
-            c = counts[lo:hi]
-            if bounds[hi - 1] != H * W:  # unless the object holds the last pixel, zeros close the code
-                c.append(H * W - bounds[hi - 1])
-            rles.append({"size": [int(H), int(W)], "counts": c})
-        out.append(rles)
-    return out
-
-
-def segments_to_rles(seg, n_objects: int, size):
-    """``batch_segments_to_rles`` for one image: seg (n, 3)"""
-    return batch_segments_to_rles(seg[None], [len(seg)], [n_objects], [size])[0]
-
-
-class _PendingObjects:
-    """sm_mask_objects queued behind the kernels that wrote ``starts`` / ``info``, its small outputs on their way into page-locked
-    memory; ``result()`` waits for those copies alone"""
-
-    def __init__(self, table, opts, starts, info, cap, mask_src=None):
-        import ctypes
-        import numpy as np
-        self.table, self.opts = table, opts
-        dev = starts.device
-        lib = N.load()
-        B, K = table.B, opts.max_objects
-        max_width = max(w for _, w in table.shapes)
-        wsb = lib.sm_mask_objects_workspace_bytes(B, cap, max_width)
-        if wsb == 0:
-            raise ValueError(f"objects: unsupported shape (an image wider than {N.OBJ_MAX_WIDTH} pixels?)")
-        self._ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        self._objects = torch.empty(B * K * ctypes.sizeof(N.Object), dtype=torch.uint8, device=dev)
-        self._summary = torch.empty((B, N.OBJ_SUMMARY_INTS), dtype=torch.int32, device=dev)
-        self._segments = torch.empty((B, lib.sm_mask_objects_seg_cap(cap, max_width), 3), dtype=torch.int32, device=dev) if opts.masks else None
-        a = N.ObjectsArgs()
-        a.starts, a.info, a.cap, a.images = starts.data_ptr(), info.data_ptr(), cap, table.dev.data_ptr()
-        self.scored = mask_src is not None
-        if self.scored:
-            masks, best, scale = mask_src
-            a.masks, a.mask_stride_b, a.best = masks.data_ptr(), masks.stride(0), best.data_ptr()
-            a.mh, a.mw, a.scale = masks.shape[2], masks.shape[3], scale
-        a.objects, a.summary, a.segments = self._objects.data_ptr(), self._summary.data_ptr(), _ptr(self._segments)
-        a.workspace, a.workspace_bytes = self._ws.data_ptr(), wsb
-        a.B, a.max_width = B, max_width
-        a.connectivity, a.min_area, a.max_objects = opts.connectivity, opts.min_area, K
-        N.check(lib.sm_mask_objects(a, ctypes.addressof(table.host), torch.cuda.current_stream(dev).cuda_stream), "sm_mask_objects")
-        self._objects_h = torch.empty(self._objects.shape, dtype=torch.uint8, pin_memory=True)
-        self._objects_h.copy_(self._objects, non_blocking=True)
-        self._summary_h = torch.empty(self._summary.shape, dtype=torch.int32, pin_memory=True)
-        self._summary_h.copy_(self._summary, non_blocking=True)
-        self._done = torch.cuda.Event()
-        self._done.record(torch.cuda.current_stream(dev))
-        self._dtype = np.dtype([(n, np.int64 if t is ctypes.c_int64 else np.int32) for n, t in N.Object._fields_])
-
-    def result(self):
-        """-> per image {"size", "n_components", "bbox", "spans", "objects": [...]} (boxes [x, y, w, h])"""
-        self._done.synchronize()
-        K = self.opts.max_objects
-        objs = self._objects_h.numpy().view(self._dtype).reshape(self.table.B, K)
-        f = {n: objs[n].tolist() for n in self._dtype.names}  # plain ints from here on
-        summ = self._summary_h.numpy()
-        assert not summ[:, 3].any(), "objects of a truncated run list (the caller finds the runs again first)"
-        all_rles, most = None, int(summ[:, 2].max(initial=0))
-        if self._segments is not None and most:
-            seg = _used_columns_host(self._segments.view(self.table.B, -1), 3 * most)
-            all_rles = batch_segments_to_rles(seg.reshape(self.table.B, most, 3), summ[:, 2], summ[:, 1].tolist(), self.table.shapes)
-        out = []
-        for b, ((H, W), row) in enumerate(zip(self.table.shapes, summ.tolist())):
-            ncomp, kept, nseg, _, x0, y0, x1, y1, flags, _area = row
-            rles = all_rles[b] if all_rles else [None] * kept
-            items = []
-            for k in range(kept):
-                area = f["area"][b][k]
-                items.append({"bbox": [f["x0"][b][k], f["y0"][b][k], f["x1"][b][k] - f["x0"][b][k] + 1, f["y1"][b][k] - f["y0"][b][k] + 1],
-                              "area": area, "centroid": (f["sum_x"][b][k] / area, f["sum_y"][b][k] / area),
-                              "score": f["mass"][b][k] / (255 * area) if self.scored else None,
-                              "first": f["first"][b][k], "spans": _spans(f["flags"][b][k]), "rle": rles[k]})
-            out.append({"size": [H, W], "n_components": ncomp, "bbox": [x0, y0, x1 - x0 + 1, y1 - y0 + 1] if x1 >= 0 else None,
-                        "spans": _spans(flags), "objects": items})
-        return out
-
-
 class PendingPredictions:
     """The finish of one batch (``predict_masks``), queued on the current stream: ``result()`` waits for THAT batch's copies only.
-    The inputs are kept until then - on overflow of ``cap`` the runs are found once more with room for the longest code - so the
+    The inputs are kept for it - on overflow of ``cap`` the runs are found once more with room for the longest code - so the
     caller must not let the stream overwrite them (a replayed graph's static outputs) before asking."""
 
     def __init__(self, mask_pred_last, objectness_last, table, scale, rle, binary, soft, cap, objects=None, soft_png=False):
+        import ctypes
         B, nq, mh, mw = mask_pred_last.shape
         dev = mask_pred_last.device
-        self._in = (mask_pred_last, objectness_last, table, float(scale))
-        self.table, self.cap = table, int(cap)
-        self.best = torch.empty(B, dtype=torch.int32, device=dev)
+        self.table, self.cap, self._rle = table, int(cap), rle
+        self.best = best = torch.empty(B, dtype=torch.int32, device=dev)
         self.binary = torch.empty(table.n_pixels, dtype=torch.uint8, device=dev) if binary else None
         self.soft = torch.empty(table.n_pixels, dtype=torch.uint8, device=dev) if soft or soft_png else None
-        self._starts = self._info = self._ws = self._objects = None
-        self._opts, self._rle = objects, rle
+        planes = (_ptr(self.binary), _ptr(self.soft))
+
+        def launch(starts, info, cap, ws, first):  # the planes are written the first time only
+            a = N.PredictArgs()
+            a.masks, a.mask_stride_b = mask_pred_last.data_ptr(), mask_pred_last.stride(0)
+            a.objectness, a.obj_stride_b = objectness_last.data_ptr(), objectness_last.stride(0)
+            a.images, a.best = table.dev.data_ptr(), best.data_ptr()
+            a.starts, a.info, a.cap = _ptr(starts), _ptr(info), cap
+            a.binary, a.soft = planes if first else (None, None)
+            a.workspace, a.workspace_bytes = _ptr(ws), 0 if ws is None else ws.numel()
+            a.B, a.nq, a.mh, a.mw, a.max_pixels, a.scale = B, nq, mh, mw, table.max_pixels, float(scale)
+            N.check(N.load().sm_predict_masks_f32(a, ctypes.addressof(table.host), torch.cuda.current_stream(dev).cuda_stream),
+                    "sm_predict_masks_f32")
+
+        self._runs = None
         if rle or objects is not None:  # the objects are found on the runs
-            self._starts = torch.empty((B, self.cap), dtype=torch.int32, device=dev)
-            self._info = torch.empty((B, 2), dtype=torch.int32, device=dev)
-        self._launch(self._starts, self._info, self.cap, self.binary, self.soft)
-        # best | info in one page-locked row per image; the planes in one buffer each
-        small = self.best[:, None] if self._starts is None else torch.cat([self.best[:, None], self._info], dim=1)
-        if objects is not None:
-            self._objects = _PendingObjects(table, objects, self._starts, self._info, self.cap, (mask_pred_last, self.best, float(scale)))
-        self._small_h = torch.empty(small.shape, dtype=torch.int32, pin_memory=True)
-        self._small_h.copy_(small, non_blocking=True)
-        self._planes_h = {}
-        for name, t in (("binary", self.binary), ("soft", self.soft if soft else None)):
+            self._runs = PendingRuns(launch, table.shapes, self.cap, table.max_pixels, dev,
+                                     objects and (table, objects, (mask_pred_last, best, float(scale))))
+        else:
+            launch(None, None, 0, None, True)
+        # best and the planes in one page-locked buffer each
+        self._host = {}
+        for name, t in (("best", best), ("binary", self.binary), ("soft", self.soft if soft else None)):
             if t is not None:
-                self._planes_h[name] = torch.empty(t.shape, dtype=torch.uint8, pin_memory=True)
-                self._planes_h[name].copy_(t, non_blocking=True)
+                self._host[name] = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+                self._host[name].copy_(t, non_blocking=True)
         self._done = torch.cuda.Event()
         self._done.record(torch.cuda.current_stream(dev))
         # the soft maps as PNG files, encoded where they lie: their raw pixels stay on the device
         self._png = png_encode_async(packed=(self.soft, table.px_off, [(h, w, 1) for h, w in table.shapes])) if soft_png else None
 
-    def _launch(self, starts, info, cap, binary, soft):
-        import ctypes
-        mask_pred, obj, table, scale = self._in
-        B, nq, mh, mw = mask_pred.shape
-        dev = mask_pred.device
-        lib = N.load()
-        a = N.PredictArgs()
-        a.masks, a.mask_stride_b = mask_pred.data_ptr(), mask_pred.stride(0)
-        a.objectness, a.obj_stride_b = obj.data_ptr(), obj.stride(0)
-        a.images, a.best = table.dev.data_ptr(), self.best.data_ptr()
-        a.starts, a.info, a.cap = _ptr(starts), _ptr(info), cap
-        a.binary, a.soft = _ptr(binary), _ptr(soft)
-        if starts is not None:
-            if self._ws is None:  # kept for the retry
-                wsb = lib.sm_predict_workspace_bytes(B, table.max_pixels)
-                if wsb == 0:
-                    raise ValueError("unsupported predict_masks shape (an image of more than 2^22 pixels?)")
-                self._ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-            a.workspace, a.workspace_bytes = self._ws.data_ptr(), self._ws.numel()
-        a.B, a.nq, a.mh, a.mw, a.max_pixels, a.scale = B, nq, mh, mw, table.max_pixels, scale
-        N.check(lib.sm_predict_masks_f32(a, ctypes.addressof(table.host), torch.cuda.current_stream(dev).cuda_stream),
-                "sm_predict_masks_f32")
+    # the reader's device buffers and pending objects under the names they have on this class (None without runs)
+    _starts = property(lambda self: getattr(self._runs, "_starts", None))
+    _info = property(lambda self: getattr(self._runs, "_info", None))
+    _objects = property(lambda self: getattr(self._runs, "_objects", None))
 
     def result(self) -> dict:
         """-> {"best": [query index], "rle": [COCO uncompressed RLE dict], "binary" / "soft": [(H_b, W_b) uint8 array], "soft_png":
         [the soft map as a PNG file, bytes], "objects": [the dict of ``_PendingObjects.result``]} (the keys asked for)"""
         self._done.synchronize()
-        small = self._small_h.numpy()
-        out = {"best": small[:, 0].tolist()}
-        if self._starts is not None:
-            info = small[:, 1:3]
-            longest = int(info[:, 0].max(initial=0))
-            starts = self._starts
-            if longest > self.cap:  # noise-like masks: once more, with room for the longest code
-                starts = torch.empty((info.shape[0], longest), dtype=torch.int32, device=starts.device)
-                self._launch(starts, self._info, longest, None, None)
-                if self._objects is not None:  # and the objects with them
-                    self._objects = _PendingObjects(self.table, self._opts, starts, self._info, longest, (self._in[0], self.best, self._in[3]))
-            if self._rle:
-                out["rle"] = _runs_to_rle(info, _used_columns_host(starts, longest), self.table.shapes)
-            if self._objects is not None:
-                out["objects"] = self._objects.result()
-        for name, h in self._planes_h.items():
-            flat = h.numpy()
-            out[name] = [flat[o:o + hh * ww].reshape(hh, ww) for o, (hh, ww) in zip(self.table.px_off, self.table.shapes)]
+        out = {"best": self._host["best"].tolist()}
+        if self._runs is not None:
+            rles, objects = self._runs.result(self._rle)
+            out.update({k: v for k, v in (("rle", rles), ("objects", objects)) if v is not None})
+        for name in ("binary", "soft"):
+            if name in self._host:
+                flat = self._host[name].numpy()
+                out[name] = [flat[o:o + hh * ww].reshape(hh, ww) for o, (hh, ww) in zip(self.table.px_off, self.table.shapes)]
         if self._png is not None:
             out["soft_png"] = self._png.result()
-        self._in = None
         return out
 
 
@@ -750,62 +569,47 @@ def predict_masks(mask_pred_last: torch.Tensor, objectness_last: torch.Tensor, t
                               ObjectOptions.of(objects), soft_png)
 
 
-class PendingPackedRuns:
-    """Run-length codes of packed 0/1 planes of different sizes (``rle_runs_packed_async``): ``result()`` -> one dict per image."""
-
-    def __init__(self, planes: torch.Tensor, table, cap: int, objects=None):
-        self.planes, self.table, self.cap, self._opts = planes, table, int(cap), objects
-        dev = planes.device
-        self._info = torch.empty((table.B, 2), dtype=torch.int32, device=dev)
-        self._ws = None
-        self._starts = self._launch(self.cap)
-        self._objects = _PendingObjects(table, objects, self._starts, self._info, self.cap) if objects is not None else None
-        self._info_h = torch.empty((table.B, 2), dtype=torch.int32, pin_memory=True)
-        self._info_h.copy_(self._info, non_blocking=True)
-        self._done = torch.cuda.Event()
-        self._done.record(torch.cuda.current_stream(dev))
-
-    def _launch(self, cap):
-        import ctypes
-        lib, t, dev = N.load(), self.table, self.planes.device
-        if self._ws is None:  # kept for the retry
-            wsb = lib.sm_predict_workspace_bytes(t.B, t.max_pixels)
-            if wsb == 0:
-                raise ValueError("unsupported rle_runs_packed shape (an image of more than 2^22 pixels?)")
-            self._ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        starts = torch.empty((t.B, cap), dtype=torch.int32, device=dev)
-        N.check(lib.sm_rle_runs_packed_u8(self.planes.data_ptr(), t.dev.data_ptr(), ctypes.addressof(t.host), t.B, starts.data_ptr(), cap,
-                                          self._info.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
-                                          torch.cuda.current_stream(dev).cuda_stream),
-                "sm_rle_runs_packed_u8")
-        return starts
+class PendingPackedRuns(PendingRuns):
+    """``rle_runs_packed_async``'s reader: ``result()`` -> one dict per image, or (those, the objects per image) when asked for them"""
 
     def result(self):
-        self._done.synchronize()
-        info = self._info_h.numpy()
-        longest = int(info[:, 0].max(initial=0))
-        starts = self._starts
-        if longest > self.cap:
-            starts = self._launch(longest)
-            if self._objects is not None:
-                self._objects = _PendingObjects(self.table, self._opts, starts, self._info, longest)
-        rles = _runs_to_rle(info, _used_columns_host(starts, longest), self.table.shapes)
-        return rles if self._objects is None else (rles, self._objects.result())
+        rles, objects = super().result()
+        return rles if objects is None else (rles, objects)
 
 
 def rle_runs_packed_async(planes: torch.Tensor, table, cap: int = 8192, objects=None) -> PendingPackedRuns:
     """Packed 0/1 uint8 planes (image b's H_b x W_b bytes at ``table.px_off[b]`` - the mixed bilateral solver's binary output) ->
     their run-length codes, without waiting (``.result()``): ``voting.rle_runs_async`` for images of different sizes.  With
     ``objects`` (as ``predict_masks``) ``result()`` is (codes, objects per image); a plane has no soft values, so ``score`` is None."""
+    import ctypes
     if not planes.is_cuda or planes.dtype != torch.uint8 or not planes.is_contiguous() or planes.numel() < table.n_pixels:
         raise RuntimeError("rle_runs_packed_async takes the packed uint8 planes of the batch on a HIP device (no CPU fallback)")
-    return PendingPackedRuns(planes, table, max(1, min(int(cap), table.max_pixels)), ObjectOptions.of(objects))
+
+    def launch(starts, info, cap, ws, first):
+        N.check(N.load().sm_rle_runs_packed_u8(planes.data_ptr(), table.dev.data_ptr(), ctypes.addressof(table.host), table.B,
+                                               starts.data_ptr(), cap, info.data_ptr(), ws.data_ptr(), ws.numel(),
+                                               torch.cuda.current_stream(planes.device).cuda_stream), "sm_rle_runs_packed_u8")
+
+    opts = ObjectOptions.of(objects)
+    return PendingPackedRuns(launch, table.shapes, max(1, min(int(cap), table.max_pixels)), table.max_pixels, planes.device,
+                             opts and (table, opts, None))
 
 
 # ---- the serving response's images: resized 8-bit mask + heat map (csrc/present.hip) ---------------------------------------------------
-_PRESENT_TABLES = {}   # (device, mh, mw, ((H, W, img_off), ...)) -> _PresentTables, the most recent _PRESENT_TABLES_MAX kept
-_PRESENT_TABLES_MAX = 64
+_PRESENT_TABLES = {}   # (device, mh, mw, ((H, W, img_off), ...)) -> _PresentTables, the most recent _TABLES_MAX kept
+_TABLES_MAX = 64
 _PRESENT_LUT = {}
+
+
+def _recent(cache: dict, key, make):
+    """``cache[key]``, made on first use, as the most recently used of the _TABLES_MAX entries the cache keeps"""
+    t = cache.pop(key, None)
+    if t is None:
+        t = make()
+    cache[key] = t  # most recently used last
+    while len(cache) > _TABLES_MAX:
+        cache.pop(next(iter(cache)))
+    return t
 
 
 class _PresentTables:
@@ -813,9 +617,8 @@ class _PresentTables:
     orders another stream's first use behind that upload).  Image b's pixels start at ``px_off[b]``, a multiple of 4."""
 
     def __init__(self, mh, mw, items, device):
-        import ctypes
         import numpy as np
-        from .pipeline import _POOL
+        from .pipeline import upload_tables
         from .present import pil_lanczos_coeffs
         B = len(items)
         self.host = (N.PresentImage * B)()
@@ -842,26 +645,11 @@ class _PresentTables:
                     d.coef_y, d.ksy = o, ks
         self.B, self.n_pixels, self.max_w = B, po, max(w for _, w, _ in items)
         self.shapes = [(h, w) for h, w, _ in items]
-        coef = _POOL.get(max(ci, 1), torch.int32)
-        coef.numpy()[:ci] = np.concatenate(parts) if parts else 0
-        descr = _POOL.get(ctypes.sizeof(self.host), torch.uint8)
-        descr.numpy()[:] = np.frombuffer(bytes(self.host), np.uint8)
-        self.coef, self.dev = coef.to(device, non_blocking=True), descr.to(device, non_blocking=True)
-        st = torch.cuda.current_stream(device)
-        _POOL.release_after((coef, descr), st)
-        self.ready = torch.cuda.Event()
-        self.ready.record(st)
+        (self.coef, self.dev), self.ready = upload_tables([np.concatenate(parts) if parts else np.zeros(1, np.int32), self.host], device)
 
 
 def _present_tables(mh, mw, items, device) -> _PresentTables:
-    key = (device, mh, mw, tuple(items))
-    t = _PRESENT_TABLES.pop(key, None)
-    if t is None:
-        t = _PresentTables(mh, mw, items, device)
-    _PRESENT_TABLES[key] = t  # most recently used last
-    while len(_PRESENT_TABLES) > _PRESENT_TABLES_MAX:
-        _PRESENT_TABLES.pop(next(iter(_PRESENT_TABLES)))
-    return t
+    return _recent(_PRESENT_TABLES, (device, mh, mw, tuple(items)), lambda: _PresentTables(mh, mw, items, device))
 
 
 def _present_lut(device) -> torch.Tensor:
@@ -962,8 +750,7 @@ def present_masks(masks: torch.Tensor, images, **kw):
 
 
 # ---- PNG files of images that are on the device (csrc/png.hip; the format: selfmask_amd/png.py) ---------------------------------------
-_PNG_TABLES = {}   # (device, ((H, W, C, pix_off), ...), filter_mode) -> _PngTables, the most recent _PNG_TABLES_MAX kept
-_PNG_TABLES_MAX = 64
+_PNG_TABLES = {}   # (device, ((H, W, C, pix_off), ...), filter_mode) -> _PngTables, the most recent _TABLES_MAX kept
 
 
 class _PngTables:
@@ -972,9 +759,7 @@ class _PngTables:
     ``sm_png_bound`` bytes of room."""
 
     def __init__(self, items, filter_mode, device):
-        import ctypes
-        import numpy as np
-        from .pipeline import _POOL
+        from .pipeline import upload_tables
         lib = N.load()
         B = len(items)
         self.host = (N.PngImage * B)()
@@ -990,24 +775,11 @@ class _PngTables:
             oo += (cap + 15) & ~15
         self.B, self.out_bytes = B, oo
         self.ws_bytes = lib.sm_png_workspace_bytes(self.host, B)
-        descr = _POOL.get(ctypes.sizeof(self.host), torch.uint8)
-        descr.numpy()[:] = np.frombuffer(bytes(self.host), np.uint8)
-        self.dev = descr.to(device, non_blocking=True)
-        st = torch.cuda.current_stream(device)
-        _POOL.release_after((descr,), st)
-        self.ready = torch.cuda.Event()
-        self.ready.record(st)
+        (self.dev,), self.ready = upload_tables([self.host], device)
 
 
 def _png_tables(items, filter_mode, device) -> _PngTables:
-    key = (device, tuple(items), filter_mode)
-    t = _PNG_TABLES.pop(key, None)
-    if t is None:
-        t = _PngTables(items, filter_mode, device)
-    _PNG_TABLES[key] = t  # most recently used last
-    while len(_PNG_TABLES) > _PNG_TABLES_MAX:
-        _PNG_TABLES.pop(next(iter(_PNG_TABLES)))
-    return t
+    return _recent(_PNG_TABLES, (device, tuple(items), filter_mode), lambda: _PngTables(items, filter_mode, device))
 
 
 class PendingPng:

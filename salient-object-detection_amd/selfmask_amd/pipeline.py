@@ -127,8 +127,8 @@ class PinnedPool:
                 if ent is not None:
                     ent[1] = None
 
-    def release_after(self, tensors, stream) -> None:
-        """The buffers behind ``tensors`` may be reused once the work queued on ``stream`` so far has finished."""
+    def release_after(self, tensors, stream):
+        """The buffers behind ``tensors`` may be reused once the work queued on ``stream`` so far has finished (-> the event behind it)."""
         ev = torch.cuda.Event()
         ev.record(stream)
         with self._lock:
@@ -136,9 +136,24 @@ class PinnedPool:
                 ent = self._by_ptr.get(t.data_ptr())  # a handed-out view starts at its buffer's first byte
                 if ent is not None:
                     ent[1] = ev
+        return ev
 
 
 _POOL = PinnedPool()
+
+
+def upload_tables(tables, device):
+    """Host tables (numpy arrays, or ctypes arrays as their bytes) -> (their device tensors, an event behind the uploads): each table
+    goes through a buffer of the page-locked pool and ONE asynchronous copy on the current stream, and the buffers return to the pool
+    behind those copies.  A table that other streams use has their first use wait for the event."""
+    staged = []
+    for t in tables:
+        a = t if isinstance(t, np.ndarray) else np.frombuffer(bytes(t), np.uint8)
+        buf = _POOL.get(a.size, getattr(torch, a.dtype.name))
+        buf.numpy()[:] = a
+        staged.append(buf)
+    out = [buf.to(device, non_blocking=True) for buf in staged]
+    return out, _POOL.release_after(staged, torch.cuda.current_stream(device))
 
 
 def pack_tables(shapes, S: Optional[int], pinned: bool = False):

@@ -18,6 +18,7 @@ from typing import Dict, Sequence, Tuple
 import torch
 
 from . import _native as N
+from .runs import PendingRuns, workspace_bytes
 
 # MaskGenerator.__init__ defaults and CLI choices (mask_generator.pyc@L21-38,255-294), pinned by tests/golden/evaluator_constants.json
 CLUSTER_TYPES = ("k-means", "spectral")
@@ -133,45 +134,6 @@ class PendingVotes:
         return out
 
 
-class PendingRuns:
-    """Run boundaries of a batch of masks (``rle_runs_async``), queued on a stream: ``result()`` waits for the batch's two small copies
-    and returns one COCO uncompressed run-length dict per mask ({"size": [H, W], "counts": [...]}: column-major runs, zeros first)."""
-
-    def __init__(self, masks: torch.Tensor, cap: int, sizes=None):
-        B, H, W = masks.shape
-        self.masks, self.cap = masks, cap
-        self.sizes = [(int(H), int(W))] * B if sizes is None else [(int(h), int(w)) for h, w in sizes]
-        dev = masks.device
-        self._starts = torch.empty((B, cap), dtype=torch.int32, device=dev)
-        self._info = torch.empty((B, 2), dtype=torch.int32, device=dev)
-        self._sizes_dev = None if sizes is None else _sizes_tensor(self.sizes, (H, W), dev)
-        N.check(N.load().sm_rle_runs_u8(masks.data_ptr(), B, H, W, None if sizes is None else self._sizes_dev.data_ptr(),
-                                        self._starts.data_ptr(), cap, self._info.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-                "sm_rle_runs_u8")
-        self._info_h = torch.empty((B, 2), dtype=torch.int32, pin_memory=True)
-        self._info_h.copy_(self._info, non_blocking=True)
-        self._done = torch.cuda.Event()
-        self._done.record(torch.cuda.current_stream(dev))
-
-    def result(self):
-        import numpy as np
-        self._done.synchronize()
-        info = self._info_h.numpy()
-        longest = int(info[:, 0].max(initial=0))
-        if longest > self.cap:  # more runs than the buffer holds (noise-like masks): once more on the device with room for the longest
-            again = PendingRuns(self.masks, longest, None if self._sizes_dev is None else self.sizes)
-            return again.result()
-        starts = self._starts[:, :max(longest, 1)].cpu().numpy()  # only as many columns as the longest code needs
-        out = []
-        for b in range(info.shape[0]):
-            n, first = int(info[b, 0]), int(info[b, 1])
-            H, W = self.sizes[b]
-            bounds = np.concatenate([[0], starts[b, :n], [H * W]])
-            counts = np.diff(bounds).tolist()
-            out.append({"size": [H, W], "counts": ([0] + counts) if first else counts})
-        return out
-
-
 def _sizes_tensor(sizes, plane, dev) -> torch.Tensor:
     """[(H_b, W_b)] -> (B, 2) int32 on the device, checked against the planes they are cut from"""
     t = torch.tensor(sizes, dtype=torch.int32).reshape(-1, 2)
@@ -180,15 +142,33 @@ def _sizes_tensor(sizes, plane, dev) -> torch.Tensor:
     return t.to(dev, non_blocking=True)
 
 
-def rle_runs_async(masks: torch.Tensor, cap: int = 8192, sizes=None) -> PendingRuns:
+class PendingPaddedRuns(PendingRuns):
+    """``rle_runs_async``'s reader: ``result()`` -> one COCO uncompressed run-length dict per mask ({"size": [H, W], "counts": [...]}:
+    column-major runs, zeros first)"""
+
+    def result(self):
+        return super().result()[0]
+
+
+def rle_runs_async(masks: torch.Tensor, cap: int = 8192, sizes=None) -> PendingPaddedRuns:
     """masks (B, H, W) uint8 on a HIP device (non-zero = set) -> their run-length codes, without waiting (``.result()``).  What
     ``mask_generator.rle_encode`` computes on the host, from the run boundaries the device finds (``sm_rle_runs_u8``).  ``sizes``
-    [(H_b, W_b)]: image b is the top-left H_b x W_b of its plane."""
+    [(H_b, W_b)]: image b is the top-left H_b x W_b of its plane.  At most 65535 planes of 2^22 pixels (ValueError)."""
     if not masks.is_cuda:
         raise RuntimeError("rle_runs_async (MI355X) needs its masks on a HIP device; mask_generator.rle_encode is the host form")
+    assert masks.dim() == 3
+    B, H, W = masks.shape
+    workspace_bytes(B, H * W)  # refuses what the walk does not take before anything is launched
     m = masks.to(torch.uint8).contiguous()
-    assert m.dim() == 3
-    return PendingRuns(m, int(min(cap, max(1, m.shape[1] * m.shape[2]))), sizes)
+    shapes = [(int(H), int(W))] * B if sizes is None else [(int(h), int(w)) for h, w in sizes]
+    sizes_dev = None if sizes is None else _sizes_tensor(shapes, (H, W), m.device)
+
+    def launch(starts, info, cap, ws, first):
+        N.check(N.load().sm_rle_runs_u8(m.data_ptr(), B, H, W, None if sizes_dev is None else sizes_dev.data_ptr(), starts.data_ptr(), cap,
+                                        info.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(m.device).cuda_stream),
+                "sm_rle_runs_u8")
+
+    return PendingPaddedRuns(launch, shapes, int(min(cap, max(1, H * W))), H * W, m.device)
 
 
 def vote_mask_batch_async(batch_pred_masks: torch.Tensor, remove_long_masks: bool = True, remove_small_large_masks: bool = False,

@@ -3,8 +3,11 @@
 Steps, each a child process of its own under its own time limit (a step that fails or runs out of time ends the run):
   finish   the fused finish (sm_predict_masks_f32: run boundaries only) against the composition of the kernels it replaces, in one
            process, the two sides alternating: sm_pick_mask_f32 -> sm_upsample_selected_native_f64 -> threshold into uint8 planes ->
-           sm_rle_runs_u8.  128 images of 300 x 400 and 8 images of 1080 x 1920 at P = 16 (masks 38 x 50 and 136 x 240, scale 8).
+           sm_rle_runs_u8 (its run step is by now the fused side's own chunked walk over a byte source: what is compared is the
+           composition).  128 images of 300 x 400 and 8 images of 1080 x 1920 at P = 16 (masks 38 x 50 and 136 x 240, scale 8).
            Device events around one call, 3 warm-up and 30 timed repetitions: min / median / max.  All buffers are allocated beforehand.
+  rle      voting.rle_runs_async on padded planes of blob masks, the same two shapes: wall clock from the call to .result(), and
+           device events around the call alone (the walk and the copy of its 8 bytes per image).
   e2e      images/s of SaliencyPredictor from files (synthetic 300-400 px set) beside the evaluator's bucketed native rate on the
            same files in the same process, wall clock.  Both are bound by the host's decode above a few thousand images/s.
 
@@ -22,7 +25,7 @@ import time
 
 ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 sys.path.insert(0, os.path.join(ROOT, "salient-object-detection_amd"))
-STEPS = {"finish": 240, "e2e": 420}  # seconds
+STEPS = {"finish": 240, "rle": 120, "e2e": 420}  # seconds
 WARMUP, REPS = 3, 30
 
 
@@ -72,7 +75,7 @@ def step_finish():
         rows = torch.zeros((B, 16), dtype=torch.float32, device=dev)
         target = torch.empty(B * H * W, dtype=torch.float64, device=dev)
         planes = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
-        starts2, info2 = torch.empty_like(starts), torch.empty_like(info)
+        starts2, info2, ws2 = torch.empty_like(starts), torch.empty_like(info), torch.empty_like(ws)
 
         def composed():
             N.check(lib.sm_pick_mask_f32(m.data_ptr(), m.stride(0), o.data_ptr(), o.stride(0), picked.data_ptr(), best2.data_ptr(), B, nq,
@@ -81,7 +84,8 @@ def step_finish():
             N.check(lib.sm_upsample_selected_native_f64(m.data_ptr(), m.stride(0), rows.data_ptr(), 14, table.dev.data_ptr(), target.data_ptr(),
                                                         B, mh, mw, scale, H * W, st()), "sm_upsample_selected_native_f64")
             torch.gt(target.view(B, H, W), 0.5, out=planes.view(torch.bool))
-            N.check(lib.sm_rle_runs_u8(planes.data_ptr(), B, H, W, None, starts2.data_ptr(), cap, info2.data_ptr(), st()), "sm_rle_runs_u8")
+            N.check(lib.sm_rle_runs_u8(planes.data_ptr(), B, H, W, None, starts2.data_ptr(), cap, info2.data_ptr(), ws2.data_ptr(), wsb,
+                                       st()), "sm_rle_runs_u8")
 
         ms = {"fused": [], "composed": []}
         for rep in range(WARMUP + REPS):
@@ -100,6 +104,40 @@ def step_finish():
         print(f"  fused    (sm_predict_masks_f32)                      {_stats(ms['fused'])}")
         print(f"  composed (pick -> upsample f64 -> threshold -> rle)  {_stats(ms['composed'])}")
         print(f"  composed / fused (medians) = {np.median(ms['composed']) / np.median(ms['fused']):.2f}x", flush=True)
+
+
+def step_rle():
+    import numpy as np
+    import torch
+    from selfmask_amd.voting import rle_runs_async
+    dev = torch.device("cuda:0")
+    for B, (H, W) in ((128, (300, 400)), (8, (1080, 1920))):
+        rng = np.random.Generator(np.random.PCG64(B))
+        yy, xx = np.mgrid[:H, :W].astype(np.float32)
+        planes = np.zeros((B, H, W), np.uint8)
+        for b in range(B):  # three blobs per image
+            for _ in range(3):
+                cy, cx, r = rng.uniform(.1, .9) * H, rng.uniform(.1, .9) * W, rng.uniform(.06, .2) * min(H, W)
+                planes[b] |= ((yy - cy) ** 2 + (xx - cx) ** 2 <= r * r).astype(np.uint8)
+        p = torch.from_numpy(planes).to(dev)
+        wall, device = [], []
+        for rep in range(WARMUP + REPS):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            codes = rle_runs_async(p).result()
+            if rep >= WARMUP:
+                wall.append((time.perf_counter() - t) * 1e3)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            pend = rle_runs_async(p)
+            e1.record()
+            e1.synchronize()
+            if rep >= WARMUP:
+                device.append(e0.elapsed_time(e1))
+            assert pend.result() == codes
+        print(f"rle_runs_async, {B} planes of {H} x {W}, longest code {max(len(c['counts']) for c in codes)} runs")
+        print(f"  call -> host result          {_stats(wall)}")
+        print(f"  the call alone (device events) {_stats(device)}", flush=True)
 
 
 def step_e2e():
@@ -146,7 +184,7 @@ def main():
     ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "predict_bench.log"))
     args = ap.parse_args()
     if args.step:
-        {"finish": step_finish, "e2e": step_e2e}[args.step]()
+        {"finish": step_finish, "rle": step_rle, "e2e": step_e2e}[args.step]()
         return 0
     with open(args.log, "w") as log:
         for step, limit in STEPS.items():

@@ -156,3 +156,32 @@ def test_images_of_different_sizes_in_one_batch():
             kept = [ref_map[k] for k in range(len(ref_map))]
             assert torch.equal(pend.iou.cpu()[b][kept][:, kept], table)
             assert codes[b] == rle_encode(ref_mask.numpy())
+
+
+def test_run_walk_seams_through_padded_planes():
+    """The chunked walk's seams through sm_rle_runs_u8's padded source: planes of 130 x 128 (16 640 positions: two workgroups, five wave
+    ranges), images of seven sizes in their top-left corners with random bytes outside, and per size the column-major patterns all zero,
+    all set, noise, alternating (npx - 1 boundaries: more than cap, so the walk runs again) and a single step at the positions where a
+    64-lane step, a wave range and a workgroup end.  Codes equal mask_generator.rle_encode of the crops, with cap 8192 and 4."""
+    from selfmask_amd.mask_generator import rle_encode
+    from selfmask_amd.voting import rle_runs_async
+    rng = np.random.Generator(np.random.PCG64(130128))
+    Hp, Wp = 130, 128
+    planes, sizes = [], []
+    for h, w in [(130, 128), (128, 128), (64, 64), (65, 63), (1, 1), (130, 1), (1, 128)]:
+        npx = h * w
+        flats = [np.zeros(npx, bool), np.ones(npx, bool), rng.random(npx) < 0.5, np.arange(npx) % 2 == 1]
+        flats += [np.arange(npx) >= q for q in (63, 64, 4095, 4096, 16384) if q < npx]
+        for f in flats:
+            plane = rng.integers(0, 256, size=(Hp, Wp), dtype=np.uint8)                   # rubbish outside the image
+            plane[:h, :w] = f.reshape(w, h).T * rng.integers(1, 256, size=(h, w), dtype=np.uint8)  # any non-zero byte is set
+            planes.append(plane)
+            sizes.append((h, w))
+    assert len(planes) == 46
+    want = [rle_encode(p[:h, :w]) for p, (h, w) in zip(planes, sizes)]
+    assert max(len(c["counts"]) for c in want) == Hp * Wp  # the alternating pattern of the full plane
+    masks = torch.from_numpy(np.stack(planes)).to(DEV)
+    for cap in (8192, 4):
+        got = rle_runs_async(masks, cap=cap, sizes=sizes).result()
+        for b in range(len(planes)):
+            assert got[b] == want[b], (b, sizes[b], cap)

@@ -200,3 +200,22 @@ def test_argument_validation_without_gpu():
     assert lib.sm_mask_objects(a, host, None) == -1 and b"image 0" in lib.sm_last_error()
     a.max_width, a.workspace_bytes = 4, 0
     assert lib.sm_mask_objects(a, host, None) == -1 and b"workspace" in lib.sm_last_error()
+
+
+@pytest.mark.parametrize("h,w", [(1, 1), (1, 9), (5, 1), (37, 53)])
+def test_host_decoder_of_run_boundaries_equals_rle_encode(h, w):
+    """the one place that turns {count, pixel 0} + ascending starts into COCO counts, fed the restatement's boundaries (what the device
+    walk writes), rows padded as the device's ``starts`` buffer is"""
+    from selfmask_amd.mask_generator import rle_encode
+    from selfmask_amd.runs import _runs_to_rle
+    yy, xx = np.mgrid[:h, :w]
+    blob = ((((yy - h * 0.4) / max(1.0, h * 0.3)) ** 2 + ((xx - w * 0.55) / max(1.0, w * 0.25)) ** 2) <= 1).astype(np.uint8)
+    first = blob.copy()
+    first[0, 0] = 200
+    planes = [blob, first, np.zeros((h, w), np.uint8), np.ones((h, w), np.uint8)]
+    bounds = [R.run_boundaries(p) for p in planes]
+    info = np.array([[len(s), p0] for s, p0 in bounds], np.int32)
+    starts = np.full((len(planes), max(int(info[:, 0].max()), 1) + 3), -7, np.int32)  # what lies past a row's count is not read
+    for b, (s, _) in enumerate(bounds):
+        starts[b, :len(s)] = s
+    assert _runs_to_rle(info, starts, [(h, w)] * len(planes)) == [rle_encode(p) for p in planes]

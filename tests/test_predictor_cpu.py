@@ -95,6 +95,23 @@ def test_validation_without_gpu():
     assert lib.sm_rle_runs_packed_u8(256, 256, C.addressof(table), 0, 256, 16, 256, 256, 0, None) == -1
 
 
+def test_padded_runs_validation_without_gpu():
+    """sm_rle_runs_u8 walks with the predictor's workspace: a missing, misaligned or short one and a plane the walk does not take are
+    refused on the host, with a message"""
+    lib = N.load()
+    need = lib.sm_predict_workspace_bytes(2, 64 * 80)
+
+    def call(H, W, ws, nbytes):  # the pointers are never dereferenced: every case is refused first
+        return lib.sm_rle_runs_u8(256, 2, H, W, None, 256, 16, 256, ws, nbytes, None)
+
+    assert call(64, 80, None, need) == -1 and "null pointer" in _err(lib)
+    assert call(64, 80, 256 + 64, need) == -1 and "misaligned" in _err(lib)
+    assert call(64, 80, 256, need - 1) == -1 and "too small" in _err(lib)
+    assert call(1, (1 << 22) + 1, 256, 1 << 30) == -1 and "4194304 pixels" in _err(lib)
+    assert call(2049, 2048, 256, 1 << 30) == -1 and "4194304 pixels" in _err(lib)
+    assert lib.sm_rle_runs_u8(256, 65536, 4, 4, None, 256, 16, 256, 256, 1 << 30, None) == -1 and "65535 masks" in _err(lib)
+
+
 def test_workspace_bytes_positive_and_monotone():
     lib = N.load()
     prev_b = 0
