@@ -432,6 +432,19 @@ typedef struct sm_spectral_args {
 } sm_spectral_args;
 size_t sm_spectral_workspace_bytes(int32_t B, int32_t n, int32_t n_neighbors, int32_t kw); /* 0 = unsupported shape */
 int sm_spectral_cluster_f32(const sm_spectral_args* args, void* stream);
+/* The same clusterer for features (B, n, D), D = 384 (the DINO tokens) or 2048 (the last map of the dilated ResNet-50 of the MoCo-v2 /
+ * SwAV types): only the k-NN lists depend on D.  The two functions above are the D = 384 call of these; any other D is SM_EINVAL
+ * (workspace: 0).  Above 8192 points the lists come from sm_knn_f32's method 0 (the workspace stays linear in n). */
+size_t sm_spectral_workspace_bytes_dim(int32_t B, int32_t n, int32_t D, int32_t n_neighbors, int32_t kw);
+int sm_spectral_cluster_dim_f32(const sm_spectral_args* args, int32_t D, void* stream);
+/* The neighbour lists alone: features (B, n, D) fp32, D = 384 or 2048 -> idx (B, n, min(n_neighbors - 1, n - 1)) int32, for every
+ * point its nearest OTHER points by (squared Euclidean distance, index), nearest first; fp32-grade products (three f16 MFMA products).
+ * method: 0 = as the clusterer chooses, 1 = Gram matrix (whole to 8192 points, above in slabs of 2048 rows, each selected from before
+ * the next is formed), 2 = streaming (no n x n array).  n <= 32768.  16 <= n, n % 4 == 0, n_neighbors 2..33.  workspace: sm_knn_workspace_bytes of the same arguments
+ * (0 = unsupported), 256-B aligned. */
+size_t sm_knn_workspace_bytes(int32_t B, int32_t n, int32_t D, int32_t n_neighbors, int32_t method);
+int sm_knn_f32(const float* features, int32_t B, int32_t n, int32_t D, int32_t n_neighbors, int32_t method, int32_t* idx, void* workspace,
+               size_t workspace_bytes, void* stream);
 
 /* ---- bilateral-solver refinement ---------------------------------------------------- */
 typedef struct sm_bilateral_args {

@@ -4,7 +4,8 @@
 // affinity + eigendecomp").  The reference's `clusterings` module exists in NO form in its repository: PARITY UNPINNED.  What is
 // built is normalised spectral clustering as the paper names it (arXiv 2203.12614 section 3.1), in the exact form scikit-learn's
 // SpectralClustering(affinity="precomputed") evaluates - the third-party witness of oracle/cluster_oracle.py:
-//   1. Gram matrix G = F F^T of the n x 384 features on the matrix cores (sm_gemm_f16x2: fp32-grade products)
+//   1. Gram matrix G = F F^T of the n x D features on the matrix cores (sm_gemm_f16x2: fp32-grade products); D = 384 (the DINO
+//      tokens) or 2048 (the ResNet maps of the MoCo-v2 / SwAV types) - only steps 1-2 depend on D
 //   2. k-NN: for every point the n_neighbors - 1 nearest others by (|f_i - f_j|^2, j)            [knn_select_kernel]
 //   3. W = (C + C^T) / 2 (C = connectivity, self loops dropped): per point its own list, then the points that list it, in O(n m)
 //                                                    [knn_indegree / knn_lists_scan / knn_reverse_scatter / knn_reverse_sort]
@@ -13,8 +14,10 @@
 //      u_i = v_i / sqrt(d_i)                                                                        [spectral_embed_kernel]
 //   5. k-means on the first k embedding columns for every requested k (ONE eigen-solve serves all)  [kmeans_embed_kernel]
 // Every sum runs in a fixed order (no floating-point atomics): labels are a function of the input alone.
-// Above 8192 points (to 32768) steps 1-2 become a streaming k-NN that never forms the Gram matrix [knn_stream_kernel]: the workspace
-// is linear in n.
+// Above 8192 points (to 32768) the workspace stays linear in n.  At D = 384 steps 1-2 become a streaming k-NN that never forms the
+// Gram matrix [knn_stream_kernel: the query fragments in registers].  At D = 2048 the matrix is formed, and selected from, in slabs
+// of 2048 rows: measured faster than the streaming kernel of that width [knn_stream_chunked_kernel: products accumulated over chunks
+// of 64 features], which stays available.  Steps 1-2 alone are sm_knn_f32, with the path as an argument.
 #include "common.h"
 #include <mutex>
 #include <set>
@@ -34,6 +37,7 @@ constexpr int SP_WAVES = SP_THREADS / 64;
 constexpr int SP_MAXM = 32;      // neighbours kept per point (n_neighbors - 1)
 constexpr int SP_MAXN = 8192;    // points per image on the Gram-matrix path
 constexpr int SP_MAXN_L = 32768; // points per image on the streaming path (8192 < n: no n x n array)
+constexpr int SP_DIM_RESNET = 2048;  // features per point of a ResNet type (SM_EMBED = 384: the DINO tokens)
 
 __device__ __forceinline__ double shfl_d(double v, int src) {
     const unsigned long long u = __double_as_longlong(v);
@@ -106,15 +110,16 @@ __device__ __forceinline__ void block_sum(double (&v)[NV], double* scratch) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// 2. k-NN selection: one wave per row of the Gram matrix.  key_j = G_jj - 2 G_ij orders the points like |f_i - f_j|^2 (G_ii is
+// 2. k-NN selection: one wave per row of the Gram matrix (or of a slab of its rows).  key_j = G_jj - 2 G_ij orders the points like |f_i - f_j|^2 (G_ii is
 // common to the row).  Every lane keeps the CAP smallest (key, j) of its strided share in registers (sorted, insertion by
 // compare-select), then the wave merges the 64 sorted lists: CAP... m rounds of a 64-lane arg-min over the list heads.
 template <int CAP>
 __global__ __launch_bounds__(256) void knn_select_kernel(const float* __restrict__ gram_all, const float* __restrict__ sq_all, int n, int m,
-                                                         int* __restrict__ idx_all) {
-    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= n) return;
-    const float* g = gram_all + ((int64_t)blockIdx.y * n + row) * n;
+                                                         int* __restrict__ idx_all, int row0, int rows) {
+    // (gram_all holds rows row0 .. row0 + rows of every image's matrix: the whole of it, or one slab)
+    const int lane = threadIdx.x & 63, slot = blockIdx.x * 4 + (threadIdx.x >> 6), row = row0 + slot;
+    if (slot >= rows) return;
+    const float* g = gram_all + ((int64_t)blockIdx.y * rows + slot) * n;
     const float* sq = sq_all + (int64_t)blockIdx.y * n;
     float key[CAP];
     int id[CAP];
@@ -202,16 +207,28 @@ __device__ __forceinline__ f32x4 ks_tile(const KsFrag& qf, const char* crow) {
     return g;
 }
 
-// sq_p = <f_p, f_p> as ks_tile forms it: the diagonal of the 16 x 16 tile of a block of 16 points with itself (one wave per block)
+// sq_p = <f_p, f_p> as ks_tile forms it: the diagonal of the 16 x 16 tile of a block of 16 points with itself (one wave per block),
+// the D / 32 steps in ascending order - for D features per point (384: the DINO tokens, 2048: the ResNet maps)
+template <int D>
 __global__ __launch_bounds__(256) void knn_sqnorm_kernel(const float* __restrict__ fs, int64_t rows, float* __restrict__ sq) {
-    const int lane = threadIdx.x & 63;
+    constexpr int ROWB = D * 4;
+    const int lane = threadIdx.x & 63, q = lane >> 4;
     const int64_t b0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16;
     if (b0 >= rows) return;  // whole waves
     const int64_t p = b0 + (lane & 15) < rows ? b0 + (lane & 15) : rows - 1;
-    const char* row = reinterpret_cast<const char*>(fs) + p * KS_ROWB;
-    KsFrag f;
-    ks_load_frag(row, f);
-    const f32x4 g = ks_tile(f, row);
+    const char* row = reinterpret_cast<const char*>(fs) + p * ROWB;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f}, crs = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 12
+    for (int s = 0; s < D / 32; ++s) {
+        const f16x8 h = *reinterpret_cast<const f16x8*>(row + (4 * s + q) * 32);
+        const f16x8 l = *reinterpret_cast<const f16x8*>(row + (4 * s + q) * 32 + 16);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(h, h, acc, 0, 0, 0);
+        crs = __builtin_amdgcn_mfma_f32_16x16x32_f16(h, l, crs, 0, 0, 0);
+        crs = __builtin_amdgcn_mfma_f32_16x16x32_f16(l, h, crs, 0, 0, 0);
+    }
+    f32x4 g;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) g[r] = acc[r] + crs[r] * (1.0f / 2048.0f);
     const int i = lane & 15, r = i - 4 * (lane >> 4);  // D[i][i] sits in element i - 4 (lane >> 4) of lane i + 16 (i >> 2)
     float v = g[0];
 #pragma unroll
@@ -305,6 +322,148 @@ __global__ __launch_bounds__(256) void knn_stream_kernel(const float* __restrict
         }
     }
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// 2''. the streaming k-NN for wide features (D = 2048: the ResNet maps; sm_knn_f32's method 2, the tuning build's switch).  A wave's 16
+// query rows are 512 VGPRs of fragments at that width, and a workgroup's 64 rows 512 KB: neither stays on chip, so the products are
+// accumulated over chunks of KC_K = 64 features.  A workgroup owns 64 query rows (16 per wave) and walks the image's points KC_COLS =
+// 64 at a time; per column tile it keeps the four 16 x 16 acc / crs pairs of its wave (32 VGPRs) and steps through the D / 64
+// chunks: the chunk of the query block and of the column tile (256 B per row: two MFMA steps) go global -> registers -> LDS, the next
+// chunk's loads in flight under this chunk's products.  LDS rows are one 256-B line each, the 16-B slots XORed with the row (mod 16):
+// the fragment reads (ds_read_b128: 16 rows x one slot pair per lane group) and the staging writes fall on distinct banks.  The
+// products are knn_stream_kernel's (acc = hi hi, crs = hi lo + lo hi, steps in ascending k: one fixed order for a given D), and only
+// after the last chunk key_j = sq_j - 2 (acc + crs 2^-11) is formed; selection (four lanes per row, 16 columns of the tile each,
+// j ascending within a lane), tie rule, fallback index and the final merge are knn_stream_kernel's.
+constexpr int KC_ROWS = 64;                  // query rows per workgroup
+constexpr int KC_COLS = 64;                  // points per column tile
+constexpr int KC_K = 64;                     // features per chunk
+constexpr int KC_CHB = KC_K * 4;             // bytes of a row's chunk in F16X2 form: one 256-B LDS line
+constexpr int KC_PIECES = KC_ROWS * KC_CHB / 16 / 256;  // 16-B pieces of one operand's chunk per thread
+static_assert(KC_CHB == 256 && KC_ROWS == KC_COLS && KC_PIECES * 16 * 256 == KC_ROWS * KC_CHB, "chunk staging");
+
+// byte offset of 16-B slot `slot` (0..15) of staged row `r`
+__device__ __forceinline__ int kc_lds(int r, int slot) { return r * KC_CHB + ((slot ^ (r & 15)) << 4); }
+
+template <int D, int CAP>
+__global__ __launch_bounds__(256) void knn_stream_chunked_kernel(const float* __restrict__ fs_all, const float* __restrict__ sq_all, int n, int m,
+                                                                 int* __restrict__ idx_all) {
+    static_assert(D % KC_K == 0, "whole chunks");
+    constexpr int ROWB = D * 4, NCH = D / KC_K;
+    __shared__ __attribute__((aligned(256))) char qtile[KC_ROWS * KC_CHB];
+    __shared__ __attribute__((aligned(256))) char ctile[KC_COLS * KC_CHB];
+    __shared__ float keys[4][16][KC_COLS + 1];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, img = blockIdx.y;
+    const int q0 = blockIdx.x * KC_ROWS;
+    const char* fs = reinterpret_cast<const char*>(fs_all + (int64_t)img * n * D);
+    const float* sq = sq_all + (int64_t)img * n;
+    // the selection: lane l keeps row q0 + 16 wave + (l >> 2), columns 16 (l & 3) .. + 16 of every tile
+    const int srow = lane >> 2, ssub = lane & 3, row = q0 + wave * 16 + srow;
+    float key[CAP], thr = INFINITY;  // thr: the lane's m-th key so far
+    int id[CAP];
+#pragma unroll
+    for (int p = 0; p < CAP; ++p) { key[p] = INFINITY; id[p] = 0x7fffffff; }
+    // staging: piece tid + 256 i = (row (tid >> 4) + 16 i, slot tid & 15) of both operands' chunk
+    const int prow = tid >> 4, pslot = tid & 15;
+    f32x4 vq[KC_PIECES], vc[KC_PIECES];
+// chunk g % NCH of the query block and of column tile g / NCH: global -> registers
+#define KC_FETCH(g)                                                                                                         \
+    {                                                                                                                       \
+        const int c0_ = ((g) / NCH) * KC_COLS;                                                                              \
+        const int64_t off_ = (int64_t)((g) % NCH) * KC_CHB + pslot * 16;                                                    \
+        _Pragma("unroll") for (int i = 0; i < KC_PIECES; ++i) {                                                             \
+            vq[i] = *reinterpret_cast<const f32x4*>(fs + (int64_t)min(q0 + prow + 16 * i, n - 1) * ROWB + off_);          \
+            vc[i] = *reinterpret_cast<const f32x4*>(fs + (int64_t)min(c0_ + prow + 16 * i, n - 1) * ROWB + off_);         \
+        }                                                                                                                   \
+    }
+    const int total = ((n + KC_COLS - 1) / KC_COLS) * NCH;
+    const int fr = lane & 15, fq = lane >> 4;  // fragment row and k-group of the lane (the 16x16x32 operand map)
+    KC_FETCH(0)
+#pragma unroll 1
+    for (int g0 = 0; g0 < total; g0 += NCH) {  // one column tile
+        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0, acc2 = acc0, acc3 = acc0, crs0 = acc0, crs1 = acc0, crs2 = acc0, crs3 = acc0;
+        static_assert(KC_COLS == 64, "four 16-column sub-tiles per wave");
+#pragma unroll 1
+        for (int g = g0; g < g0 + NCH; ++g) {
+            __syncthreads();  // the previous chunk's fragment reads are done
+#pragma unroll
+            for (int i = 0; i < KC_PIECES; ++i) {
+                *reinterpret_cast<f32x4*>(qtile + kc_lds(prow + 16 * i, pslot)) = vq[i];
+                *reinterpret_cast<f32x4*>(ctile + kc_lds(prow + 16 * i, pslot)) = vc[i];
+            }
+            __syncthreads();
+            KC_FETCH(min(g + 1, total - 1))  // (the last iteration fetches its own chunk again: nothing waits for it)
+#pragma unroll
+            for (int s = 0; s < KC_K / 32; ++s) {
+                const f16x8 qh = *reinterpret_cast<const f16x8*>(qtile + kc_lds(wave * 16 + fr, (4 * s + fq) * 2));
+                const f16x8 ql = *reinterpret_cast<const f16x8*>(qtile + kc_lds(wave * 16 + fr, (4 * s + fq) * 2 + 1));
+#define KC_SUBTILE(u, ACC, CRS)                                                                                             \
+    {                                                                                                                       \
+        const f16x8 chh = *reinterpret_cast<const f16x8*>(ctile + kc_lds((u) * 16 + fr, (4 * s + fq) * 2));                 \
+        const f16x8 cl = *reinterpret_cast<const f16x8*>(ctile + kc_lds((u) * 16 + fr, (4 * s + fq) * 2 + 1));              \
+        ACC = __builtin_amdgcn_mfma_f32_16x16x32_f16(qh, chh, ACC, 0, 0, 0);                                                \
+        CRS = __builtin_amdgcn_mfma_f32_16x16x32_f16(qh, cl, CRS, 0, 0, 0);                                                 \
+        CRS = __builtin_amdgcn_mfma_f32_16x16x32_f16(ql, chh, CRS, 0, 0, 0);                                                \
+    }
+                KC_SUBTILE(0, acc0, crs0)
+                KC_SUBTILE(1, acc1, crs1)
+                KC_SUBTILE(2, acc2, crs2)
+                KC_SUBTILE(3, acc3, crs3)
+#undef KC_SUBTILE
+            }
+        }
+        // the tile's products are complete: keys, then the selection
+        const int c0 = (g0 / NCH) * KC_COLS;
+#define KC_KEYS(u, ACC, CRS)                                                                                                \
+    {                                                                                                                       \
+        const float sj = sq[min(c0 + (u) * 16 + fr, n - 1)];                                                                \
+        _Pragma("unroll") for (int r = 0; r < 4; ++r)                                                                       \
+            keys[wave][4 * fq + r][(u) * 16 + fr] = sj - 2.0f * (ACC[r] + CRS[r] * (1.0f / 2048.0f));                       \
+    }
+        KC_KEYS(0, acc0, crs0)
+        KC_KEYS(1, acc1, crs1)
+        KC_KEYS(2, acc2, crs2)
+        KC_KEYS(3, acc3, crs3)
+#undef KC_KEYS
+        __syncthreads();  // the keys are in place (read by other lanes of the wave; rewritten only after the next tile's barriers)
+#pragma unroll 1
+        for (int cc = 0; cc < KC_COLS / 4; ++cc) {
+            const int jl = ssub * (KC_COLS / 4) + cc, j = c0 + jl;
+            if (j >= n || j == row) continue;
+            const float kj = keys[wave][srow][jl];
+            if (kj < thr) {  // j ascends within a lane: on equal keys the earlier index stays in front
+#pragma unroll
+                for (int p = CAP - 1; p > 0; --p) {
+                    const bool up = kj < key[p - 1];
+                    const bool here = !up && kj < key[p];
+                    key[p] = up ? key[p - 1] : (here ? kj : key[p]);
+                    id[p] = up ? id[p - 1] : (here ? j : id[p]);
+                }
+                if (kj < key[0]) { key[0] = kj; id[0] = j; }
+#pragma unroll
+                for (int p = 0; p < CAP; ++p) thr = p == m - 1 ? key[p] : thr;
+            }
+        }
+    }
+    int* out = idx_all + ((int64_t)img * n + row) * m;
+    for (int r = 0; r < m; ++r) {
+        float bk = key[0];
+        int bi = id[0];
+#pragma unroll
+        for (int o = 1; o < 4; o <<= 1) {
+            const float ok = __shfl_xor(bk, o, 64);
+            const int oi = __shfl_xor(bi, o, 64);
+            if (ok < bk || (ok == bk && oi < bi)) { bk = ok; bi = oi; }
+        }
+        if (ssub == 0 && row < n) out[r] = (unsigned)bi < (unsigned)n ? bi : (row + 1 + r) % n;  // (knn_select_kernel's fallback)
+        if (id[0] == bi) {
+#pragma unroll
+            for (int p = 0; p < CAP - 1; ++p) { key[p] = key[p + 1]; id[p] = id[p + 1]; }
+            key[CAP - 1] = INFINITY;
+            id[CAP - 1] = 0x7fffffff;
+        }
+    }
+}
+#undef KC_FETCH
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // 3. the graph as ONE adjacency list per point: its own m neighbours (nearest first), then the points that list it in ascending
@@ -1386,15 +1545,27 @@ __global__ __launch_bounds__(256) void gram_diag_kernel(const float* __restrict_
 
 static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// the paths of steps 1-2 (sp_knn_lists below)
+enum { KNN_GRAM = 0, KNN_STREAM = 1, KNN_SLABS = 2 };
+constexpr int SP_SLAB_ROWS = 2048;
+// What the clusterer takes above SP_MAXN points at D = 2048 (sm_knn_f32's method 0): measured on the MI355X (scripts/knn_dim_bench.py ->
+// profiles/knn_dim_bench.log).  D = 384 keeps its streaming kernel.
+constexpr bool SP_WIDE_SLABS = true;
+static inline int sp_auto_path(int n, int D) { return n <= SP_MAXN ? KNN_GRAM : (D == SP_DIM_RESNET && SP_WIDE_SLABS) ? KNN_SLABS : KNN_STREAM; }
+static inline size_t sp_gram_bytes(int B, int n, int path) {
+    return path == KNN_GRAM ? (size_t)B * n * n * 4 : path == KNN_SLABS ? (size_t)B * (n < SP_SLAB_ROWS ? n : SP_SLAB_ROWS) * n * 4 : 0;
+}
+
 // The features in F16X2 form, the Gram matrix (n <= 8192 only), norms, lists, graph, the two blocks of the eigen-solver, the embedding.
 struct SpLayout { size_t fs, gram, sq, idx, cnt, inptr, inlen, incol, rev, isd, blocks, emb, total; };
-static SpLayout sp_layout(int B, int n, int m, int kw) {
+static SpLayout sp_layout(int B, int n, int D, int m, int kw) {
     const bool gram = n <= SP_MAXN;
+    const int path = sp_auto_path(n, D);
     const size_t col = (size_t)B * sp_col_capacity(n, m) * 4;
     SpLayout l = {};
     size_t o = 0;
-    l.fs = o;     o += al256((size_t)B * n * SM_EMBED * 4);
-    if (gram) { l.gram = o; o += al256((size_t)B * n * n * 4); }
+    l.fs = o;     o += al256((size_t)B * n * D * 4);
+    if (path != KNN_STREAM) { l.gram = o; o += al256(sp_gram_bytes(B, n, path)); }  // (the whole matrix, or one slab above SP_MAXN)
     l.sq = o;     o += al256((size_t)B * n * 4);
     l.idx = o;    o += al256((size_t)B * n * m * 4);
     // the in-degrees / cursors; with the Gram matrix at the size of the n x n bitmap that held the graph before the O(n m) build (the
@@ -1403,8 +1574,8 @@ static SpLayout sp_layout(int B, int n, int m, int kw) {
     l.inptr = o;  o += al256((size_t)B * (n + 1) * 4);
     l.inlen = o;  o += al256((size_t)B * n * 4);
     l.incol = o;  o += al256(col);
-    // the scattered reverse edges: with the Gram matrix in the features (n * 1536 B per image >= the col capacity for m <= 32; dead
-    // once the k-NN lists exist)
+    // the scattered reverse edges: with the Gram matrix in the features (n * 4 D >= n * 1536 B per image >= the col capacity for
+    // m <= 32; dead once the k-NN lists exist)
     if (gram) l.rev = l.fs;
     else { l.rev = o; o += al256(col); }
     l.isd = o;    o += al256((size_t)B * n * 8);
@@ -1469,14 +1640,152 @@ static const SpEmbedKernel sp_embed_kernels[] = {SP_EMBED(8, 2), SP_EMBED(4, 3),
 
 }  // namespace sm
 
-extern "C" size_t sm_spectral_workspace_bytes(int32_t B, int32_t n, int32_t n_neighbors, int32_t kw) {
-    if (B < 1 || n < 2 * sm::SP_B || n > sm::SP_MAXN_L || n_neighbors < 2 || n_neighbors - 1 > sm::SP_MAXM || kw < 1 || kw > 6) return 0;
-    const int m = n_neighbors - 1 < n - 1 ? n_neighbors - 1 : n - 1;
-    return sm::sp_layout(B, n, m, kw).total;
+namespace sm {
+
+static inline bool sp_dim_ok(int D) { return D == SM_EMBED || D == SP_DIM_RESNET; }
+
+// Steps 1-2 for features (B, n, D): the F16X2 copy in `fs`, then the neighbour lists (B, n, m) in `idx`, by one of three paths:
+// KNN_GRAM the whole Gram matrix in `gram` (n <= SP_MAXN), KNN_STREAM the streaming kernels (no n x n array), KNN_SLABS the Gram
+// matrix SP_SLAB_ROWS rows at a time (`gram`: B slabs), each slab selected from before the next is formed - gemm_f16x2's tiles with a
+// workspace linear in n; the squared norms then come from knn_sqnorm_kernel (a slab does not hold the whole diagonal).  `sq` takes the norms.
+static void sp_launch_sqnorm(const float* fs, int64_t rows, int D, float* sq, hipStream_t st) {
+    const dim3 sgrid((unsigned)((rows + 63) / 64));
+    if (D == SM_EMBED) hipLaunchKernelGGL(sm::knn_sqnorm_kernel<SM_EMBED>, sgrid, dim3(256), 0, st, fs, rows, sq);
+    else hipLaunchKernelGGL(sm::knn_sqnorm_kernel<SP_DIM_RESNET>, sgrid, dim3(256), 0, st, fs, rows, sq);
 }
 
-extern "C" int sm_spectral_cluster_f32(const sm_spectral_args* a, void* stream) {
+// rows row0 .. row0 + rows of every image's Gram matrix into `gram` (B, rows, n)
+static int sp_gram_rows(const float* fs, int B, int n, int D, int row0, int rows, float* gram, void* stream) {
+    sm_gemm_args g = {};
+    g.A = fs + (int64_t)row0 * D;
+    g.W = fs;
+    g.C = gram;
+    g.strideA = g.strideW = (int64_t)n * D;
+    g.strideC = (int64_t)rows * n;
+    g.M = rows;
+    g.N = n;
+    g.K = D;
+    g.lda = g.ldw = D;
+    g.ldc = n;
+    g.batch = B;
+    g.epilogue = SM_EPI_BIAS;
+    return sm_gemm_f16x2(&g, 0, stream);
+}
+
+static void sp_launch_select(const float* gram, const float* sq, int B, int n, int m, int* idx, int row0, int rows, hipStream_t st) {
+    if (m <= 16)
+        hipLaunchKernelGGL(sm::knn_select_kernel<16>, dim3((rows + 3) / 4, B), dim3(256), 0, st, gram, sq, n, m, idx, row0, rows);
+    else
+        hipLaunchKernelGGL(sm::knn_select_kernel<32>, dim3((rows + 3) / 4, B), dim3(256), 0, st, gram, sq, n, m, idx, row0, rows);
+}
+
+static int sp_knn_lists(const float* features, int B, int n, int D, int m, int path, float* fs, float* gram, float* sq, int* idx,
+                        void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const double nd = (double)n, Bd = (double)B;
+    int rc;
+    if (path == KNN_STREAM) {
+        // (flops: the three f16 products per multiply-add of every pair, as the tap of gemm_f16x2 counts its own)
+        sm::TapGuard tap(stream, "spectral: split_f16x2 + knn_stream", 2.0 * Bd * nd * nd * D, Bd * nd * D * 8);
+        rc = sm_split_f16x2(features, D, fs, D, (int64_t)B * n, D, stream);
+        if (rc) return rc;
+        sp_launch_sqnorm(fs, (int64_t)B * n, D, sq, st);
+        if (D == SM_EMBED) {
+            const dim3 grid((n + sm::KS_ROWS - 1) / sm::KS_ROWS, B);
+            if (m <= 16) hipLaunchKernelGGL(sm::knn_stream_kernel<16>, grid, dim3(256), 0, st, fs, sq, n, m, idx);
+            else hipLaunchKernelGGL(sm::knn_stream_kernel<32>, grid, dim3(256), 0, st, fs, sq, n, m, idx);
+        } else {
+            const dim3 grid((n + sm::KC_ROWS - 1) / sm::KC_ROWS, B);
+            if (m <= 16) hipLaunchKernelGGL((sm::knn_stream_chunked_kernel<SP_DIM_RESNET, 16>), grid, dim3(256), 0, st, fs, sq, n, m, idx);
+            else hipLaunchKernelGGL((sm::knn_stream_chunked_kernel<SP_DIM_RESNET, 32>), grid, dim3(256), 0, st, fs, sq, n, m, idx);
+        }
+    } else if (path == KNN_SLABS) {
+        sm::TapGuard tap(stream, "spectral: split_f16x2 + Gram slabs + knn_select", 2.0 * Bd * nd * nd * D, Bd * (nd * D * 8 + 2.0 * nd * nd * 4));
+        rc = sm_split_f16x2(features, D, fs, D, (int64_t)B * n, D, stream);
+        if (rc) return rc;
+        sp_launch_sqnorm(fs, (int64_t)B * n, D, sq, st);
+        for (int row0 = 0; row0 < n; row0 += SP_SLAB_ROWS) {
+            const int rows = n - row0 < SP_SLAB_ROWS ? n - row0 : SP_SLAB_ROWS;
+            rc = sp_gram_rows(fs, B, n, D, row0, rows, gram, stream);
+            if (rc) return rc;
+            sp_launch_select(gram, sq, B, n, m, idx, row0, rows, st);
+        }
+    } else {
+        {
+            sm::TapGuard tap(stream, "spectral: split_f16x2 + Gram gemm_f16x2", 2.0 * Bd * nd * nd * D, Bd * (nd * D * 8 + nd * nd * 4));
+            rc = sm_split_f16x2(features, D, fs, D, (int64_t)B * n, D, stream);
+            if (rc) return rc;
+            rc = sp_gram_rows(fs, B, n, D, 0, n, gram, stream);
+            if (rc) return rc;
+        }
+        sm::TapGuard tap(stream, "spectral: knn_select", 0.0, Bd * (nd * nd * 4 + nd * m * 4));
+        hipLaunchKernelGGL(sm::gram_diag_kernel, dim3((unsigned)(((int64_t)B * n + 255) / 256)), dim3(256), 0, st, gram, n, (int64_t)B * n, sq);
+        sp_launch_select(gram, sq, B, n, m, idx, 0, n, st);
+    }
+    return SM_OK;
+}
+
+// sm_knn_f32's workspace: the F16X2 copy, the Gram matrix or one slab of it, the squared norms
+struct KnnLayout { size_t fs, gram, sq, total; };
+static KnnLayout knn_layout(int B, int n, int D, int path) {
+    KnnLayout l = {};
+    size_t o = 0;
+    l.fs = o;   o += al256((size_t)B * n * D * 4);
+    l.gram = o; o += al256(sp_gram_bytes(B, n, path));
+    l.sq = o;   o += al256((size_t)B * n * 4);
+    l.total = o;
+    return l;
+}
+// method 0 / 1 / 2 -> the path, -1 = no such method
+static int knn_path(int n, int D, int method) {
+    if (method == 0) return sp_auto_path(n, D);
+    if (method == 1) return n <= SP_MAXN ? KNN_GRAM : KNN_SLABS;
+    return method == 2 ? KNN_STREAM : -1;
+}
+
+}  // namespace sm
+
+extern "C" size_t sm_knn_workspace_bytes(int32_t B, int32_t n, int32_t D, int32_t n_neighbors, int32_t method) {
+    if (B < 1 || n < 2 * sm::SP_B || n > sm::SP_MAXN_L || n % 4 != 0 || !sm::sp_dim_ok(D) || n_neighbors < 2 ||
+        n_neighbors - 1 > sm::SP_MAXM || sm::knn_path(n, D, method) < 0)
+        return 0;
+    return sm::knn_layout(B, n, D, sm::knn_path(n, D, method)).total;
+}
+
+extern "C" int sm_knn_f32(const float* features, int32_t B, int32_t n, int32_t D, int32_t n_neighbors, int32_t method, int32_t* idx,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+    SM_REQUIRE(features && idx && workspace, "sm_knn_f32: null pointer");
+    SM_REQUIRE(sm::sp_dim_ok(D), "sm_knn_f32: %d features per point (%d or %d)", D, SM_EMBED, sm::SP_DIM_RESNET);
+    SM_REQUIRE(B >= 1 && n >= 2 * sm::SP_B && n <= sm::SP_MAXN_L && n % 4 == 0, "sm_knn_f32: %d points (16 <= n <= %d, n %% 4 == 0)", n,
+               sm::SP_MAXN_L);
+    SM_REQUIRE(n_neighbors >= 2 && n_neighbors - 1 <= sm::SP_MAXM, "sm_knn_f32: n_neighbors %d (2..%d)", n_neighbors, sm::SP_MAXM + 1);
+    const int path = sm::knn_path(n, D, method);
+    SM_REQUIRE(path >= 0, "sm_knn_f32: method %d (0 = as the clusterer chooses, 1 = Gram matrix, 2 = streaming)", method);
+    const sm::KnnLayout l = sm::knn_layout(B, n, D, path);
+    SM_REQUIRE(workspace_bytes >= l.total && ((uintptr_t)workspace % 256 == 0), "sm_knn_f32: workspace of %zu bytes, %zu needed (256-B aligned)",
+               workspace_bytes, l.total);
+    char* ws = (char*)workspace;
+    const int m = n_neighbors - 1 < n - 1 ? n_neighbors - 1 : n - 1;
+    const int rc = sm::sp_knn_lists(features, B, n, D, m, path, (float*)(ws + l.fs), (float*)(ws + l.gram), (float*)(ws + l.sq), idx, stream);
+    return rc ? rc : sm::check_launch("sm_knn_f32");
+}
+
+extern "C" size_t sm_spectral_workspace_bytes_dim(int32_t B, int32_t n, int32_t D, int32_t n_neighbors, int32_t kw) {
+    if (B < 1 || n < 2 * sm::SP_B || n > sm::SP_MAXN_L || !sm::sp_dim_ok(D) || n_neighbors < 2 || n_neighbors - 1 > sm::SP_MAXM || kw < 1 || kw > 6)
+        return 0;
+    const int m = n_neighbors - 1 < n - 1 ? n_neighbors - 1 : n - 1;
+    return sm::sp_layout(B, n, D, m, kw).total;
+}
+
+extern "C" size_t sm_spectral_workspace_bytes(int32_t B, int32_t n, int32_t n_neighbors, int32_t kw) {
+    return sm_spectral_workspace_bytes_dim(B, n, SM_EMBED, n_neighbors, kw);
+}
+
+extern "C" int sm_spectral_cluster_f32(const sm_spectral_args* a, void* stream) { return sm_spectral_cluster_dim_f32(a, SM_EMBED, stream); }
+
+extern "C" int sm_spectral_cluster_dim_f32(const sm_spectral_args* a, int32_t D, void* stream) {
     SM_REQUIRE(a && a->features && a->labels && a->cluster_sizes && a->workspace, "sm_spectral_cluster_f32: null pointer");
+    SM_REQUIRE(sm::sp_dim_ok(D), "sm_spectral_cluster_f32: %d features per point (%d or %d)", D, SM_EMBED, sm::SP_DIM_RESNET);
     SM_REQUIRE(a->B >= 1 && a->n >= 2 * sm::SP_B && a->n <= sm::SP_MAXN_L && a->n % 4 == 0,
                "sm_spectral_cluster_f32: %d points (16 <= n <= %d, n %% 4 == 0)", a->n, sm::SP_MAXN_L);
     SM_REQUIRE(a->n_neighbors >= 2 && a->n_neighbors - 1 <= sm::SP_MAXM, "sm_spectral_cluster_f32: n_neighbors %d (2..%d)", a->n_neighbors,
@@ -1490,59 +1799,20 @@ extern "C" int sm_spectral_cluster_f32(const sm_spectral_args* a, void* stream) 
         if (sizes.k[i] > kw) kw = sizes.k[i];
     }
     const int B = a->B, n = a->n, m = a->n_neighbors - 1 < n - 1 ? a->n_neighbors - 1 : n - 1;
-    const sm::SpLayout l = sm::sp_layout(B, n, m, kw);
+    const sm::SpLayout l = sm::sp_layout(B, n, D, m, kw);
     SM_REQUIRE(a->workspace_bytes >= l.total && ((uintptr_t)a->workspace % 256 == 0),
                "sm_spectral_cluster_f32: workspace of %zu bytes, %zu needed (256-B aligned)", a->workspace_bytes, l.total);
-    bool knn_stream = n > sm::SP_MAXN;  // k-NN without the Gram matrix
-#ifdef SM_TUNING  // the tuning build can force it at any n (tests: against the Gram path)
-    if (const char* e = getenv("SM_SPECTRAL_KNN")) knn_stream = knn_stream || strcmp(e, "stream") == 0;
+    int path = sm::sp_auto_path(n, D);
+#ifdef SM_TUNING  // the tuning build can force the streaming k-NN at any n (tests: against the Gram path)
+    if (const char* e = getenv("SM_SPECTRAL_KNN")) path = strcmp(e, "stream") == 0 ? (int)sm::KNN_STREAM : path;
 #endif
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)a->workspace;
-    float* fs = (float*)(ws + l.fs);
     int* idx = a->knn ? a->knn : (int*)(ws + l.idx);
     double* emb = a->embedding ? a->embedding : (double*)(ws + l.emb);
     const double nd = (double)n, Bd = (double)B;
-    int rc;
-    float* sq = (float*)(ws + l.sq);
-    if (knn_stream) {
-        // (flops: the three f16 products per multiply-add of every pair, as the tap of gemm_f16x2 counts its own)
-        sm::TapGuard tap(stream, "spectral: split_f16x2 + knn_stream", 2.0 * Bd * nd * nd * SM_EMBED, Bd * nd * SM_EMBED * 8);
-        rc = sm_split_f16x2(a->features, SM_EMBED, fs, SM_EMBED, (int64_t)B * n, SM_EMBED, stream);
-        if (rc) return rc;
-        const int64_t rows = (int64_t)B * n;
-        hipLaunchKernelGGL(sm::knn_sqnorm_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(256), 0, st, fs, rows, sq);
-        const dim3 grid((n + sm::KS_ROWS - 1) / sm::KS_ROWS, B);
-        if (m <= 16) hipLaunchKernelGGL(sm::knn_stream_kernel<16>, grid, dim3(256), 0, st, fs, sq, n, m, idx);
-        else hipLaunchKernelGGL(sm::knn_stream_kernel<32>, grid, dim3(256), 0, st, fs, sq, n, m, idx);
-    } else {
-        float* gram = (float*)(ws + l.gram);
-        {
-            sm::TapGuard tap(stream, "spectral: split_f16x2 + Gram gemm_f16x2", 2.0 * Bd * nd * nd * SM_EMBED, Bd * (nd * SM_EMBED * 8 + nd * nd * 4));
-            rc = sm_split_f16x2(a->features, SM_EMBED, fs, SM_EMBED, (int64_t)B * n, SM_EMBED, stream);
-            if (rc) return rc;
-            sm_gemm_args g = {};
-            g.A = fs;
-            g.W = fs;
-            g.C = gram;
-            g.strideA = g.strideW = (int64_t)n * SM_EMBED;
-            g.strideC = (int64_t)n * n;
-            g.M = g.N = n;
-            g.K = SM_EMBED;
-            g.lda = g.ldw = SM_EMBED;
-            g.ldc = n;
-            g.batch = B;
-            g.epilogue = SM_EPI_BIAS;
-            rc = sm_gemm_f16x2(&g, 0, stream);
-            if (rc) return rc;
-        }
-        sm::TapGuard tap(stream, "spectral: knn_select", 0.0, Bd * (nd * nd * 4 + nd * m * 4));
-        hipLaunchKernelGGL(sm::gram_diag_kernel, dim3((unsigned)(((int64_t)B * n + 255) / 256)), dim3(256), 0, st, gram, n, (int64_t)B * n, sq);
-        if (m <= 16)
-            hipLaunchKernelGGL(sm::knn_select_kernel<16>, dim3((n + 3) / 4, B), dim3(256), 0, st, gram, sq, n, m, idx);
-        else
-            hipLaunchKernelGGL(sm::knn_select_kernel<32>, dim3((n + 3) / 4, B), dim3(256), 0, st, gram, sq, n, m, idx);
-    }
+    const int rc = sm::sp_knn_lists(a->features, B, n, D, m, path, (float*)(ws + l.fs), (float*)(ws + l.gram), (float*)(ws + l.sq), idx, stream);
+    if (rc) return rc;
     {
         sm::TapGuard tap(stream, "spectral: knn_graph", 0.0, Bd * (6.0 * nd * m * 4 + nd * 24));
         int* cnt = (int*)(ws + l.cnt);

@@ -11,6 +11,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SM_HIP_LIB") or os.path.normpath(os.path.join(_HERE, "..", "lib", "libselfmask_hip.so"))
 
 EMBED, HEADS, HEAD_DIM, MLP, ENC_DEPTH, MAX_DEC_LAYERS = 384, 6, 64, 1536, 12, 8
+RESNET_EMBED = 2048                       # features per point of a ResNet type (the clusterers' other width)
+KNN_METHODS = {"auto": 0, "gram": 1, "stream": 2}  # sm_knn_f32's `method`
 EPI_BIAS, EPI_GELU, EPI_RELU, EPI_RESIDUAL, EPI_SIGMOID2, EPI_PATCH, EPI_RESIDUAL_LN = range(7)
 
 fp = C.c_void_p  # device pointers travel as integers (tensor.data_ptr())
@@ -259,6 +261,10 @@ SYMBOLS = {
     "sm_labels_to_masks_u8": (C.c_int, [fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp, fp]),
     "sm_spectral_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "sm_spectral_cluster_f32": (C.c_int, [C.POINTER(SpectralArgs), fp]),
+    "sm_spectral_workspace_bytes_dim": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "sm_spectral_cluster_dim_f32": (C.c_int, [C.POINTER(SpectralArgs), C.c_int32, fp]),
+    "sm_knn_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "sm_knn_f32": (C.c_int, [fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp, fp, C.c_size_t, fp]),
     "sm_evaluate_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "sm_evaluate_masks_f32": (C.c_int, [C.POINTER(EvalArgs), fp]),
     "sm_bilateral_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double]),

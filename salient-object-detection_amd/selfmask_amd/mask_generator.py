@@ -1,8 +1,8 @@
 """Mirror of the reference's ``datasets.mask_generator.MaskGenerator`` (bytecode only: SURVEY.md Appendix B, mask_generator.pyc@L21-252;
-its constants are pinned by tests/golden/evaluator_constants.json), DINO branch, on the MI355X:
+its constants are pinned by tests/golden/evaluator_constants.json) on the MI355X:
 
-    MaskGenerator(cluster_sizes=(2, 3, 4), cluster_type="spectral", feature_types=["dino"], network=model)(p_images)
-        -> {filename: run-length-encoded salient mask}
+    MaskGenerator(cluster_sizes=(2, 3, 4), cluster_type="spectral", feature_types=["mocov2", "swav", "dino"], network=model,
+                  backbones={"mocov2": r1, "swav": r2})(p_images)      -> {filename: run-length-encoded salient mask}
 
 ``extract_candidate_masks`` (@L136-200): every image at its native resolution, normalised as ``CustomDataset`` does
 (/root/reference/datasets/custom_dataset.py:26-32: RGB, ``to_tensor``, ImageNet mean / std), zero-padded to a multiple of the stride
@@ -12,10 +12,13 @@ one patch grid share a batch (the reference's DataLoader runs batch 1; images ar
 in a batch as alone): the crop to its own H x W happens inside the vote and the run-length kernels.  ``vote_mask`` (@L202-230) picks the candidate that
 agrees most with the others.  ``__call__`` (@L232-252) returns the winner per file name, run-length encoded.
 
-Differences kept on purpose: (1) only the ``"dino"`` feature type - the dilated ResNet-50 of the MoCo-v2 / SwAV branches is built
-(``selfmask_amd.resnet``: ``ResNet50``, ``resnet_features`` = what @L150-159 hands the clusterer), but the clusterers take 384-d points
-only and the checkpoints are absent from the reference repository, so asking for those types still raises; (2) the encoder is the ``network`` handed in
-(a ``selfmask_amd.MaskFormer`` whose encoder holds the DINO weights): the reference fetches them from the network at construction time
+The ResNet feature types ("mocov2", "swav": ``backbones={type: selfmask_amd.ResNet50}``) give nine more candidates each
+(``voting.extract_candidate_masks_resnet``: the image padded to a multiple of 8, the dilated ResNet-50's last map, the same x2
+up-sample, the spectral clusterer at 2048 dimensions, nearest up-sample by 4), and all 27 go into one vote.
+
+Differences kept on purpose: (1) k-means on the 2048-d points of a ResNet type is not built (``cluster_type="k-means"`` with such a
+type raises); (2) the encoder is the ``network`` handed in (a ``selfmask_amd.MaskFormer`` whose encoder holds the DINO weights) and the
+ResNets are the ``backbones`` handed in: the reference fetches all of them from the network at construction time
 (utils/misc.py:196,243), which must never happen here; (3) the reference encodes with ``pycocotools.mask.encode`` (absent from this
 image): ``rle_encode`` writes COCO's UNCOMPRESSED run-length form ({"size": [h, w], "counts": [n0, n1, ...]}, column-major, first run =
 zeros), which ``pycocotools.mask.frPyObjects`` turns into the compressed string; (4) both clusterers are parity UNPINNED - the
@@ -60,24 +63,40 @@ class MaskGenerator:
     def __init__(self, cluster_sizes: Sequence[int] = VT.DEFAULT_CLUSTER_SIZES, cluster_type: str = VT.DEFAULT_CLUSTER_TYPE,
                  feature_types: Sequence[str] = ("dino",), use_gpu: bool = True, device: torch.device = torch.device("cuda:0"),
                  network=None, batch_size: int = 128, n_neighbors: int = 10, streams: int = 3, workers: Optional[int] = None,
-                 max_stream_bytes: int = 16 << 30):
+                 max_stream_bytes: int = 16 << 30, backbones: Optional[Dict[str, object]] = None):
         """``batch_size``: the most images of ONE size clustered together - the eigen-solver runs one workgroup per image, so a launch
         takes about as long for 128 images as for 8 (profiles/r04_pseudo_masks_by_batch.log); ``streams``: batches in flight (one's
         eigen-solve, half of the CUs at 128 images, runs beside the next one's encoder); ``workers``: decode processes
-        (default: this rank's share of the host cores); ``max_stream_bytes``: for patch grids of more than 8192 clustered points only
-        (n = 4 gh gw: above about 1024 x 512 pixels at P = 16), the batch is cut so that the clusterer's and the encoder's scratch
-        of one stream stay within this many bytes (default 16 GiB; at least one image per batch) - smaller grids keep ``batch_size``."""
+        (default: this rank's share of the host cores); ``max_stream_bytes``: for patch grids of more than 8192 clustered points
+        (n = 4 gh gw: above about 1024 x 512 pixels at P = 16) - and for EVERY size once a ResNet type is asked for - the batch is cut
+        so that the clusterer's and the networks' scratch of one stream stay within this many bytes (default 16 GiB; at least one
+        image per batch); ``feature_types=["dino"]`` on smaller grids keeps ``batch_size``.  ``backbones``: {"mocov2" | "swav": a
+        ``selfmask_amd.ResNet50`` whose weights the caller has loaded (``load_pretrained``)} - one per ResNet feature type asked for;
+        nothing is fetched or read from a fixed path."""
         assert cluster_type in VT.CLUSTER_TYPES + ("kmeans",), cluster_type  # mask_generator.pyc@L30: ('k-means', 'spectral')
-        unsupported = [f for f in feature_types if f != "dino"]
+        backbones = dict(backbones or {})
+        unsupported = [f for f in feature_types if f != "dino" and (f not in VT.RESNET_FEATURE_TYPES or backbones.get(f) is None)]
         if unsupported:
-            raise NotImplementedError(f"feature types {unsupported}: the MoCo-v2 / SwAV ResNet-50 backbones and their weights are absent "
-                                      f"from the reference repository; only 'dino' is built")
-        if network is None:
+            raise NotImplementedError(f"feature types {unsupported}: the MoCo-v2 / SwAV ResNet-50 checkpoints are absent from the reference "
+                                      f"repository and nothing is downloaded; hand each one in as `backbones={{type: ResNet50}}` with its "
+                                      f"weights loaded ('dino' needs `network`)")
+        self.resnet_types = [f for f in feature_types if f != "dino"]
+        if "dino" in feature_types and network is None:
             raise ValueError("MaskGenerator needs `network` (a selfmask_amd.MaskFormer whose encoder holds the DINO ViT-S weights): the "
                              "reference downloads them at construction time, which this build never does")
+        if not feature_types:
+            raise ValueError("MaskGenerator needs at least one feature type")
         if not use_gpu:
             raise RuntimeError("the MI355X build has no CPU path")
+        if self.resnet_types and cluster_type != "spectral":
+            raise NotImplementedError(f"cluster_type={cluster_type!r} with feature types {self.resnet_types}: k-means on 2048-d points is "
+                                      f"not built (kmeans_kernel keeps its centres for 384-d points in the LDS); use 'spectral'")
         self.cluster_sizes, self.cluster_type, self.feature_types = tuple(int(k) for k in cluster_sizes), cluster_type, list(feature_types)
+        n_cand = sum(self.cluster_sizes) * len(self.feature_types)
+        if n_cand > VT.MAX_VOTE_CANDIDATES:
+            raise ValueError(f"MaskGenerator: {sum(self.cluster_sizes)} candidates x {len(self.feature_types)} feature types = {n_cand} "
+                             f"planes; the vote takes at most {VT.MAX_VOTE_CANDIDATES}")
+        self.backbones = {f: backbones[f] for f in self.resnet_types}
         self.device, self.network, self.batch_size, self.n_neighbors = torch.device(device), network, int(batch_size), int(n_neighbors)
         self.streams, self.workers, self.max_stream_bytes = max(1, int(streams)), workers, int(max_stream_bytes)
         self._ring = None  # the streams of __call__, made once: the per-stream scratch of the clusterer (voting._arena) stays bounded
@@ -91,23 +110,48 @@ class MaskGenerator:
         x = (rgb - np.asarray(MEAN, np.float32)) / np.asarray(STD, np.float32)               # normalize
         return torch.from_numpy(np.ascontiguousarray(x.transpose(2, 0, 1)))
 
+    def _patch(self) -> int:
+        """the DINO encoder's patch size (total stride); without the "dino" type the ResNets' stride stands in"""
+        return self.network.encoder.patch_size if "dino" in self.feature_types else VT.RESNET_TOTAL_STRIDE
+
+    def _bucket_stride(self) -> int:
+        """images share a batch when they pad to one grid of this stride: the ResNets' 8 when one is asked for (the reference pads every
+        image alone to a multiple of 8 for them, and the size of that grid enters the align_corners up-sample; P is a multiple of 8, so
+        such a bucket shares the DINO grid too), else the patch size"""
+        return VT.RESNET_TOTAL_STRIDE if self.resnet_types else self._patch()
+
     def _points(self, hw) -> int:
         """points the clusterer sees for an image of size hw: the patch tokens of its padded grid after the x2 up-sample"""
-        P = self.network.encoder.patch_size
+        P = self._patch()
         return 4 * (-(-int(hw[0]) // P)) * (-(-int(hw[1]) // P))
+
+    def _points_resnet(self, hw) -> int:
+        """the same for a ResNet type: the stride-8 grid of the image padded to a multiple of 8, after the x2 up-sample"""
+        s = VT.RESNET_TOTAL_STRIDE
+        return 4 * (-(-int(hw[0]) // s)) * (-(-int(hw[1]) // s))
 
     def _batch_cap(self, hw) -> int:
         """the most images of the padded size of hw in one batch: ``batch_size``, and above 8192 clustered points as many as the
-        clusterer's plus the encoder's workspace allow within ``max_stream_bytes`` (both grow linearly in the batch)"""
+        clusterer's plus the encoder's workspace allow within ``max_stream_bytes`` (both grow linearly in the batch).  With a ResNet
+        type every size is counted: per image the backbone's workspace, its 2048-d rows and the clusterer's workspace at that width
+        (the Gram matrix, n^2 * 4 B, is part of it to 8192 points: 225 MB at 300 x 400), beside the DINO type's share."""
         n = self._points(hw)
-        if self.cluster_type != "spectral" or n <= VT.SPECTRAL_GRAM_POINTS:
+        if not self.resnet_types and (self.cluster_type != "spectral" or n <= VT.SPECTRAL_GRAM_POINTS):
             return self.batch_size
         from . import _native as N
         lib = N.load()
-        P = self.network.encoder.patch_size
+        P = self._patch()
         Hp, Wp = -(-int(hw[0]) // P) * P, -(-int(hw[1]) // P) * P
-        per = (lib.sm_spectral_workspace_bytes(1, n, self.n_neighbors, max(self.cluster_sizes))
-               + lib.sm_forward_workspace_bytes(self.network._weights(), 1, Hp, Wp))
+        per = 0
+        if "dino" in self.feature_types:
+            per += (lib.sm_spectral_workspace_bytes(1, n, self.n_neighbors, max(self.cluster_sizes))
+                    + lib.sm_forward_workspace_bytes(self.network._weights(), 1, Hp, Wp))
+        if self.resnet_types:
+            s = VT.RESNET_TOTAL_STRIDE
+            H8, W8, nr = -(-int(hw[0]) // s) * s, -(-int(hw[1]) // s) * s, self._points_resnet(hw)
+            # (the types run one after the other on the stream: their scratch is shared, counted once)
+            per += (lib.sm_resnet50_workspace_bytes(1, H8, W8, 1) + nr * N.RESNET_EMBED * 4
+                    + lib.sm_spectral_workspace_bytes_dim(1, nr, N.RESNET_EMBED, self.n_neighbors, max(self.cluster_sizes)))
         return max(1, min(self.batch_size, self.max_stream_bytes // max(per, 1)))
 
     def _plan(self, p_images: Sequence[str]):
@@ -117,17 +161,24 @@ class MaskGenerator:
         from .pipeline import native_buckets
         p_images = list(p_images)
         sizes = [probe_size(p) for p in p_images]  # headers only
-        if self.cluster_type == "spectral":
-            for p, hw in zip(p_images, sizes):
-                n = self._points(hw)
-                if not VT.SPECTRAL_MIN_POINTS <= n <= VT.SPECTRAL_MAX_POINTS:
-                    raise ValueError(f"MaskGenerator: {p} ({hw[0]} x {hw[1]}) gives {n} points to the spectral clusterer "
-                                     f"({VT.SPECTRAL_MIN_POINTS} <= n <= {VT.SPECTRAL_MAX_POINTS}); nothing was run")
+        self._check_points(p_images, sizes)
         batches = []
-        for b in native_buckets(sizes, self.network.encoder.patch_size, self.batch_size):
+        for b in native_buckets(sizes, self._bucket_stride(), self.batch_size):
             cap = self._batch_cap(sizes[b[0]])
             batches += [b[s:s + cap] for s in range(0, len(b), cap)]
         return p_images, sizes, sorted(batches, key=len, reverse=True)
+
+    def _check_points(self, p_images, sizes) -> None:
+        """every feature type's point count of every file against the spectral clusterer's limits"""
+        if self.cluster_type != "spectral":
+            return
+        for p, hw in zip(p_images, sizes):
+            counts = ([("dino", self._points(hw))] if "dino" in self.feature_types else []) + \
+                     [(f, self._points_resnet(hw)) for f in self.resnet_types]
+            for f, n in counts:
+                if not VT.SPECTRAL_MIN_POINTS <= n <= VT.SPECTRAL_MAX_POINTS:
+                    raise ValueError(f"MaskGenerator: {p} ({hw[0]} x {hw[1]}) gives {n} points to the spectral clusterer for "
+                                     f"feature type {f!r} ({VT.SPECTRAL_MIN_POINTS} <= n <= {VT.SPECTRAL_MAX_POINTS}); nothing was run")
 
     def _batches(self, p_images: Sequence[str], pack: bool = False, plan=None):
         """-> (file names, decoded uint8 RGB arrays) per batch of at most ``batch_size`` images that pad to ONE patch grid
@@ -141,24 +192,40 @@ class MaskGenerator:
             yield [p_images[i].split("/")[-1] for i in idx], rgbs
 
     def _candidates(self, rgbs):
-        """decoded images of one patch grid (arrays, or the loader's (staging buffers, shapes)) -> ((B, sum(cluster_sizes), Hp, Wp) uint8
-        candidates, [(H_b, W_b)]), queued on the current stream: every image zero-padded to the grid's Hp x Wp after normalisation - what
-        ``pad_input_image`` (@L124-134) builds for it alone - and its candidates are the top-left H_b x W_b of its planes"""
+        """decoded images of one grid (arrays, or the loader's (staging buffers, shapes)) -> ((B, M, Hp, Wp) uint8 candidates, [(H_b, W_b)]),
+        queued on the current stream, M = sum(cluster_sizes) per feature type in ``feature_types`` order (the reference appends them per
+        image in that order): every image zero-padded to the grid's Hp x Wp after normalisation - what ``pad_input_image`` (@L124-134) builds
+        for it alone - and its candidates are the top-left H_b x W_b of its planes.  A ResNet type sees the top-left ceil8 region of the
+        same batch: the image padded to a multiple of 8, as the reference pads it for that type."""
         from .pipeline import preprocess_on_device
-        P = self.network.encoder.patch_size
+        P = self._patch()
         packed = None
         if isinstance(rgbs, tuple):
             packed, rgbs = rgbs
         sizes = [(int(r[0]), int(r[1])) if packed is not None else (int(r.shape[0]), int(r.shape[1])) for r in rgbs]
         Hp, Wp = -(-max(h for h, _ in sizes) // P) * P, -(-max(w for _, w in sizes) // P) * P
         x = preprocess_on_device(rgbs, None, self.device, pinned=True, packed=packed, pad_to=(Hp, Wp))  # to_tensor + normalize + pad (device)
-        cands = VT.extract_candidate_masks(self.network, x, self.cluster_sizes, cluster_type=self.cluster_type, n_neighbors=self.n_neighbors)
-        return (cands[None] if cands.dim() == 3 else cands), sizes
+        if not self.resnet_types:
+            cands = VT.extract_candidate_masks(self.network, x, self.cluster_sizes, cluster_type=self.cluster_type, n_neighbors=self.n_neighbors)
+            return (cands[None] if cands.dim() == 3 else cands), sizes
+        s = VT.RESNET_TOTAL_STRIDE
+        H8, W8 = -(-max(h for h, _ in sizes) // s) * s, -(-max(w for _, w in sizes) // s) * s  # (one bucket: every image's own ceil8)
+        k = sum(self.cluster_sizes)
+        out = torch.zeros((len(sizes), k * len(self.feature_types), Hp, Wp), dtype=torch.uint8, device=x.device)
+        xr = x[:, :, :H8, :W8].contiguous() if (H8, W8) != (Hp, Wp) else x
+        for t, f in enumerate(self.feature_types):
+            if f == "dino":
+                c = VT.extract_candidate_masks(self.network, x, self.cluster_sizes, cluster_type=self.cluster_type, n_neighbors=self.n_neighbors)
+                out[:, t * k:(t + 1) * k] = c[None] if c.dim() == 3 else c
+            else:
+                c = VT.extract_candidate_masks_resnet(self.backbones[f], xr, self.cluster_sizes, self.n_neighbors, self.cluster_type)
+                out[:, t * k:(t + 1) * k, :H8, :W8] = c[None] if c.dim() == 3 else c
+        return out, sizes
 
     @torch.no_grad()
     def extract_candidate_masks(self, p_images: Sequence[str]) -> Dict[str, torch.Tensor]:
-        """file name -> (sum(cluster_sizes), H, W) uint8 on the device (the reference concatenates the candidates of its three
-        feature types per file name; here there is one)."""
+        """file name -> (sum(cluster_sizes) * len(feature_types), H, W) uint8 on the device: the candidates of the feature types
+        concatenated in ``feature_types`` order, as the reference appends them per file name."""
         out: Dict[str, torch.Tensor] = {}
         for names, rgbs in self._batches(p_images):
             cands, sizes = self._candidates(rgbs)

@@ -9,6 +9,7 @@ import torch
 
 from . import _native as N
 from .runs import ObjectOptions, PendingRuns, batch_segments_to_rles, segments_to_rles  # noqa: F401  (part of this module's surface)
+from .voting import knn  # noqa: F401  (sm_knn_f32: the neighbour lists of 384-d / 2048-d points)
 
 
 def _stream() -> int:

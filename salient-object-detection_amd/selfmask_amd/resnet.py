@@ -208,24 +208,30 @@ class ResNet50(nn.Module):
         return [m.permute(0, 3, 1, 2) for m in maps]
 
 
-def upsample_nhwc_aligned(f: torch.Tensor, scale: int = 2) -> torch.Tensor:
+def upsample_nhwc_aligned(f: torch.Tensor, scale: int = 2, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """F.interpolate(scale_factor=scale, mode="bilinear", align_corners=True) of a channels-last map: (B, h, w, C) -> (B, scale h,
-    scale w, C) on the device (sm_upsample_nhwc_aligned_f32)."""
+    scale w, C) on the device (sm_upsample_nhwc_aligned_f32).  ``out``: a contiguous float32 tensor of that many elements to write into
+    (a caller's scratch)."""
     if not f.is_cuda or f.dtype != torch.float32:
         raise RuntimeError("upsample_nhwc_aligned needs a float32 tensor on a HIP device (no CPU fallback)")
     f = f.contiguous()
     B, h, w, C = f.shape
-    up = torch.empty((B, scale * h, scale * w, C), device=f.device, dtype=torch.float32)
+    shape = (B, scale * h, scale * w, C)
+    if out is None:
+        up = torch.empty(shape, device=f.device, dtype=torch.float32)
+    else:
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B * scale * h * scale * w * C
+        up = out.view(shape)
     N.check(N.load().sm_upsample_nhwc_aligned_f32(f.data_ptr(), up.data_ptr(), B, h, w, C, scale, torch.cuda.current_stream().cuda_stream),
             "sm_upsample_nhwc_aligned_f32")
     return up
 
 
 @torch.no_grad()
-def resnet_features(model: ResNet50, x: torch.Tensor) -> Tuple[torch.Tensor, Tuple[int, int]]:
+def resnet_features(model: ResNet50, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Tuple[int, int]]:
     """What mask_generator.pyc@L150-159 hands the clusterer for a ResNet feature type: x zero-padded right / bottom to a multiple of
     the total stride 8 (pad_input_image @L124-134), ``model(x)[-1]``, bilinear x 2 (align_corners=True), one row per position:
-    ((B, 2h * 2w, n_embs), (h, w)) with (h, w) the last map's grid."""
+    ((B, 2h * 2w, n_embs), (h, w)) with (h, w) the last map's grid.  ``out``: scratch for the rows (``upsample_nhwc_aligned``)."""
     if not x.is_cuda:
         raise RuntimeError("resnet_features needs its input on a HIP device; there is no CPU fallback")
     H, W = x.shape[-2:]
@@ -233,4 +239,4 @@ def resnet_features(model: ResNet50, x: torch.Tensor) -> Tuple[torch.Tensor, Tup
     x = nn.functional.pad(x, (0, (s - W % s) % s, 0, (s - H % s) % s), value=0)
     f = model(x)[-1].permute(0, 2, 3, 1)  # the (B, h, w, C) rows the forward wrote
     B, h, w, C = f.shape
-    return upsample_nhwc_aligned(f, 2).view(B, 4 * h * w, C), (h, w)
+    return upsample_nhwc_aligned(f, 2, out).view(B, 4 * h * w, C), (h, w)

@@ -9,9 +9,9 @@ in the shipped YAML: ``clustering_mode: "spectral"``, configs/duts-dino-k234-nq2
 csrc/spectral.hip: k-NN graph -> normalised Laplacian -> eigenvectors -> k-means, the algorithm scikit-learn's
 ``SpectralClustering(affinity="precomputed")`` evaluates, which is its third-party witness) and ``kmeans`` (the
 ``cluster_type="kmeans"`` option, csrc/cluster.hip); any other clusterer can be passed as a callable, as the reference's class
-takes one.  The MoCo-v2 / SwAV feature branches: their backbone and its features exist (``selfmask_amd.resnet``: ``ResNet50``,
-``resnet_features``: 2048-d points at stride 8), but both clusterers here are written for the DINO branch's 384-d points, so those
-branches are not wired in yet."""
+takes one.  The MoCo-v2 / SwAV feature branches (``selfmask_amd.resnet``: ``ResNet50``, ``resnet_features``: 2048-d points at
+stride 8) go through ``extract_candidate_masks_resnet``: ``spectral_cluster`` takes 384-d and 2048-d points; ``kmeans`` is written
+for 384-d points only (its centres live in the LDS), so a ResNet type with ``cluster_type="k-means"`` raises."""
 import ctypes as C
 from typing import Dict, Sequence, Tuple
 
@@ -29,6 +29,10 @@ DEFAULT_CLUSTER_TYPE = "spectral"
 FEATURE_UPSAMPLE = {"scale_factor": 2, "mode": "bilinear", "align_corners": True}  # mask_generator.pyc@L159
 MASK_UPSAMPLE_MODE = "nearest"                                                       # mask_generator.pyc@L161
 DINO_TOTAL_STRIDE = 16                                                               # mask_generator.pyc@L150-157 (ResNets: 8)
+RESNET_TOTAL_STRIDE = 8
+RESNET_FEATURE_TYPES = ("mocov2", "swav")                                            # the dilated ResNet-50 types (@L140-157)
+FEATURE_DIMS = (N.EMBED, N.RESNET_EMBED)                                             # the widths the spectral clusterer takes
+MAX_VOTE_CANDIDATES = 64                                                             # sm_vote_masks_*: M <= 64
 
 
 def vote_mask(batch_pred_masks: torch.Tensor, remove_long_masks: bool = True, remove_small_large_masks: bool = False):
@@ -226,21 +230,23 @@ def kmeans(features: torch.Tensor, k: int, iters: int = 20):
 
 def spectral_cluster(features: torch.Tensor, cluster_sizes: Sequence[int] = (2, 3, 4), n_neighbors: int = 10, tol: float = 1e-9,
                      degree: int = 24, max_outer: int = 60, return_details: bool = False):
-    """features (B, n, 384) fp32 on a HIP device -> labels (B, len(cluster_sizes), n) int32: normalised spectral clustering
-    (csrc/spectral.hip), one eigen-solve per image shared by every cluster size.  ``return_details`` adds a dict with the
+    """features (B, n, D) fp32 on a HIP device, D = 384 (DINO tokens) or 2048 (ResNet maps; any other D: ValueError) -> labels
+    (B, len(cluster_sizes), n) int32: normalised spectral clustering (csrc/spectral.hip), one eigen-solve per image shared by every cluster size.  ``return_details`` adds a dict with the
     neighbour lists ``knn`` (B, n, n_neighbors - 1), the ``eigenvalues`` (B, kw) of the normalised Laplacian, the ``embedding``
     (B, n, kw), the eigen-``residuals`` (B, kw) and ``info`` (B, 4: outer iterations, block mat-vecs, converged, guard).
-    Up to 8192 points the neighbours come from a Gram matrix; above (to 32768) from a streaming k-NN that never forms one, with a
-    graph build and workspace linear in n (the same results up to fp32-grade ties of neighbour distances)."""
+    Up to 8192 points the neighbours come from a Gram matrix; above (to 32768) from a streaming k-NN that never forms one (D = 384)
+    or from the matrix in slabs of rows (D = 2048), with a graph build and workspace linear in n (the same results up to fp32-grade
+    ties of neighbour distances).  ``knn`` returns the lists alone."""
     if not features.is_cuda:
         raise RuntimeError("spectral_cluster (MI355X) needs its features on a HIP device; there is no CPU fallback")
     f = features.contiguous().float()
     B, n, d = f.shape
-    assert d == N.EMBED
+    if d not in FEATURE_DIMS:
+        raise ValueError(f"spectral_cluster: {d} features per point ({FEATURE_DIMS[0]} or {FEATURE_DIMS[1]})")
     sizes = [int(k) for k in cluster_sizes]
     kw = max(sizes)
     lib = N.load()
-    nbytes = lib.sm_spectral_workspace_bytes(B, n, n_neighbors, kw)
+    nbytes = lib.sm_spectral_workspace_bytes_dim(B, n, d, n_neighbors, kw)
     if nbytes == 0:
         raise ValueError(f"spectral_cluster: {n} points, n_neighbors {n_neighbors}, {kw} vectors (16 <= n <= 32768, n_neighbors 2..33, k <= 6)")
     dev = f.device
@@ -262,9 +268,37 @@ def spectral_cluster(features: torch.Tensor, cluster_sizes: Sequence[int] = (2, 
                "info": torch.empty((B, 4), dtype=torch.int32, device=dev)}
         a.knn, a.eigenvalues, a.embedding = det["knn"].data_ptr(), det["eigenvalues"].data_ptr(), det["embedding"].data_ptr()
         a.residuals, a.info = det["residuals"].data_ptr(), det["info"].data_ptr()
-    N.check(lib.sm_spectral_cluster_f32(C.byref(a), torch.cuda.current_stream(dev).cuda_stream), "sm_spectral_cluster_f32")
+    N.check(lib.sm_spectral_cluster_dim_f32(C.byref(a), d, torch.cuda.current_stream(dev).cuda_stream), "sm_spectral_cluster_dim_f32")
     labels.record_stream(torch.cuda.current_stream(dev))
     return (labels, det) if return_details else labels
+
+
+def knn(features: torch.Tensor, n_neighbors: int = 10, method: str = "auto") -> torch.Tensor:
+    """features (B, n, D) fp32 on a HIP device, D = 384 or 2048 -> (B, n, min(n_neighbors - 1, n - 1)) int32: for every point its
+    nearest OTHER points by (squared Euclidean distance, index), nearest first - the lists the spectral clusterer builds its graph
+    from (``sm_knn_f32``).  ``method``: "gram" (a Gram matrix on the matrix cores: whole to 8192 points, in slabs of rows above), "stream"
+    (no n x n array) or "auto" (what the clusterer takes at this n and D); n <= 32768; they agree up to fp32-grade ties of distances."""
+    if not features.is_cuda:
+        raise RuntimeError("knn (MI355X) needs its features on a HIP device; there is no CPU fallback")
+    if method not in N.KNN_METHODS:
+        raise ValueError(f"knn: method {method!r} ({', '.join(N.KNN_METHODS)})")
+    f = features.contiguous().float()
+    B, n, d = f.shape
+    if d not in FEATURE_DIMS:
+        raise ValueError(f"knn: {d} features per point ({FEATURE_DIMS[0]} or {FEATURE_DIMS[1]})")
+    lib = N.load()
+    meth = N.KNN_METHODS[method]
+    nbytes = lib.sm_knn_workspace_bytes(B, n, d, n_neighbors, meth)
+    if nbytes == 0:
+        raise ValueError(f"knn: {n} points, n_neighbors {n_neighbors}, method {method!r} (16 <= n <= 32768, n % 4 == 0, "
+                         f"n_neighbors 2..33)")
+    dev = f.device
+    ws = _arena("knn", nbytes, dev)
+    idx = torch.empty((B, n, min(n_neighbors - 1, n - 1)), dtype=torch.int32, device=dev)
+    N.check(lib.sm_knn_f32(f.data_ptr(), B, n, d, n_neighbors, meth, idx.data_ptr(), ws.data_ptr(), nbytes,
+                           torch.cuda.current_stream(dev).cuda_stream), "sm_knn_f32")
+    idx.record_stream(torch.cuda.current_stream(dev))
+    return idx
 
 
 def upsample_tokens_aligned(tokens: torch.Tensor, gh: int, gw: int, scale: int = 2, scratch: bool = False) -> torch.Tensor:
@@ -331,4 +365,28 @@ def extract_candidate_masks(model, x: torch.Tensor, cluster_sizes=(2, 3, 4), clu
     else:
         lab = torch.stack([kmeans(flat, k, iters)[0] for k in cluster_sizes], dim=1)
     out = labels_to_masks_batch(lab, cluster_sizes, 2 * gh, 2 * gw, p // 2, H, W)  # (B, sum k, H, W): one launch
+    return out[0] if B == 1 else out
+
+
+@torch.no_grad()
+def extract_candidate_masks_resnet(backbone, x: torch.Tensor, cluster_sizes=(2, 3, 4), n_neighbors: int = 10,
+                                   cluster_type: str = "spectral") -> torch.Tensor:
+    """mask_generator.pyc@L136-200 for a ResNet feature type ("mocov2" / "swav"): normalised images x (B, 3, H, W) of one size on a
+    HIP device -> ``resnet_features(backbone, x)`` (x zero-padded to a multiple of 8, the last map of the dilated ResNet-50, bilinear
+    x2 with align_corners=True: (B, 4 h w, 2048)) -> ``spectral_cluster`` -> one-hot -> nearest up-sample by total_stride // 2 = 4
+    (@L161) -> crop to (H, W).  Returns (sum(cluster_sizes), H, W) uint8 for B = 1 and (B, sum(cluster_sizes), H, W) otherwise, as
+    ``extract_candidate_masks`` does.  The clusterer's scratch lives in the stream's arena.  k-means on 2048-d points is not built."""
+    from .resnet import resnet_features
+    assert x.dim() == 4
+    assert cluster_type in CLUSTER_TYPES + ("kmeans",), cluster_type
+    if cluster_type != "spectral":
+        raise NotImplementedError("k-means on the 2048-d points of a ResNet feature type is not built (kmeans_kernel keeps its centres for "
+                                  "384-d points in the LDS); use cluster_type='spectral'")
+    B, _, H, W = x.shape
+    s = RESNET_TOTAL_STRIDE
+    hw = backbone.output_shapes(B, -(-H // s) * s, -(-W // s) * s)[-1]  # (B, C, h, w) of the last map
+    rows = _arena("resnet_features", 4 * B * 4 * hw[2] * hw[3] * hw[1], x.device).view(torch.float32)  # valid until the next call on this stream
+    feats, (h, w) = resnet_features(backbone, x, out=rows)  # (B, 2h * 2w, 2048)
+    lab = spectral_cluster(feats, cluster_sizes, n_neighbors)
+    out = labels_to_masks_batch(lab, cluster_sizes, 2 * h, 2 * w, RESNET_TOTAL_STRIDE // 2, H, W)
     return out[0] if B == 1 else out
