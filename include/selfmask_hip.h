@@ -646,6 +646,60 @@ typedef struct sm_jpeg_image {
 int sm_jpeg_decode_batch_u8(const sm_jpeg_image* descr_host, const sm_jpeg_image* descr_dev, int32_t B, int16_t* coef,
                             const uint16_t* qt, uint8_t* pixels_out, void* stream);
 
+/* ---- the entropy decode on the device (csrc/jpeg_entropy.hip; host preparation in csrc/jpeg_host.h): the Huffman decode of the
+ * scan itself, into the coefficient layout and with the verdict of sm_jpeg_entropy_decode, bit for bit.  The host only walks the
+ * markers and removes the byte stuffing (sm_jpeg_scan_prepare, no Huffman decoding); the self-synchronising decode of
+ * Weissenberger & Schmidt ("Accelerating JPEG Decompression on GPUs") runs one workgroup per image. */
+#define SM_JPEG_HUFF_BYTES 1416 /* one table in device form: uint16 fast[512], int32 maxcode[17], int32 valoff[17], uint8 vals[256] */
+#define SM_JPEG_MAX_SCAN_BYTES (1 << 28) /* bit positions are 32-bit: a longer scan is SM_JPEG_UNSUPPORTED for the prepare step */
+#define SM_JPEG_SUBSEQ_BITS_MIN 64       /* at least the longest symbol (16 + 11 bits); a multiple of 32                           */
+#define SM_JPEG_SUBSEQ_BITS_MAX 65536
+#define SM_JPEG_SUBSEQ_BITS_DEFAULT 1024
+#define SM_JPEG_CHUNK_SUBSEQS_MAX 1024   /* = lanes of the workgroup; also the default                                            */
+typedef struct sm_jpeg_segment { /* one restart interval (the whole scan when DRI is 0) */
+    int32_t byte_off, byte_len;  /* inside the unstuffed scan bytes */
+    int32_t mcu0, mcus;          /* first MCU and number of MCUs    */
+} sm_jpeg_segment;
+typedef struct sm_jpeg_scan {
+    int64_t rec_off;   /* byte offset of the image's record inside `scans`, a multiple of 16 (prepare writes 0: the caller's)    */
+    int64_t coef_off;  /* byte offset of its coefficients inside `coef_out`, a multiple of 16 (prepare writes 0: the caller's)   */
+    /* byte offsets inside the record, multiples of 16 */
+    int32_t scan_off;  /* the unstuffed entropy bytes (FF 00 -> FF, markers and fill bytes removed), zero-padded by >= 8 bytes   */
+    int32_t scan_len;
+    int32_t seg_off;   /* n_seg x sm_jpeg_segment                                                                                */
+    int32_t n_seg;
+    int32_t huff_off;  /* n_huff x SM_JPEG_HUFF_BYTES: the tables the scan uses                                                  */
+    int32_t n_huff;
+    int32_t qt_off;    /* components x 64 uint16, natural order (what sm_jpeg_entropy_decode's qt_out gets)                      */
+    int32_t rec_bytes; /* bytes of the record that are in use, a multiple of 16                                                  */
+    int32_t components, mcus_x, mcus_y, restart_interval;
+    int32_t blocks_w[3], blocks_h[3];  /* sm_jpeg_info's */
+    int32_t h[3], v[3];                /* sampling factors per component                                                          */
+    int32_t dc[3], ac[3];              /* per component: index of its DC / AC table among the record's n_huff                     */
+    int32_t td[3], ta[3];              /* the scan header's table selectors those came from                                       */
+} sm_jpeg_scan;
+/* HOST, thread-safe, every read bounds-checked, no GPU.  Bound: record bytes that always suffice for a file of `len` bytes with
+ * this header.  Prepare: probe + ONE pass over the scan that copies the entropy bytes without their stuffing into record_out
+ * (`cap` bytes, 16-byte aligned; SM_ENOSPACE when too small) and checks the marker structure as sm_jpeg_entropy_decode meets it:
+ * RST0..RST7 in order and in the number the header implies, 0xFF fill bytes in front of a marker tolerated, no other marker, EOI
+ * behind the last interval (bytes behind EOI are not looked at, as there).  Any other file is SM_JPEG_UNSUPPORTED
+ * (info->supported = 0).  qt_out (may be NULL) gets the tables as well. */
+size_t sm_jpeg_scan_bound(const sm_jpeg_info* info, size_t len);
+int sm_jpeg_scan_prepare(const uint8_t* bytes, size_t len, uint8_t* record_out, size_t cap, sm_jpeg_scan* scan, uint16_t* qt_out,
+                         sm_jpeg_info* info);
+/* DEVICE: B records -> coefficients exactly as sm_jpeg_entropy_decode writes them (natural order, DC prediction undone, component
+ * planes of blocks_h x blocks_w blocks) at coef_off, and status[b] = 0 where that function returns SM_OK on the file,
+ * SM_JPEG_UNSUPPORTED where it returns that (then image b's coefficients are all zero).  descr_host is validated, descr_dev is the
+ * same table in device memory, `scans` holds the records.  subseq_bits: bits per lane (0 = default 1024; a multiple of 32 in
+ * 64 .. 65536), chunk_subseqs: sub-sequences synchronised at a time (0 = default 1024; 1 .. 1024) - small values make many chunks
+ * and many rounds on tiny images, for tests.  workspace: B x 2 int32, [synchronisation rounds in all, chunks] per image.
+ * status[b] = SM_EINVAL marks a record whose segment table sm_jpeg_scan_prepare did not write.  One launch, one workgroup per
+ * image; nothing is allocated, copied or synchronised. */
+size_t sm_jpeg_entropy_workspace_bytes(const sm_jpeg_scan* descr_host, int32_t B, int32_t subseq_bits, int32_t chunk_subseqs);
+int sm_jpeg_entropy_decode_batch(const sm_jpeg_scan* descr_host, const sm_jpeg_scan* descr_dev, int32_t B, const uint8_t* scans,
+                                 int16_t* coef_out, int32_t* status, void* workspace, size_t workspace_bytes, int32_t subseq_bits,
+                                 int32_t chunk_subseqs, void* stream);
+
 /* ---- PNG encoding on the device (csrc/png.hip): 8-bit grey / RGB / RGBA images that are in device memory -> PNG files in device memory,
  * so that the serving response's three pictures leave the GPU compressed.  The bytes are DEFINED by selfmask_amd/png.py
  * (encode_reference) and are a function of the image and filter_mode alone: per-row adaptive filter (smallest sum of |signed byte|, ties

@@ -216,6 +216,30 @@ extern "C" int sm_jpeg_entropy_decode(const uint8_t* bytes, size_t len, int16_t*
     return SM_OK;
 }
 
+extern "C" size_t sm_jpeg_scan_bound(const sm_jpeg_info* info, size_t len) {
+    if (!info) {
+        sm::set_error("sm_jpeg_scan_bound: null pointer");
+        return 0;
+    }
+    return smjpeg::scan_bound(*info, len);
+}
+
+extern "C" int sm_jpeg_scan_prepare(const uint8_t* bytes, size_t len, uint8_t* record_out, size_t cap, sm_jpeg_scan* scan, uint16_t* qt_out,
+                                    sm_jpeg_info* info) {
+    SM_REQUIRE(bytes && record_out && scan && info, "sm_jpeg_scan_prepare: null pointer");
+    SM_REQUIRE(((uintptr_t)record_out & 15) == 0, "sm_jpeg_scan_prepare: record_out must be 16-byte aligned");
+    smjpeg::Frame f;
+    const bool ok = smjpeg::parse_headers(bytes, len, f);
+    *info = f.info;
+    memset(scan, 0, sizeof(*scan));
+    if (!ok) return SM_JPEG_UNSUPPORTED;
+    const int rc = smjpeg::prepare_scan(bytes, len, f, record_out, cap, *scan);
+    if (rc == SM_ENOSPACE) sm::set_error("sm_jpeg_scan_prepare: room for %zu record bytes, sm_jpeg_scan_bound gives what suffices", cap);
+    if (rc == SM_JPEG_UNSUPPORTED) info->supported = 0;
+    if (rc == SM_OK && qt_out) smjpeg::write_tables(f, qt_out);
+    return rc;
+}
+
 extern "C" int sm_jpeg_decode_batch_u8(const sm_jpeg_image* descr_host, const sm_jpeg_image* descr_dev, int32_t B, int16_t* coef,
                                        const uint16_t* qt, uint8_t* pixels_out, void* stream) {
     SM_REQUIRE(descr_host && descr_dev && coef && qt && pixels_out, "sm_jpeg_decode_batch_u8: null pointer");

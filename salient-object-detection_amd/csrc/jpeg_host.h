@@ -54,6 +54,7 @@ struct Frame {
 // counts[1..16] codes per length, vals: the symbols in code order.  false: not a prefix code libjpeg would accept
 inline bool build_huff(Huff& h, const uint8_t* counts, const uint8_t* vals, int nvals) {
     memset(h.fast, 0, sizeof(h.fast));
+    memset(h.vals, 0, sizeof(h.vals));  // the table travels to the device whole (prepare_scan): no byte of it is left undefined
     memcpy(h.vals, vals, (size_t)nvals);
     int32_t code = 0;
     int k = 0;
@@ -377,6 +378,112 @@ inline bool decode_scan(const uint8_t* p, size_t n, Frame& f, int16_t* coef) {
 
 inline void write_tables(const Frame& f, uint16_t* qt_out) {
     for (int c = 0; c < f.info.components; ++c) memcpy(qt_out + 64 * c, f.qt[f.comp[c].tq], 64 * sizeof(uint16_t));
+}
+
+// ---- preparation of a scan for the device's entropy decoder (csrc/jpeg_entropy.hip): no Huffman decoding here ---------------------
+struct DevHuff {  // SM_JPEG_HUFF_BYTES: Huff without its flag
+    uint16_t fast[1 << FAST_BITS];
+    int32_t maxcode[17], valoff[17];
+    uint8_t vals[256];
+};
+static_assert(sizeof(DevHuff) == SM_JPEG_HUFF_BYTES, "sm_jpeg_scan's table size");
+
+inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// restart intervals the header implies; 0 when the header is not one parse_headers accepted
+inline int64_t scan_segments(const sm_jpeg_info& in) {
+    const int64_t n_mcu = (int64_t)in.mcus_x * in.mcus_y;
+    if (!in.supported || n_mcu < 1) return 0;
+    return in.restart_interval > 0 ? (n_mcu + in.restart_interval - 1) / in.restart_interval : 1;
+}
+
+// bytes of everything in a record but the scan bytes, for `segs` table entries
+inline size_t record_fixed_bytes(int64_t segs) { return align16((size_t)segs * sizeof(sm_jpeg_segment)) + align16(6 * sizeof(DevHuff)) + 384; }
+
+inline size_t scan_bound(const sm_jpeg_info& in, size_t len) {
+    int64_t segs = scan_segments(in);
+    if (segs > (int64_t)(len / 2) + 1) segs = (int64_t)(len / 2) + 1;  // every interval but the last ends in a two-byte marker
+    return record_fixed_bytes(segs) + align16(len + 8);
+}
+
+// SM_OK, SM_JPEG_UNSUPPORTED or SM_ENOSPACE.  f: what parse_headers filled (it returned true).  Record layout:
+// [segment table | Huffman tables | quantisation tables | unstuffed scan bytes + >= 8 zero bytes].
+inline int prepare_scan(const uint8_t* p, size_t n, const Frame& f, uint8_t* rec, size_t cap, sm_jpeg_scan& sc) {
+    const sm_jpeg_info& in = f.info;
+    memset(&sc, 0, sizeof(sc));
+    const int nc = in.components;
+    const int64_t n_mcu = (int64_t)in.mcus_x * in.mcus_y, segs = scan_segments(in);
+    const size_t raw = n - f.scan_pos;  // parse_headers: scan_pos <= n
+    if (segs < 1 || (size_t)(segs - 1) > raw / 2 || raw >= (size_t)SM_JPEG_MAX_SCAN_BYTES) return SM_JPEG_UNSUPPORTED;
+    // the tables the components name, each once
+    int n_huff = 0, slot_dc[4] = {-1, -1, -1, -1}, slot_ac[4] = {-1, -1, -1, -1};
+    for (int c = 0; c < nc; ++c) {
+        if (slot_dc[f.comp[c].td] < 0) slot_dc[f.comp[c].td] = n_huff++;
+        if (slot_ac[f.comp[c].ta] < 0) slot_ac[f.comp[c].ta] = n_huff++;
+    }
+    const size_t seg_at = 0, huff_at = align16((size_t)segs * sizeof(sm_jpeg_segment)), qt_at = huff_at + align16((size_t)n_huff * sizeof(DevHuff)),
+                 scan_at = qt_at + 384;
+    if ((uint64_t)scan_at + align16(raw + 8) >= ((uint64_t)1 << 31)) return SM_JPEG_UNSUPPORTED;  // the record's offsets are 32-bit
+    if (cap < scan_at + align16(raw + 8)) return SM_ENOSPACE;
+    memset(rec + huff_at, 0, qt_at - huff_at);
+    for (int t = 0; t < 4; ++t)
+        for (int k = 0; k < 2; ++k) {
+            const int slot = k ? slot_ac[t] : slot_dc[t];
+            if (slot < 0) continue;
+            const Huff& h = k ? f.ac[t] : f.dc[t];
+            DevHuff d;
+            memcpy(d.fast, h.fast, sizeof(d.fast));
+            d.maxcode[0] = -1, d.valoff[0] = 0;  // lengths start at 1
+            memcpy(d.maxcode + 1, h.maxcode + 1, 16 * sizeof(int32_t));
+            memcpy(d.valoff + 1, h.valoff + 1, 16 * sizeof(int32_t));
+            memcpy(d.vals, h.vals, sizeof(d.vals));
+            memcpy(rec + huff_at + (size_t)slot * sizeof(DevHuff), &d, sizeof(d));
+        }
+    memset(rec + qt_at, 0, 384);
+    for (int c = 0; c < nc; ++c) memcpy(rec + qt_at + 128 * c, f.qt[f.comp[c].tq], 128);
+    // one pass: runs between 0xFF bytes are copied, FF 00 becomes FF, anything else behind an FF ends the interval
+    uint8_t* dst = rec + scan_at;
+    size_t pos = f.scan_pos, w = 0, seg_start = 0;
+    const int64_t ri = in.restart_interval > 0 ? in.restart_interval : n_mcu;
+    for (int64_t k = 0;;) {
+        const uint8_t* q = pos < n ? (const uint8_t*)memchr(p + pos, 0xFF, n - pos) : nullptr;
+        const size_t run = q ? (size_t)(q - (p + pos)) : n - pos;
+        memcpy(dst + w, p + pos, run);  // w + run <= raw: the copy never outruns what it read
+        w += run, pos += run;
+        if (!q) return SM_JPEG_UNSUPPORTED;  // the file ends inside the scan
+        if (pos + 1 < n && p[pos + 1] == 0x00) {
+            dst[w++] = 0xFF;
+            pos += 2;
+            continue;
+        }
+        size_t t = pos;
+        while (t < n && p[t] == 0xFF) ++t;  // fill bytes
+        if (t >= n) return SM_JPEG_UNSUPPORTED;
+        sm_jpeg_segment s;
+        s.byte_off = (int32_t)seg_start, s.byte_len = (int32_t)(w - seg_start);
+        s.mcu0 = (int32_t)(k * ri), s.mcus = (int32_t)(n_mcu - k * ri < ri ? n_mcu - k * ri : ri);
+        memcpy(rec + seg_at + (size_t)k * sizeof(s), &s, sizeof(s));
+        if (k == segs - 1) {
+            if (p[t] != 0xD9) return SM_JPEG_UNSUPPORTED;  // EOI belongs here and nothing else
+            break;
+        }
+        if (p[t] != 0xD0 + (int)(k & 7)) return SM_JPEG_UNSUPPORTED;
+        ++k, seg_start = w, pos = t + 1;
+    }
+    memset(dst + w, 0, align16(w + 8) - w);
+    sc.scan_off = (int32_t)scan_at, sc.scan_len = (int32_t)w;
+    sc.seg_off = (int32_t)seg_at, sc.n_seg = (int32_t)segs;
+    sc.huff_off = (int32_t)huff_at, sc.n_huff = n_huff;
+    sc.qt_off = (int32_t)qt_at;
+    sc.rec_bytes = (int32_t)(scan_at + align16(w + 8));
+    sc.components = nc, sc.mcus_x = in.mcus_x, sc.mcus_y = in.mcus_y, sc.restart_interval = in.restart_interval;
+    for (int c = 0; c < nc; ++c) {
+        sc.blocks_w[c] = in.blocks_w[c], sc.blocks_h[c] = in.blocks_h[c];
+        sc.h[c] = f.comp[c].h, sc.v[c] = f.comp[c].v;
+        sc.td[c] = f.comp[c].td, sc.ta[c] = f.comp[c].ta;
+        sc.dc[c] = slot_dc[f.comp[c].td], sc.ac[c] = slot_ac[f.comp[c].ta];
+    }
+    return SM_OK;
 }
 
 }  // namespace smjpeg

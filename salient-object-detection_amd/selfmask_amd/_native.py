@@ -178,6 +178,20 @@ class JpegImage(C.Structure):
                 ("sampling", C.c_int32), ("blocks_w", C.c_int32 * 3), ("blocks_h", C.c_int32 * 3), ("reserved", C.c_int32 * 2)]
 
 
+class JpegSegment(C.Structure):
+    _fields_ = [("byte_off", C.c_int32), ("byte_len", C.c_int32), ("mcu0", C.c_int32), ("mcus", C.c_int32)]
+
+
+class JpegScan(C.Structure):
+    _fields_ = [("rec_off", C.c_int64), ("coef_off", C.c_int64), ("scan_off", C.c_int32), ("scan_len", C.c_int32), ("seg_off", C.c_int32),
+                ("n_seg", C.c_int32), ("huff_off", C.c_int32), ("n_huff", C.c_int32), ("qt_off", C.c_int32), ("rec_bytes", C.c_int32),
+                ("components", C.c_int32), ("mcus_x", C.c_int32), ("mcus_y", C.c_int32), ("restart_interval", C.c_int32),
+                ("blocks_w", C.c_int32 * 3), ("blocks_h", C.c_int32 * 3), ("h", C.c_int32 * 3), ("v", C.c_int32 * 3), ("dc", C.c_int32 * 3),
+                ("ac", C.c_int32 * 3), ("td", C.c_int32 * 3), ("ta", C.c_int32 * 3)]
+
+
+JPEG_HUFF_BYTES = 1416
+JPEG_SUBSEQ_BITS_MIN, JPEG_SUBSEQ_BITS_DEFAULT, JPEG_CHUNK_SUBSEQS_MAX = 64, 1024, 1024
 JPEG_UNSUPPORTED = 1
 JPEG_GRAY, JPEG_444, JPEG_422, JPEG_420 = range(4)
 
@@ -287,6 +301,10 @@ SYMBOLS = {
     "sm_jpeg_probe": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(JpegInfo)]),
     "sm_jpeg_entropy_decode": (C.c_int, [C.c_char_p, C.c_size_t, fp, C.c_size_t, fp, C.POINTER(JpegInfo)]),
     "sm_jpeg_decode_batch_u8": (C.c_int, [fp, fp, C.c_int32, fp, fp, fp, fp]),
+    "sm_jpeg_scan_bound": (C.c_size_t, [C.POINTER(JpegInfo), C.c_size_t]),
+    "sm_jpeg_scan_prepare": (C.c_int, [C.c_char_p, C.c_size_t, fp, C.c_size_t, C.POINTER(JpegScan), fp, C.POINTER(JpegInfo)]),
+    "sm_jpeg_entropy_workspace_bytes": (C.c_size_t, [fp, C.c_int32, C.c_int32, C.c_int32]),
+    "sm_jpeg_entropy_decode_batch": (C.c_int, [fp, fp, C.c_int32, fp, fp, fp, fp, C.c_size_t, C.c_int32, C.c_int32, fp]),
     "sm_conv_gather_f16x2": (C.c_int, [fp, fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp]),
     "sm_resnet_stem_gather_f16x2": (C.c_int, [fp, fp, C.c_int32, C.c_int32, C.c_int32, fp]),
     "sm_maxpool3x3s2_nhwc_f32": (C.c_int, [fp, fp, fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp]),

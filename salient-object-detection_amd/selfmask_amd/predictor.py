@@ -27,6 +27,7 @@ DEFAULT_CAP = 8192       # run boundaries stored per image before the retry, as 
 MAX_PIXELS = 1 << 22     # sm_predict_masks_f32's largest image
 MAX_OBJECTS_WIDTH = 16384  # sm_mask_objects' widest image
 DECODES = ("host", "device")
+ENTROPIES = ("host", "device")  # who Huffman-decodes the scans of decode="device" (selfmask_amd/jpeg.py)
 
 
 class _Files:
@@ -49,15 +50,15 @@ class _DeviceDecoded:
     One feeder thread runs the host halves (file reads + entropy decode on the thread pool) ``depth`` batches ahead; the consumer
     queues the device half on its batch's stream (``HostBatch.to_device``)."""
 
-    def __init__(self, p_images, batches, threads, depth):
-        self.p_images, self.batches, self.threads, self.depth = p_images, batches, threads, max(1, depth)
+    def __init__(self, p_images, batches, threads, depth, entropy="host"):
+        self.p_images, self.batches, self.threads, self.depth, self.entropy = p_images, batches, threads, max(1, depth), entropy
 
     def __iter__(self):
         from concurrent.futures import ThreadPoolExecutor
         from .jpeg import HostBatch
         with ThreadPoolExecutor(max_workers=1, thread_name_prefix="sm_jpeg_feed") as feeder:
             def submit(k):
-                return feeder.submit(HostBatch, [self.p_images[i] for i in self.batches[k]], self.threads)
+                return feeder.submit(HostBatch, [self.p_images[i] for i in self.batches[k]], self.threads, self.entropy)
             inflight = deque(submit(k) for k in range(min(self.depth, len(self.batches))))
             hb = None
             try:
@@ -77,7 +78,8 @@ class _DeviceDecoded:
 
 class SaliencyPredictor:
     def __init__(self, network, device: torch.device = torch.device("cuda:0"), batch_size: int = 64, streams: int = 3,
-                 workers: Optional[int] = None, hip_graph: bool = True, cap: int = DEFAULT_CAP, decode: str = "host", png_encoder: str = "host"):
+                 workers: Optional[int] = None, hip_graph: bool = True, cap: int = DEFAULT_CAP, decode: str = "host", png_encoder: str = "host",
+                 entropy: str = "host"):
         """``network``: a ``selfmask_amd.MaskFormer`` with ``use_binary_classifier=True`` on ``device``; ``batch_size``: the most
         images per forward (of ONE token grid at native resolution); ``streams``: batches in flight; ``workers``: decode processes
         (default: this rank's share of the host cores); ``hip_graph``: replay recurring batch shapes as captured graphs;
@@ -85,9 +87,16 @@ class SaliencyPredictor:
         JPEGs entropy-decoded on at most 16 host THREADS (``workers`` caps them) and finished on the device, every other file by
         Pillow on those threads: the same pixels, so the same results, without worker processes; ``png_encoder``: who writes the
         soft maps' PNG files (output ``"soft_png"``, ``--png_dir``): "host" = Pillow from the soft maps copied to the host; "device" =
-        csrc/png.hip on the packed planes, only the files cross - other bytes, the same pixels for whoever reads them."""
+        csrc/png.hip on the packed planes, only the files cross - other bytes, the same pixels for whoever reads them; ``entropy``
+        (with ``decode="device"`` only): "host" = those threads Huffman-decode; "device" = they only strip markers and byte stuffing
+        and the GPU decodes the scans (csrc/jpeg_entropy.hip) - the same pixels, at the price of one wait per batch for its verdicts."""
         if decode not in DECODES:
             raise ValueError(f"decode={decode!r}: one of {DECODES}")
+        if entropy not in ENTROPIES:
+            raise ValueError(f"entropy={entropy!r}: one of {ENTROPIES}")
+        if entropy == "device" and decode != "device":
+            raise ValueError(f"entropy={entropy!r} needs decode='device' (got decode={decode!r}): the device decodes the scans of the "
+                             f"files it also finishes")
         if png_encoder not in PNG_ENCODERS:
             raise ValueError(f"png_encoder={png_encoder!r}: one of {PNG_ENCODERS}")
         device = torch.device(device)
@@ -104,7 +113,7 @@ class SaliencyPredictor:
                                f"fallback - call network.to(device)")
         self.network, self.device, self.batch_size = network, device, max(1, int(batch_size))
         self.streams, self.workers, self.hip_graph, self.cap = max(1, int(streams)), workers, bool(hip_graph), int(cap)
-        self.decode, self.png_encoder = decode, png_encoder
+        self.decode, self.png_encoder, self.entropy = decode, png_encoder, entropy
         self.last_best: Dict[str, int] = {}
         self._ring = None
 
@@ -263,7 +272,7 @@ class SaliencyPredictor:
         avg = max(1, len(p_images) // len(batches))  # buckets are often smaller than batch_size: keep every decode worker busy
         depth = max(len(ring.streams) + 1, -(-2 * (self.workers or default_workers()) // avg))
         if self.decode == "device":
-            loader = _DeviceDecoded(p_images, batches, self.workers, len(ring.streams) + 1)
+            loader = _DeviceDecoded(p_images, batches, self.workers, len(ring.streams) + 1, self.entropy)
         else:
             loader = PrefetchingLoader(_Files(p_images), range(len(p_images)), self.batch_size, workers=self.workers, depth=depth,
                                        batches=batches, pack=True, pack_size=img_size)
@@ -384,6 +393,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--max_objects", type=int, default=16, help="the largest objects kept per image (1 .. 64)")
     ap.add_argument("--decode", type=str, default="host", choices=list(DECODES),
                     help="device: baseline JPEGs are entropy-decoded on host threads and finished on the GPU (same pixels as Pillow)")
+    ap.add_argument("--entropy", type=str, default="host", choices=list(ENTROPIES),
+                    help="device (with --decode device): the GPU also Huffman-decodes the scans; the host threads only strip markers and stuffing")
     ap.add_argument("--gpu_id", type=int, default=0)
     return ap
 
@@ -401,7 +412,8 @@ def main(argv=None):
     model = get_model("maskformer", configs=cfg)
     load_checkpoint(model, args.p_state_dict)
     model = model.to(device).eval()
-    pred = SaliencyPredictor(model, device=device, batch_size=args.batch_size, decode=args.decode, png_encoder=args.png_encoder)
+    pred = SaliencyPredictor(model, device=device, batch_size=args.batch_size, decode=args.decode, png_encoder=args.png_encoder,
+                             entropy=args.entropy)
     soft = "soft_png" if pred.png_encoder == "device" else "soft"
     outputs = ("rle",) + ((soft,) if args.png_dir else ()) + (("objects",) if args.objects_out else ())
     objects = dict(connectivity=args.connectivity, min_area=args.min_area, max_objects=args.max_objects) if args.objects_out else None
