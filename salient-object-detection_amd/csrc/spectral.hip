@@ -113,6 +113,44 @@ __device__ __forceinline__ void block_sum(double (&v)[NV], double* scratch) {
 // 2. k-NN selection: one wave per row of the Gram matrix (or of a slab of its rows).  key_j = G_jj - 2 G_ij orders the points like |f_i - f_j|^2 (G_ii is
 // common to the row).  Every lane keeps the CAP smallest (key, j) of its strided share in registers (sorted, insertion by
 // compare-select), then the wave merges the 64 sorted lists: CAP... m rounds of a 64-lane arg-min over the list heads.
+// The list is two arrays of the kernel's own - key[CAP] ascending, id[CAP] beside it - and the three operations on it are macros over
+// those names, shared by the three k-NN kernels.  (As __forceinline__ functions taking the arrays, by reference or pointer or as one
+// struct, the same expressions were allocated otherwise: knn_select_kernel<32> 79 -> 108-134 VGPRs, 6 -> 3-4 waves per SIMD, and the
+// streaming kernels kept a list in scratch, 80-260 B per lane.)
+#define KNN_LIST_INIT()                                                                                                    \
+    _Pragma("unroll") for (int p = 0; p < CAP; ++p) { key[p] = INFINITY; id[p] = 0x7fffffff; }
+// (the caller admits kj: below the last key, or below the m-th).  j ascends within a lane: on equal keys the earlier index stays in front
+#define KNN_LIST_INSERT(kj, j)                                                                                              \
+    {                                                                                                                       \
+        _Pragma("unroll") for (int p = CAP - 1; p > 0; --p) {                                                               \
+            const bool up = kj < key[p - 1]; /* the element above moves down */                                             \
+            const bool here = !up && kj < key[p];                                                                           \
+            key[p] = up ? key[p - 1] : (here ? kj : key[p]);                                                                \
+            id[p] = up ? id[p - 1] : (here ? j : id[p]);                                                                    \
+        }                                                                                                                   \
+        if (kj < key[0]) { key[0] = kj; id[0] = j; }                                                                        \
+    }
+// one round of the merge of the sorted lists of LANES neighbouring lanes: bi = the arg-min over their heads (ties to the lower index;
+// 0x7fffffff once the lists are empty), STORE runs, and the owner pops its head (indices are unique across lanes)
+#define KNN_LIST_MERGE(LANES, STORE)                                                                                        \
+    {                                                                                                                       \
+        float bk = key[0];                                                                                                  \
+        int bi = id[0];                                                                                                     \
+        _Pragma("unroll") for (int o = (LANES) / 2; o > 0; o >>= 1) {                                                        \
+            const float ok = __shfl_xor(bk, o, 64);                                                                         \
+            const int oi = __shfl_xor(bi, o, 64);                                                                           \
+            if (ok < bk || (ok == bk && oi < bi)) { bk = ok; bi = oi; }                                                     \
+        }                                                                                                                   \
+        STORE;                                                                                                              \
+        if (id[0] == bi) {                                                                                                  \
+            _Pragma("unroll") for (int p = 0; p < CAP - 1; ++p) { key[p] = key[p + 1]; id[p] = id[p + 1]; }                 \
+            key[CAP - 1] = INFINITY;                                                                                        \
+            id[CAP - 1] = 0x7fffffff;                                                                                       \
+        }                                                                                                                   \
+    }
+// entry r of row's list: non-finite features leave the lists empty - any valid index keeps the later kernels inside their arrays
+__device__ __forceinline__ int knn_entry(int bi, int n, int row, int r) { return (unsigned)bi < (unsigned)n ? bi : (row + 1 + r) % n; }
+
 template <int CAP>
 __global__ __launch_bounds__(256) void knn_select_kernel(const float* __restrict__ gram_all, const float* __restrict__ sq_all, int n, int m,
                                                          int* __restrict__ idx_all, int row0, int rows) {
@@ -123,40 +161,15 @@ __global__ __launch_bounds__(256) void knn_select_kernel(const float* __restrict
     const float* sq = sq_all + (int64_t)blockIdx.y * n;
     float key[CAP];
     int id[CAP];
-#pragma unroll
-    for (int p = 0; p < CAP; ++p) { key[p] = INFINITY; id[p] = 0x7fffffff; }
+    KNN_LIST_INIT()
     for (int j = lane; j < n; j += 64) {
         if (j == row) continue;
         const float kj = sq[j] - 2.0f * g[j];
-        if (kj < key[CAP - 1]) {  // j ascends within a lane: on equal keys the earlier index stays in front
-#pragma unroll
-            for (int p = CAP - 1; p > 0; --p) {
-                const bool up = kj < key[p - 1];  // the element above moves down
-                const bool here = !up && kj < key[p];
-                key[p] = up ? key[p - 1] : (here ? kj : key[p]);
-                id[p] = up ? id[p - 1] : (here ? j : id[p]);
-            }
-            if (kj < key[0]) { key[0] = kj; id[0] = j; }
-        }
+        if (kj < key[CAP - 1]) KNN_LIST_INSERT(kj, j)
     }
     int* out = idx_all + ((int64_t)blockIdx.y * n + row) * m;
     for (int r = 0; r < m; ++r) {
-        float bk = key[0];
-        int bi = id[0];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ok = __shfl_xor(bk, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            if (ok < bk || (ok == bk && oi < bi)) { bk = ok; bi = oi; }
-        }
-        // non-finite features leave the lists empty: any valid index keeps the later kernels inside their arrays
-        if (lane == 0) out[r] = (unsigned)bi < (unsigned)n ? bi : (row + 1 + r) % n;
-        if (id[0] == bi) {  // the owner pops its head (indices are unique across lanes)
-#pragma unroll
-            for (int p = 0; p < CAP - 1; ++p) { key[p] = key[p + 1]; id[p] = id[p + 1]; }
-            key[CAP - 1] = INFINITY;
-            id[CAP - 1] = 0x7fffffff;
-        }
+        KNN_LIST_MERGE(64, if (lane == 0) out[r] = knn_entry(bi, n, row, r))
     }
 }
 
@@ -188,6 +201,21 @@ __device__ __forceinline__ void ks_load_frag(const char* row, KsFrag& f) {
     }
 }
 
+// one 16x16x32 step of gemm_f16x2's three-product form over F16X2 operands (hi, lo halves): acc += a_hi b_hi, crs += a_hi b_lo + a_lo b_hi,
+// and the value the two accumulators stand for
+__device__ __forceinline__ void f16x2_step(f16x8 ah, f16x8 al, f16x8 bh, f16x8 bl, f32x4& acc, f32x4& crs) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc, 0, 0, 0);
+    crs = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, crs, 0, 0, 0);
+    crs = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, crs, 0, 0, 0);
+}
+__device__ __forceinline__ float f16x2_join(float acc, float crs) { return acc + crs * (1.0f / 2048.0f); }
+__device__ __forceinline__ f32x4 f16x2_join(f32x4 acc, f32x4 crs) {
+    f32x4 g;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) g[r] = f16x2_join(acc[r], crs[r]);
+    return g;
+}
+
 // D[i][j] = sum_k Q[i][k] C[j][k] for the 16 rows of `qf` and the 16 points whose F16X2 rows `crow` points at (lane's point l & 15);
 // lane l returns D[4 (l >> 4) + r][l & 15] in element r
 __device__ __forceinline__ f32x4 ks_tile(const KsFrag& qf, const char* crow) {
@@ -197,14 +225,9 @@ __device__ __forceinline__ f32x4 ks_tile(const KsFrag& qf, const char* crow) {
     for (int s = 0; s < KS_KSTEPS; ++s) {
         const f16x8 ch = *reinterpret_cast<const f16x8*>(crow + (4 * s + q) * 32);
         const f16x8 cl = *reinterpret_cast<const f16x8*>(crow + (4 * s + q) * 32 + 16);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(qf.h[s], ch, acc, 0, 0, 0);
-        crs = __builtin_amdgcn_mfma_f32_16x16x32_f16(qf.h[s], cl, crs, 0, 0, 0);
-        crs = __builtin_amdgcn_mfma_f32_16x16x32_f16(qf.l[s], ch, crs, 0, 0, 0);
+        f16x2_step(qf.h[s], qf.l[s], ch, cl, acc, crs);
     }
-    f32x4 g;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) g[r] = acc[r] + crs[r] * (1.0f / 2048.0f);
-    return g;
+    return f16x2_join(acc, crs);
 }
 
 // sq_p = <f_p, f_p> as ks_tile forms it: the diagonal of the 16 x 16 tile of a block of 16 points with itself (one wave per block),
@@ -222,13 +245,9 @@ __global__ __launch_bounds__(256) void knn_sqnorm_kernel(const float* __restrict
     for (int s = 0; s < D / 32; ++s) {
         const f16x8 h = *reinterpret_cast<const f16x8*>(row + (4 * s + q) * 32);
         const f16x8 l = *reinterpret_cast<const f16x8*>(row + (4 * s + q) * 32 + 16);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(h, h, acc, 0, 0, 0);
-        crs = __builtin_amdgcn_mfma_f32_16x16x32_f16(h, l, crs, 0, 0, 0);
-        crs = __builtin_amdgcn_mfma_f32_16x16x32_f16(l, h, crs, 0, 0, 0);
+        f16x2_step(h, l, h, l, acc, crs);
     }
-    f32x4 g;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) g[r] = acc[r] + crs[r] * (1.0f / 2048.0f);
+    const f32x4 g = f16x2_join(acc, crs);
     const int i = lane & 15, r = i - 4 * (lane >> 4);  // D[i][i] sits in element i - 4 (lane >> 4) of lane i + 16 (i >> 2)
     float v = g[0];
 #pragma unroll
@@ -251,8 +270,7 @@ __global__ __launch_bounds__(256) void knn_stream_kernel(const float* __restrict
     const int srow = lane >> 2, ssub = lane & 3, row = q0 + srow;
     float key[CAP], thr = INFINITY;  // thr: the lane's m-th key so far
     int id[CAP];
-#pragma unroll
-    for (int p = 0; p < CAP; ++p) { key[p] = INFINITY; id[p] = 0x7fffffff; }
+    KNN_LIST_INIT()
     // a tile moves global -> registers -> LDS in two halves (the whole tile in flight would spill the query fragments)
     auto stage = [&](int c0) {
 #pragma unroll
@@ -289,15 +307,8 @@ __global__ __launch_bounds__(256) void knn_stream_kernel(const float* __restrict
             const int jl = ssub * 8 + cc, j = c0 + jl;
             if (j >= n || j == row) continue;
             const float kj = keys[wave][srow][jl];
-            if (kj < thr) {  // j ascends within a lane: on equal keys the earlier index stays in front
-#pragma unroll
-                for (int p = CAP - 1; p > 0; --p) {
-                    const bool up = kj < key[p - 1];
-                    const bool here = !up && kj < key[p];
-                    key[p] = up ? key[p - 1] : (here ? kj : key[p]);
-                    id[p] = up ? id[p - 1] : (here ? j : id[p]);
-                }
-                if (kj < key[0]) { key[0] = kj; id[0] = j; }
+            if (kj < thr) {
+                KNN_LIST_INSERT(kj, j)
 #pragma unroll
                 for (int p = 0; p < CAP; ++p) thr = p == m - 1 ? key[p] : thr;
             }
@@ -305,21 +316,7 @@ __global__ __launch_bounds__(256) void knn_stream_kernel(const float* __restrict
     }
     int* out = idx_all + ((int64_t)img * n + row) * m;
     for (int r = 0; r < m; ++r) {
-        float bk = key[0];
-        int bi = id[0];
-#pragma unroll
-        for (int o = 1; o < 4; o <<= 1) {
-            const float ok = __shfl_xor(bk, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            if (ok < bk || (ok == bk && oi < bi)) { bk = ok; bi = oi; }
-        }
-        if (ssub == 0 && row < n) out[r] = (unsigned)bi < (unsigned)n ? bi : (row + 1 + r) % n;  // (knn_select_kernel's fallback)
-        if (id[0] == bi) {
-#pragma unroll
-            for (int p = 0; p < CAP - 1; ++p) { key[p] = key[p + 1]; id[p] = id[p + 1]; }
-            key[CAP - 1] = INFINITY;
-            id[CAP - 1] = 0x7fffffff;
-        }
+        KNN_LIST_MERGE(4, if (ssub == 0 && row < n) out[r] = knn_entry(bi, n, row, r))
     }
 }
 
@@ -360,8 +357,7 @@ __global__ __launch_bounds__(256) void knn_stream_chunked_kernel(const float* __
     const int srow = lane >> 2, ssub = lane & 3, row = q0 + wave * 16 + srow;
     float key[CAP], thr = INFINITY;  // thr: the lane's m-th key so far
     int id[CAP];
-#pragma unroll
-    for (int p = 0; p < CAP; ++p) { key[p] = INFINITY; id[p] = 0x7fffffff; }
+    KNN_LIST_INIT()
     // staging: piece tid + 256 i = (row (tid >> 4) + 16 i, slot tid & 15) of both operands' chunk
     const int prow = tid >> 4, pslot = tid & 15;
     f32x4 vq[KC_PIECES], vc[KC_PIECES];
@@ -400,9 +396,7 @@ __global__ __launch_bounds__(256) void knn_stream_chunked_kernel(const float* __
     {                                                                                                                       \
         const f16x8 chh = *reinterpret_cast<const f16x8*>(ctile + kc_lds((u) * 16 + fr, (4 * s + fq) * 2));                 \
         const f16x8 cl = *reinterpret_cast<const f16x8*>(ctile + kc_lds((u) * 16 + fr, (4 * s + fq) * 2 + 1));              \
-        ACC = __builtin_amdgcn_mfma_f32_16x16x32_f16(qh, chh, ACC, 0, 0, 0);                                                \
-        CRS = __builtin_amdgcn_mfma_f32_16x16x32_f16(qh, cl, CRS, 0, 0, 0);                                                 \
-        CRS = __builtin_amdgcn_mfma_f32_16x16x32_f16(ql, chh, CRS, 0, 0, 0);                                                \
+        f16x2_step(qh, ql, chh, cl, ACC, CRS);                                                                              \
     }
                 KC_SUBTILE(0, acc0, crs0)
                 KC_SUBTILE(1, acc1, crs1)
@@ -417,7 +411,7 @@ __global__ __launch_bounds__(256) void knn_stream_chunked_kernel(const float* __
     {                                                                                                                       \
         const float sj = sq[min(c0 + (u) * 16 + fr, n - 1)];                                                                \
         _Pragma("unroll") for (int r = 0; r < 4; ++r)                                                                       \
-            keys[wave][4 * fq + r][(u) * 16 + fr] = sj - 2.0f * (ACC[r] + CRS[r] * (1.0f / 2048.0f));                       \
+            keys[wave][4 * fq + r][(u) * 16 + fr] = sj - 2.0f * f16x2_join(ACC[r], CRS[r]);                                 \
     }
         KC_KEYS(0, acc0, crs0)
         KC_KEYS(1, acc1, crs1)
@@ -430,15 +424,8 @@ __global__ __launch_bounds__(256) void knn_stream_chunked_kernel(const float* __
             const int jl = ssub * (KC_COLS / 4) + cc, j = c0 + jl;
             if (j >= n || j == row) continue;
             const float kj = keys[wave][srow][jl];
-            if (kj < thr) {  // j ascends within a lane: on equal keys the earlier index stays in front
-#pragma unroll
-                for (int p = CAP - 1; p > 0; --p) {
-                    const bool up = kj < key[p - 1];
-                    const bool here = !up && kj < key[p];
-                    key[p] = up ? key[p - 1] : (here ? kj : key[p]);
-                    id[p] = up ? id[p - 1] : (here ? j : id[p]);
-                }
-                if (kj < key[0]) { key[0] = kj; id[0] = j; }
+            if (kj < thr) {
+                KNN_LIST_INSERT(kj, j)
 #pragma unroll
                 for (int p = 0; p < CAP; ++p) thr = p == m - 1 ? key[p] : thr;
             }
@@ -446,24 +433,13 @@ __global__ __launch_bounds__(256) void knn_stream_chunked_kernel(const float* __
     }
     int* out = idx_all + ((int64_t)img * n + row) * m;
     for (int r = 0; r < m; ++r) {
-        float bk = key[0];
-        int bi = id[0];
-#pragma unroll
-        for (int o = 1; o < 4; o <<= 1) {
-            const float ok = __shfl_xor(bk, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            if (ok < bk || (ok == bk && oi < bi)) { bk = ok; bi = oi; }
-        }
-        if (ssub == 0 && row < n) out[r] = (unsigned)bi < (unsigned)n ? bi : (row + 1 + r) % n;  // (knn_select_kernel's fallback)
-        if (id[0] == bi) {
-#pragma unroll
-            for (int p = 0; p < CAP - 1; ++p) { key[p] = key[p + 1]; id[p] = id[p + 1]; }
-            key[CAP - 1] = INFINITY;
-            id[CAP - 1] = 0x7fffffff;
-        }
+        KNN_LIST_MERGE(4, if (ssub == 0 && row < n) out[r] = knn_entry(bi, n, row, r))
     }
 }
 #undef KC_FETCH
+#undef KNN_LIST_INIT
+#undef KNN_LIST_INSERT
+#undef KNN_LIST_MERGE
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // 3. the graph as ONE adjacency list per point: its own m neighbours (nearest first), then the points that list it in ascending
@@ -709,37 +685,63 @@ __device__ __forceinline__ SpChunk sp_gather_chunk(const char* col, uint2 q) {
     return c;
 }
 
-// (Two items per lane at a time - two independent chains of LDS round trips per wave - changed nothing: 17.0 k against 16.7 k cycles
-// per step; the step is not bound by one chain's latency.)
+// What a walk over the resident graph reads past the end of a list: a chunk of four entries at the zero row.  The caller forms it once,
+// before its loop over the items, and lends it by reference: "c < my ? e[c] : zz" compiles to a load through a selected address, so zz
+// lives in a stack slot - the caller's, written once per call (by value it was written once per item).
+__device__ __forceinline__ uint2 sp_res_padding(const SpResGraph& rg) {
+    return make_uint2(rg.zoff | (rg.zoff << 16), rg.zoff | (rg.zoff << 16));
+}
+// An item = (sorted position, TC = 2 columns, or the one of W = 1): the row at that position, its `my` chunks of four entries at `e`,
+// and the trip count of the wave - its first row is its longest
+struct SpResItem { int i, jj, my, nch; const uint2* e; };
+template <int W>
+__device__ __forceinline__ SpResItem sp_res_item(const SpResGraph& rg, int t) {
+    constexpr int TC = W >= 2 ? 2 : 1, PER_ROW = W / TC;
+    const int pos = t / PER_ROW;
+    SpResItem it;
+    it.jj = (t % PER_ROW) * TC;
+    it.i = rg.row[pos];
+    it.my = (int)rg.ptr4[pos + 1] - (int)rg.ptr4[pos];
+    it.e = reinterpret_cast<const uint2*>(rg.ent + (int)rg.ptr4[pos] * 4);
+    it.nch = __builtin_amdgcn_readfirstlane(it.my);
+    return it;
+}
+// (a0, a1) = the sums, in list order, of the two columns at `col` + an entry's offset over the item's list: the next chunk's gathers
+// and the index pair after it are in flight while this chunk is summed.  (Two items per lane at a time - two independent chains of
+// LDS round trips per wave - changed nothing: 17.0 k against 16.7 k cycles per step; the step is not bound by one chain's latency.)
+template <int TC>
+__device__ __forceinline__ void sp_res_sum(const SpResItem& it, const uint2& zz, const char* col, double& a0, double& a1) {
+    a0 = 0.0;
+    a1 = 0.0;
+    SpChunk cur = sp_gather_chunk<TC>(col, 0 < it.my ? it.e[0] : zz);
+    uint2 qn = 1 < it.my ? it.e[1] : zz;
+#pragma unroll 1
+    for (int c = 0; c < it.nch; ++c) {
+        SpChunk nxt = cur;
+        if (c + 1 < it.nch) nxt = sp_gather_chunk<TC>(col, qn);
+        const uint2 qnn = c + 2 < it.my ? it.e[c + 2] : zz;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { a0 += cur.v[u].x; a1 += cur.v[u].y; }
+        cur = nxt;
+        qn = qnn;
+    }
+}
+
 template <int W, bool LAST>
 __device__ __forceinline__ void sp_filter_step_resident(const SpResGraph& rg, int n, const double* yl, double* xl, double c0, double f1,
                                                         double f2) {
     constexpr int TC = W >= 2 ? 2 : 1, PER_ROW = W / TC;
     const int total = n * PER_ROW;
-    const uint2 zz = make_uint2(rg.zoff | (rg.zoff << 16), rg.zoff | (rg.zoff << 16));
+    const uint2 zz = sp_res_padding(rg);
 #pragma unroll 1
     for (int t = threadIdx.x; t < total; t += SP_THREADS) {
-        const int pos = t / PER_ROW, jj = (t % PER_ROW) * TC;
-        const int i = rg.row[pos], my = (int)rg.ptr4[pos + 1] - (int)rg.ptr4[pos];
-        const uint2* e = reinterpret_cast<const uint2*>(rg.ent + (int)rg.ptr4[pos] * 4);
-        const int nch = __builtin_amdgcn_readfirstlane(my);  // the wave's first row is its longest
-        const char* ycol = reinterpret_cast<const char*>(yl + jj);
+        const SpResItem it = sp_res_item<W>(rg, t);
+        const int i = it.i, jj = it.jj;
         const double2 yo = sp_load_cols<TC>(reinterpret_cast<const char*>(yl + i * W + jj));
         const double2 xo = sp_load_cols<TC>(reinterpret_cast<const char*>(xl + i * W + jj));
         const double w = rg.isd[i];
-        double a0 = 0.0, a1 = 0.0;
-        SpChunk cur = sp_gather_chunk<TC>(ycol, 0 < my ? e[0] : zz);
-        uint2 qn = 1 < my ? e[1] : zz;
-#pragma unroll 1
-        for (int c = 0; c < nch; ++c) {
-            SpChunk nxt = cur;
-            if (c + 1 < nch) nxt = sp_gather_chunk<TC>(ycol, qn);       // the next chunk's gathers and the index pair after it are in flight
-            const uint2 qnn = c + 2 < my ? e[c + 2] : zz;           // while this chunk is summed
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { a0 += cur.v[u].x; a1 += cur.v[u].y; }
-            cur = nxt;
-            qn = qnn;
-        }
+        double a0, a1;
+        sp_res_sum<TC>(it, zz, reinterpret_cast<const char*>(yl + jj), a0, a1);
         const double h = 0.5 * w * w;
         const double l0 = yo.x - h * a0, l1 = yo.y - h * a1;
         double2 xn;
@@ -785,21 +787,19 @@ template <int W>
 __device__ __forceinline__ void sp_apply_sym_resident(const SpResGraph& rg, int n, const double* in, double* out) {
     constexpr int TC = W >= 2 ? 2 : 1, PER_ROW = W / TC, ISD_SHIFT = W == 8 ? 3 : W == 4 ? 2 : 1;  // row byte offset -> isd byte offset
     const int total = n * PER_ROW;
-    const uint2 zz = make_uint2(rg.zoff | (rg.zoff << 16), rg.zoff | (rg.zoff << 16));
+    const uint2 zz = sp_res_padding(rg);
     const char* isdb = reinterpret_cast<const char*>(rg.isd);
 #pragma unroll 1
     for (int t = threadIdx.x; t < total; t += SP_THREADS) {
-        const int pos = t / PER_ROW, jj = (t % PER_ROW) * TC;
-        const int i = rg.row[pos], my = (int)rg.ptr4[pos + 1] - (int)rg.ptr4[pos];
-        const uint2* e = reinterpret_cast<const uint2*>(rg.ent + (int)rg.ptr4[pos] * 4);
-        const int nch = __builtin_amdgcn_readfirstlane(my);
+        const SpResItem it = sp_res_item<W>(rg, t);
+        const int i = it.i, jj = it.jj;
         const char* col = reinterpret_cast<const char*>(in + jj);
         const double2 self = *reinterpret_cast<const double2*>(in + i * W + jj);
         const double wi = rg.isd[i];
         double a0 = 0.0, a1 = 0.0;
 #pragma unroll 1
-        for (int c = 0; c < nch; ++c) {
-            const uint2 q = c < my ? e[c] : zz;
+        for (int c = 0; c < it.nch; ++c) {
+            const uint2 q = c < it.my ? it.e[c] : zz;
             const unsigned off[4] = {q.x & 0xffffu, q.x >> 16, q.y & 0xffffu, q.y >> 16};  // W * 8 B per row, 8 per isd entry
             double2 y[4];
             double w[4];
@@ -825,29 +825,15 @@ __device__ __forceinline__ void sp_apply_sym_cols(const SpResGraph& rg, int n, c
                                                   double* __restrict__ Out, int c) {
     constexpr int TC = W >= 2 ? 2 : 1, PER_ROW = W / TC;
     const int total = n * PER_ROW;
-    const uint2 zz = make_uint2(rg.zoff | (rg.zoff << 16), rg.zoff | (rg.zoff << 16));
+    const uint2 zz = sp_res_padding(rg);
 #pragma unroll 1
     for (int t = threadIdx.x; t < total; t += SP_THREADS) {
-        const int pos = t / PER_ROW, jj = (t % PER_ROW) * TC;
-        const int i = rg.row[pos], my = (int)rg.ptr4[pos + 1] - (int)rg.ptr4[pos];
-        const uint2* e = reinterpret_cast<const uint2*>(rg.ent + (int)rg.ptr4[pos] * 4);
-        const int nch = __builtin_amdgcn_readfirstlane(my);
-        const char* col = reinterpret_cast<const char*>(xs + jj);
+        const SpResItem it = sp_res_item<W>(rg, t);
+        const int i = it.i, jj = it.jj;
         const double2 self = sp_load_cols<TC>(reinterpret_cast<const char*>(In + (int64_t)i * SP_B + c + jj));
         const double wi = rg.isd[i];
-        double a0 = 0.0, a1 = 0.0;
-        SpChunk cur = sp_gather_chunk<TC>(col, 0 < my ? e[0] : zz);
-        uint2 qn = 1 < my ? e[1] : zz;
-#pragma unroll 1
-        for (int k = 0; k < nch; ++k) {
-            SpChunk nxt = cur;
-            if (k + 1 < nch) nxt = sp_gather_chunk<TC>(col, qn);
-            const uint2 qnn = k + 2 < my ? e[k + 2] : zz;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { a0 += cur.v[u].x; a1 += cur.v[u].y; }
-            cur = nxt;
-            qn = qnn;
-        }
+        double a0, a1;
+        sp_res_sum<TC>(it, zz, reinterpret_cast<const char*>(xs + jj), a0, a1);
         double2 o;
         o.x = self.x - 0.5 * wi * a0;
         o.y = self.y - 0.5 * wi * a1;
@@ -1138,6 +1124,35 @@ __device__ __forceinline__ double sp_init_value(int i, int j) {  // splitmix64 o
     return (double)(long long)(x >> 11) * (2.0 / 9007199254740992.0) - 1.0;
 }
 
+// The start of the scaled Chebyshev recurrence (see the kernel) for W columns of the block from column c: xl = X_0 = D^-1/2 U,
+// yl = X_1 = (D^-1/2 V - c0 X_0) f.  IN_PLACE: the whole block, xl = U and yl = V; else rows of W doubles (the LDS column groups).
+template <int W, bool IN_PLACE>
+__device__ __forceinline__ void sp_chebyshev_start(const double* isd, int n, const double* U, const double* V, int c, double* xl, double* yl,
+                                                   double c0, double f) {
+    for (int t = threadIdx.x; t < n * W; t += SP_THREADS) {
+        const int at = IN_PLACE ? t : (t / W) * SP_B + c + t % W;
+        const double w = isd[t / W], x = U[at] * w;
+        xl[t] = x;
+        yl[t] = (V[at] * w - c0 * x) * f;
+    }
+}
+// Steps 2 .. degree, in the kernel's names (degree, e, tau, c0; sig and matvecs are updated): STEP(LAST) writes X_{i+1} = (L X_i - c0 X_i)
+// f1 - f2 X_{i-1} over X_{i-1} = xl from X_i = yl, COUNT runs, and the two exchange roles - yl ends as the filtered block.  (A macro:
+// as a function taking the step as a callable the same loop moved the register allocation of the whole kernel, which spills at
+// its 256 VGPRs, and cost the resident plans 4 % - profiles/spectral_refactor_ab.log.)
+#define SP_CHEBYSHEV(xl, yl, STEP, COUNT)              \
+    for (int it = 2; it <= degree; ++it) {             \
+        const double sn = 1.0 / (tau - sig);           \
+        const double f1 = 2.0 * sn / e, f2 = sig * sn; \
+        if (it == degree) STEP(true);                  \
+        else STEP(false);                              \
+        COUNT;                                         \
+        double* sw = xl;                               \
+        xl = yl;                                       \
+        yl = sw;                                       \
+        sig = sn;                                      \
+    }
+
 // MODE 0: graph in memory, CG columns of the block staged per step; 1: graph and block in memory, nothing staged (CG = 8: n above
 // 19 199, where one staged column no longer fits); 2: graph and both blocks in the LDS for the whole solve (CG = 8);
 // 3: graph and CG columns of both blocks in the LDS for a whole filter, column group after column group
@@ -1294,56 +1309,31 @@ __global__ __launch_bounds__(SP_THREADS) void spectral_embed_kernel(const int* _
         const double a = fmin(fmax(sh.th[SP_B - 1], 1e-8), 1.9), ub = 2.0;
         const double e = 0.5 * (ub - a), c0 = 0.5 * (ub + a);
         double sig = e / (0.0 - c0);
-        const double tau = 2.0 / sig;
+        const double tau = 2.0 / sig, f = sig / e;
         __syncthreads();  // everyone has read sh.res / sh.th
         SP_T0;
         if (MODE == 2) {
-            double* xl = U;  // X_0 = D^-1/2 U, in place
+            double* xl = U;  // X_0, in place
             double* yl = V;  // X_1
-            const double f = sig / e;
-            for (int t = tid; t < n * SP_B; t += SP_THREADS) {
-                const double w = rg.isd[t / SP_B], x = xl[t] * w;
-                xl[t] = x;
-                yl[t] = (yl[t] * w - c0 * x) * f;
-            }
+            sp_chebyshev_start<SP_B, true>(rg.isd, n, xl, yl, 0, xl, yl, c0, f);
             __syncthreads();
-            for (int it = 2; it <= degree; ++it) {
-                const double sn = 1.0 / (tau - sig);
-                const double f1 = 2.0 * sn / e, f2 = sig * sn;
-                if (it == degree) sp_filter_step_resident<SP_B, true>(rg, n, yl, xl, c0, f1, f2);
-                else sp_filter_step_resident<SP_B, false>(rg, n, yl, xl, c0, f1, f2);
-                ++matvecs;
-                double* sw = xl;
-                xl = yl;
-                yl = sw;
-                sig = sn;
-            }
+#define SP_STEP(LAST) sp_filter_step_resident<SP_B, LAST>(rg, n, yl, xl, c0, f1, f2)
+            SP_CHEBYSHEV(xl, yl, SP_STEP, ++matvecs)
+#undef SP_STEP
             U = yl;  // the filtered block
             V = xl;
         } else if (MODE == 3 && lds_graph) {
-            const double f = sig / e, sig1 = sig;
+            const double sig1 = sig;
 #pragma unroll 1
-            for (int c = 0; c < SP_B; c += CG) {
-                double* xl = xa;  // X_0 = D^-1/2 U, these columns
-                double* yl = xb;  // X_1
-                for (int t = tid; t < n * CG; t += SP_THREADS) {
-                    const int at = (t / CG) * SP_B + c + t % CG;
-                    const double w = rg.isd[t / CG], x = U[at] * w;
-                    xl[t] = x;
-                    yl[t] = (V[at] * w - c0 * x) * f;
-                }
+            for (int c = 0; c < SP_B; c += CG) {  // every step of the filter on one column group after the other
+                double* xl = xa;
+                double* yl = xb;
+                sp_chebyshev_start<CG, false>(rg.isd, n, U, V, c, xl, yl, c0, f);
                 __syncthreads();
                 sig = sig1;
-                for (int it = 2; it <= degree; ++it) {
-                    const double sn = 1.0 / (tau - sig);
-                    const double f1 = 2.0 * sn / e, f2 = sig * sn;
-                    if (it == degree) sp_filter_step_resident<CG, true>(rg, n, yl, xl, c0, f1, f2);
-                    else sp_filter_step_resident<CG, false>(rg, n, yl, xl, c0, f1, f2);
-                    double* sw = xl;
-                    xl = yl;
-                    yl = sw;
-                    sig = sn;
-                }
+#define SP_STEP(LAST) sp_filter_step_resident<CG, LAST>(rg, n, yl, xl, c0, f1, f2)
+                SP_CHEBYSHEV(xl, yl, SP_STEP, (void)0)
+#undef SP_STEP
                 for (int t = tid; t < n * CG; t += SP_THREADS) U[(t / CG) * SP_B + c + t % CG] = yl[t];  // the filtered columns, in place
                 __syncthreads();
             }
@@ -1351,26 +1341,11 @@ __global__ __launch_bounds__(SP_THREADS) void spectral_embed_kernel(const int* _
         } else {
             double* X = U;
             double* Y = V;
-            {
-                const double f = sig / e;
-                for (int t = tid; t < n * SP_B; t += SP_THREADS) {
-                    const double w = g.isd[t / SP_B], x = X[t] * w;
-                    X[t] = x;
-                    Y[t] = (Y[t] * w - c0 * x) * f;
-                }
-            }
+            sp_chebyshev_start<SP_B, true>(g.isd, n, X, Y, 0, X, Y, c0, f);
             __syncthreads();
-            for (int it = 2; it <= degree; ++it) {
-                const double sn = 1.0 / (tau - sig);
-                const double f1 = 2.0 * sn / e, f2 = sig * sn;
-                if (it == degree) sp_filter_step<CG, true, MODE == 1>(g, Y, X, ylds, c0, f1, f2);
-                else sp_filter_step<CG, false, MODE == 1>(g, Y, X, ylds, c0, f1, f2);
-                ++matvecs;
-                double* sw = X;
-                X = Y;
-                Y = sw;
-                sig = sn;
-            }
+#define SP_STEP(LAST) sp_filter_step<CG, LAST, MODE == 1>(g, Y, X, ylds, c0, f1, f2)
+            SP_CHEBYSHEV(X, Y, SP_STEP, ++matvecs)
+#undef SP_STEP
             U = Y;  // the filtered block
             V = X;
         }
@@ -1407,6 +1382,8 @@ __global__ __launch_bounds__(SP_THREADS) void spectral_embed_kernel(const int* _
 #endif
     }
 }
+
+#undef SP_CHEBYSHEV
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // 5. k-means on the first K columns of the embedding, fp64, one workgroup per (cluster size, image): farthest-point initial
@@ -1556,17 +1533,30 @@ static inline size_t sp_gram_bytes(int B, int n, int path) {
     return path == KNN_GRAM ? (size_t)B * n * n * 4 : path == KNN_SLABS ? (size_t)B * (n < SP_SLAB_ROWS ? n : SP_SLAB_ROWS) * n * 4 : 0;
 }
 
+// sm_knn_f32's workspace, the start of the clusterer's: the F16X2 copy, the Gram matrix or one slab of it (the streaming path: nothing), the
+// squared norms
+struct KnnLayout { size_t fs, gram, sq, total; };
+static KnnLayout knn_layout(int B, int n, int D, int path) {
+    KnnLayout l = {};
+    size_t o = 0;
+    l.fs = o;   o += al256((size_t)B * n * D * 4);
+    l.gram = o; o += al256(sp_gram_bytes(B, n, path));
+    l.sq = o;   o += al256((size_t)B * n * 4);
+    l.total = o;
+    return l;
+}
+
 // The features in F16X2 form, the Gram matrix (n <= 8192 only), norms, lists, graph, the two blocks of the eigen-solver, the embedding.
 struct SpLayout { size_t fs, gram, sq, idx, cnt, inptr, inlen, incol, rev, isd, blocks, emb, total; };
 static SpLayout sp_layout(int B, int n, int D, int m, int kw) {
     const bool gram = n <= SP_MAXN;
-    const int path = sp_auto_path(n, D);
+    const KnnLayout k = knn_layout(B, n, D, sp_auto_path(n, D));
     const size_t col = (size_t)B * sp_col_capacity(n, m) * 4;
     SpLayout l = {};
-    size_t o = 0;
-    l.fs = o;     o += al256((size_t)B * n * D * 4);
-    if (path != KNN_STREAM) { l.gram = o; o += al256(sp_gram_bytes(B, n, path)); }  // (the whole matrix, or one slab above SP_MAXN)
-    l.sq = o;     o += al256((size_t)B * n * 4);
+    l.fs = k.fs;
+    l.gram = k.gram;
+    l.sq = k.sq;
+    size_t o = k.total;
     l.idx = o;    o += al256((size_t)B * n * m * 4);
     // the in-degrees / cursors; with the Gram matrix at the size of the n x n bitmap that held the graph before the O(n m) build (the
     // workspace sizes, and the batch caps resting on them, stay as they were)
@@ -1642,7 +1632,17 @@ static const SpEmbedKernel sp_embed_kernels[] = {SP_EMBED(8, 2), SP_EMBED(4, 3),
 
 namespace sm {
 
+// The shapes sm_knn_f32 and the clusterer take: the *_workspace_bytes functions answer 0 to any other, the entry points refuse it
+// part by part under their own names
 static inline bool sp_dim_ok(int D) { return D == SM_EMBED || D == SP_DIM_RESNET; }
+static inline bool sp_points_ok(int B, int n) { return B >= 1 && n >= 2 * SP_B && n <= SP_MAXN_L && n % 4 == 0; }
+static inline bool sp_neighbors_ok(int n_neighbors) { return n_neighbors >= 2 && n_neighbors - 1 <= SP_MAXM; }
+static inline bool sp_shape_ok(int B, int n, int D, int n_neighbors) { return sp_dim_ok(D) && sp_points_ok(B, n) && sp_neighbors_ok(n_neighbors); }
+#define SP_REQUIRE_SHAPE(who, B, n, D, n_neighbors)                                                                             \
+    SM_REQUIRE(sm::sp_dim_ok(D), who ": %d features per point (%d or %d)", D, SM_EMBED, sm::SP_DIM_RESNET);                      \
+    SM_REQUIRE(sm::sp_points_ok(B, n), who ": %d points (16 <= n <= %d, n %% 4 == 0)", n, sm::SP_MAXN_L);                         \
+    SM_REQUIRE(sm::sp_neighbors_ok(n_neighbors), who ": n_neighbors %d (2..%d)", n_neighbors, sm::SP_MAXM + 1)
+static inline int sp_list_length(int n, int n_neighbors) { return n_neighbors - 1 < n - 1 ? n_neighbors - 1 : n - 1; }  // m
 
 // Steps 1-2 for features (B, n, D): the F16X2 copy in `fs`, then the neighbour lists (B, n, m) in `idx`, by one of three paths:
 // KNN_GRAM the whole Gram matrix in `gram` (n <= SP_MAXN), KNN_STREAM the streaming kernels (no n x n array), KNN_SLABS the Gram
@@ -1672,47 +1672,25 @@ static int sp_gram_rows(const float* fs, int B, int n, int D, int row0, int rows
     return sm_gemm_f16x2(&g, 0, stream);
 }
 
+// a k-NN kernel's instantiation by the list length: 16 or 32 entries per lane
+template <class K>
+static K* sp_by_cap(int m, K* cap16, K* cap32) { return m <= 16 ? cap16 : cap32; }
+
 static void sp_launch_select(const float* gram, const float* sq, int B, int n, int m, int* idx, int row0, int rows, hipStream_t st) {
-    if (m <= 16)
-        hipLaunchKernelGGL(sm::knn_select_kernel<16>, dim3((rows + 3) / 4, B), dim3(256), 0, st, gram, sq, n, m, idx, row0, rows);
-    else
-        hipLaunchKernelGGL(sm::knn_select_kernel<32>, dim3((rows + 3) / 4, B), dim3(256), 0, st, gram, sq, n, m, idx, row0, rows);
+    hipLaunchKernelGGL(sp_by_cap(m, sm::knn_select_kernel<16>, sm::knn_select_kernel<32>), dim3((rows + 3) / 4, B), dim3(256), 0, st, gram, sq,
+                       n, m, idx, row0, rows);
 }
 
 static int sp_knn_lists(const float* features, int B, int n, int D, int m, int path, float* fs, float* gram, float* sq, int* idx,
                         void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const double nd = (double)n, Bd = (double)B;
+    // (flops: the three f16 products per multiply-add of every pair count once, as the tap of gemm_f16x2 counts its own)
+    const double flops = 2.0 * Bd * nd * nd * D;
     int rc;
-    if (path == KNN_STREAM) {
-        // (flops: the three f16 products per multiply-add of every pair, as the tap of gemm_f16x2 counts its own)
-        sm::TapGuard tap(stream, "spectral: split_f16x2 + knn_stream", 2.0 * Bd * nd * nd * D, Bd * nd * D * 8);
-        rc = sm_split_f16x2(features, D, fs, D, (int64_t)B * n, D, stream);
-        if (rc) return rc;
-        sp_launch_sqnorm(fs, (int64_t)B * n, D, sq, st);
-        if (D == SM_EMBED) {
-            const dim3 grid((n + sm::KS_ROWS - 1) / sm::KS_ROWS, B);
-            if (m <= 16) hipLaunchKernelGGL(sm::knn_stream_kernel<16>, grid, dim3(256), 0, st, fs, sq, n, m, idx);
-            else hipLaunchKernelGGL(sm::knn_stream_kernel<32>, grid, dim3(256), 0, st, fs, sq, n, m, idx);
-        } else {
-            const dim3 grid((n + sm::KC_ROWS - 1) / sm::KC_ROWS, B);
-            if (m <= 16) hipLaunchKernelGGL((sm::knn_stream_chunked_kernel<SP_DIM_RESNET, 16>), grid, dim3(256), 0, st, fs, sq, n, m, idx);
-            else hipLaunchKernelGGL((sm::knn_stream_chunked_kernel<SP_DIM_RESNET, 32>), grid, dim3(256), 0, st, fs, sq, n, m, idx);
-        }
-    } else if (path == KNN_SLABS) {
-        sm::TapGuard tap(stream, "spectral: split_f16x2 + Gram slabs + knn_select", 2.0 * Bd * nd * nd * D, Bd * (nd * D * 8 + 2.0 * nd * nd * 4));
-        rc = sm_split_f16x2(features, D, fs, D, (int64_t)B * n, D, stream);
-        if (rc) return rc;
-        sp_launch_sqnorm(fs, (int64_t)B * n, D, sq, st);
-        for (int row0 = 0; row0 < n; row0 += SP_SLAB_ROWS) {
-            const int rows = n - row0 < SP_SLAB_ROWS ? n - row0 : SP_SLAB_ROWS;
-            rc = sp_gram_rows(fs, B, n, D, row0, rows, gram, stream);
-            if (rc) return rc;
-            sp_launch_select(gram, sq, B, n, m, idx, row0, rows, st);
-        }
-    } else {
+    if (path == KNN_GRAM) {
         {
-            sm::TapGuard tap(stream, "spectral: split_f16x2 + Gram gemm_f16x2", 2.0 * Bd * nd * nd * D, Bd * (nd * D * 8 + nd * nd * 4));
+            sm::TapGuard tap(stream, "spectral: split_f16x2 + Gram gemm_f16x2", flops, Bd * (nd * D * 8 + nd * nd * 4));
             rc = sm_split_f16x2(features, D, fs, D, (int64_t)B * n, D, stream);
             if (rc) return rc;
             rc = sp_gram_rows(fs, B, n, D, 0, n, gram, stream);
@@ -1721,21 +1699,32 @@ static int sp_knn_lists(const float* features, int B, int n, int D, int m, int p
         sm::TapGuard tap(stream, "spectral: knn_select", 0.0, Bd * (nd * nd * 4 + nd * m * 4));
         hipLaunchKernelGGL(sm::gram_diag_kernel, dim3((unsigned)(((int64_t)B * n + 255) / 256)), dim3(256), 0, st, gram, n, (int64_t)B * n, sq);
         sp_launch_select(gram, sq, B, n, m, idx, 0, n, st);
+        return SM_OK;
+    }
+    // no whole matrix to take the diagonal of: the norms from the features
+    const bool slabs = path == KNN_SLABS;
+    sm::TapGuard tap(stream, slabs ? "spectral: split_f16x2 + Gram slabs + knn_select" : "spectral: split_f16x2 + knn_stream", flops,
+                     slabs ? Bd * (nd * D * 8 + 2.0 * nd * nd * 4) : Bd * nd * D * 8);
+    rc = sm_split_f16x2(features, D, fs, D, (int64_t)B * n, D, stream);
+    if (rc) return rc;
+    sp_launch_sqnorm(fs, (int64_t)B * n, D, sq, st);
+    if (slabs) {
+        for (int row0 = 0; row0 < n; row0 += SP_SLAB_ROWS) {
+            const int rows = n - row0 < SP_SLAB_ROWS ? n - row0 : SP_SLAB_ROWS;
+            rc = sp_gram_rows(fs, B, n, D, row0, rows, gram, stream);
+            if (rc) return rc;
+            sp_launch_select(gram, sq, B, n, m, idx, row0, rows, st);
+        }
+    } else if (D == SM_EMBED) {
+        hipLaunchKernelGGL(sp_by_cap(m, sm::knn_stream_kernel<16>, sm::knn_stream_kernel<32>), dim3((n + sm::KS_ROWS - 1) / sm::KS_ROWS, B),
+                           dim3(256), 0, st, fs, sq, n, m, idx);
+    } else {
+        hipLaunchKernelGGL(sp_by_cap(m, sm::knn_stream_chunked_kernel<SP_DIM_RESNET, 16>, sm::knn_stream_chunked_kernel<SP_DIM_RESNET, 32>),
+                           dim3((n + sm::KC_ROWS - 1) / sm::KC_ROWS, B), dim3(256), 0, st, fs, sq, n, m, idx);
     }
     return SM_OK;
 }
 
-// sm_knn_f32's workspace: the F16X2 copy, the Gram matrix or one slab of it, the squared norms
-struct KnnLayout { size_t fs, gram, sq, total; };
-static KnnLayout knn_layout(int B, int n, int D, int path) {
-    KnnLayout l = {};
-    size_t o = 0;
-    l.fs = o;   o += al256((size_t)B * n * D * 4);
-    l.gram = o; o += al256(sp_gram_bytes(B, n, path));
-    l.sq = o;   o += al256((size_t)B * n * 4);
-    l.total = o;
-    return l;
-}
 // method 0 / 1 / 2 -> the path, -1 = no such method
 static int knn_path(int n, int D, int method) {
     if (method == 0) return sp_auto_path(n, D);
@@ -1746,35 +1735,28 @@ static int knn_path(int n, int D, int method) {
 }  // namespace sm
 
 extern "C" size_t sm_knn_workspace_bytes(int32_t B, int32_t n, int32_t D, int32_t n_neighbors, int32_t method) {
-    if (B < 1 || n < 2 * sm::SP_B || n > sm::SP_MAXN_L || n % 4 != 0 || !sm::sp_dim_ok(D) || n_neighbors < 2 ||
-        n_neighbors - 1 > sm::SP_MAXM || sm::knn_path(n, D, method) < 0)
-        return 0;
+    if (!sm::sp_shape_ok(B, n, D, n_neighbors) || sm::knn_path(n, D, method) < 0) return 0;
     return sm::knn_layout(B, n, D, sm::knn_path(n, D, method)).total;
 }
 
 extern "C" int sm_knn_f32(const float* features, int32_t B, int32_t n, int32_t D, int32_t n_neighbors, int32_t method, int32_t* idx,
                           void* workspace, size_t workspace_bytes, void* stream) {
     SM_REQUIRE(features && idx && workspace, "sm_knn_f32: null pointer");
-    SM_REQUIRE(sm::sp_dim_ok(D), "sm_knn_f32: %d features per point (%d or %d)", D, SM_EMBED, sm::SP_DIM_RESNET);
-    SM_REQUIRE(B >= 1 && n >= 2 * sm::SP_B && n <= sm::SP_MAXN_L && n % 4 == 0, "sm_knn_f32: %d points (16 <= n <= %d, n %% 4 == 0)", n,
-               sm::SP_MAXN_L);
-    SM_REQUIRE(n_neighbors >= 2 && n_neighbors - 1 <= sm::SP_MAXM, "sm_knn_f32: n_neighbors %d (2..%d)", n_neighbors, sm::SP_MAXM + 1);
+    SP_REQUIRE_SHAPE("sm_knn_f32", B, n, D, n_neighbors);
     const int path = sm::knn_path(n, D, method);
     SM_REQUIRE(path >= 0, "sm_knn_f32: method %d (0 = as the clusterer chooses, 1 = Gram matrix, 2 = streaming)", method);
     const sm::KnnLayout l = sm::knn_layout(B, n, D, path);
     SM_REQUIRE(workspace_bytes >= l.total && ((uintptr_t)workspace % 256 == 0), "sm_knn_f32: workspace of %zu bytes, %zu needed (256-B aligned)",
                workspace_bytes, l.total);
     char* ws = (char*)workspace;
-    const int m = n_neighbors - 1 < n - 1 ? n_neighbors - 1 : n - 1;
+    const int m = sm::sp_list_length(n, n_neighbors);
     const int rc = sm::sp_knn_lists(features, B, n, D, m, path, (float*)(ws + l.fs), (float*)(ws + l.gram), (float*)(ws + l.sq), idx, stream);
     return rc ? rc : sm::check_launch("sm_knn_f32");
 }
 
 extern "C" size_t sm_spectral_workspace_bytes_dim(int32_t B, int32_t n, int32_t D, int32_t n_neighbors, int32_t kw) {
-    if (B < 1 || n < 2 * sm::SP_B || n > sm::SP_MAXN_L || !sm::sp_dim_ok(D) || n_neighbors < 2 || n_neighbors - 1 > sm::SP_MAXM || kw < 1 || kw > 6)
-        return 0;
-    const int m = n_neighbors - 1 < n - 1 ? n_neighbors - 1 : n - 1;
-    return sm::sp_layout(B, n, D, m, kw).total;
+    if (!sm::sp_shape_ok(B, n, D, n_neighbors) || kw < 1 || kw > 6) return 0;
+    return sm::sp_layout(B, n, D, sm::sp_list_length(n, n_neighbors), kw).total;
 }
 
 extern "C" size_t sm_spectral_workspace_bytes(int32_t B, int32_t n, int32_t n_neighbors, int32_t kw) {
@@ -1785,11 +1767,7 @@ extern "C" int sm_spectral_cluster_f32(const sm_spectral_args* a, void* stream) 
 
 extern "C" int sm_spectral_cluster_dim_f32(const sm_spectral_args* a, int32_t D, void* stream) {
     SM_REQUIRE(a && a->features && a->labels && a->cluster_sizes && a->workspace, "sm_spectral_cluster_f32: null pointer");
-    SM_REQUIRE(sm::sp_dim_ok(D), "sm_spectral_cluster_f32: %d features per point (%d or %d)", D, SM_EMBED, sm::SP_DIM_RESNET);
-    SM_REQUIRE(a->B >= 1 && a->n >= 2 * sm::SP_B && a->n <= sm::SP_MAXN_L && a->n % 4 == 0,
-               "sm_spectral_cluster_f32: %d points (16 <= n <= %d, n %% 4 == 0)", a->n, sm::SP_MAXN_L);
-    SM_REQUIRE(a->n_neighbors >= 2 && a->n_neighbors - 1 <= sm::SP_MAXM, "sm_spectral_cluster_f32: n_neighbors %d (2..%d)", a->n_neighbors,
-               sm::SP_MAXM + 1);
+    SP_REQUIRE_SHAPE("sm_spectral_cluster_f32", a->B, a->n, D, a->n_neighbors);
     SM_REQUIRE(a->n_sizes >= 1 && a->n_sizes <= 8, "sm_spectral_cluster_f32: 1..8 cluster sizes");
     int kw = 0;
     sm::KeSizes sizes = {};
@@ -1798,7 +1776,7 @@ extern "C" int sm_spectral_cluster_dim_f32(const sm_spectral_args* a, int32_t D,
         sizes.k[i] = a->cluster_sizes[i];
         if (sizes.k[i] > kw) kw = sizes.k[i];
     }
-    const int B = a->B, n = a->n, m = a->n_neighbors - 1 < n - 1 ? a->n_neighbors - 1 : n - 1;
+    const int B = a->B, n = a->n, m = sm::sp_list_length(n, a->n_neighbors);
     const sm::SpLayout l = sm::sp_layout(B, n, D, m, kw);
     SM_REQUIRE(a->workspace_bytes >= l.total && ((uintptr_t)a->workspace % 256 == 0),
                "sm_spectral_cluster_f32: workspace of %zu bytes, %zu needed (256-B aligned)", a->workspace_bytes, l.total);
