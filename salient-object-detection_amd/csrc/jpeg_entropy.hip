@@ -1,6 +1,6 @@
 // Entropy decode of baseline JPEG scans on the device: the Huffman decode that csrc/jpeg_host.h's decode_scan does on a host thread,
 // into the same int16 coefficient layout, with the same verdict.  Input: the records of sm_jpeg_scan_prepare (unstuffed scan bytes, one
-// table entry per restart interval, the Huffman tables in the host decoder's own form, the quantisation tables).
+// table entry per restart interval, the Huffman tables in the host decoder's own form - walked by the host decoder's own lookup, the quantisation tables).
 //
 // The self-synchronising scheme of Weissenberger & Schmidt, "Accelerating JPEG Decompression on GPUs", cut so that all
 // synchronisation stays inside one workgroup: ONE WORKGROUP PER IMAGE (1024 lanes), which walks the image's restart intervals, each
@@ -69,32 +69,12 @@ struct JeBlock {     // per block inside the MCU
     int comp;
 };
 struct JeImage {
-    const smjpeg::DevHuff* huff;  // LDS
+    const smjpeg::HuffTable* huff;  // LDS
     const uint8_t* zigzag;        // LDS
     const JeBlock* blk;           // LDS
     int nb;                       // blocks per MCU
     int mcus_x;
 };
-
-// one symbol's code: its length (0: no code) and value, decode_symbol of jpeg_host.h on 32 peeked bits
-__device__ __forceinline__ int je_symbol(const smjpeg::DevHuff& h, uint32_t bits, int& len) {
-    const uint32_t e = h.fast[bits >> (32 - smjpeg::FAST_BITS)];
-    if (e) {
-        len = (int)(e >> 8);
-        return (int)(e & 255);
-    }
-    for (int l = smjpeg::FAST_BITS + 1; l <= 16; ++l) {
-        const int32_t code = (int32_t)(bits >> (32 - l));
-        if (code <= h.maxcode[l]) {
-            const int i = code + h.valoff[l];
-            if (i < 0 || i > 255) break;
-            len = l;
-            return h.vals[i];
-        }
-    }
-    len = 0;
-    return 0;
-}
 
 // Decodes the symbols that start in [st.p, limit) of the interval that ends at bit seg_end; -> blocks completed.  WRITE: `blk0` is the
 // number inside the interval of the block that is open at entry; coefficients go to coef (the image's), nothing is decoded once
@@ -111,7 +91,7 @@ __device__ int je_run(const JeImage& im, JeReader& rd, JeState& st, uint32_t lim
         const JeBlock& kb = im.blk[st.bi];
         const uint32_t bits = rd.peek32(st.p);
         int len, s, r = 0;
-        const int sym = je_symbol(im.huff[st.z == 0 ? kb.dc : kb.ac], bits, len);
+        const int sym = smjpeg::huff_lookup(im.huff[st.z == 0 ? kb.dc : kb.ac], bits, len);
         bool bad = len == 0, store = false, eob = false;
         if (st.z == 0) {
             s = sym;
@@ -140,7 +120,7 @@ __device__ int je_run(const JeImage& im, JeReader& rd, JeState& st, uint32_t lim
                 int val = 0;
                 if (s) {
                     const int raw = (int)((bits << len) >> (32 - s));
-                    val = raw < (1 << (s - 1)) ? raw - (1 << s) + 1 : raw;
+                    val = smjpeg::extend(raw, s);
                 }
                 if (blk_of != done) {  // the block's place: MCU by MCU in the scan, raster order in the component's plane
                     const int bn = blk0 + done, mcu = mcu0 + bn / im.nb;
@@ -190,7 +170,7 @@ __device__ __forceinline__ int je_scan(int* s_val, int* s_flag, int v, int f, in
 __global__ __launch_bounds__(JE_THREADS) void jpeg_entropy_kernel(const sm_jpeg_scan* __restrict__ descr, const uint8_t* __restrict__ scans,
                                                                   int16_t* __restrict__ coef_out, int32_t* __restrict__ status,
                                                                   int32_t* __restrict__ stats, int subseq_bits, int chunk_subseqs) {
-    __shared__ smjpeg::DevHuff s_huff[JE_MAX_HUFF];
+    __shared__ smjpeg::HuffTable s_huff[JE_MAX_HUFF];
     __shared__ uint32_t s_p[JE_THREADS], s_bz[JE_THREADS];
     __shared__ int s_cnt[JE_THREADS], s_val[JE_THREADS], s_rst[JE_THREADS];
     __shared__ int s_qt[192];
@@ -218,7 +198,7 @@ __global__ __launch_bounds__(JE_THREADS) void jpeg_entropy_kernel(const sm_jpeg_
     {
         const uint32_t* src = reinterpret_cast<const uint32_t*>(rec + sc.huff_off);
         uint32_t* dst = reinterpret_cast<uint32_t*>(s_huff);
-        for (int i = t; i < sc.n_huff * (int)(sizeof(smjpeg::DevHuff) / 4); i += JE_THREADS) dst[i] = src[i];
+        for (int i = t; i < sc.n_huff * (int)(sizeof(smjpeg::HuffTable) / 4); i += JE_THREADS) dst[i] = src[i];
         const uint16_t* q = reinterpret_cast<const uint16_t*>(rec + sc.qt_off);
         if (t < 192) s_qt[t] = q[t];
         if (t < 64) s_zigzag[t] = smjpeg::ZIGZAG[t];

@@ -17,8 +17,18 @@
 #include <string.h>
 
 #include "../../include/selfmask_hip.h"
+#include "host_common.h"
+
+// what the device's entropy decoder (csrc/jpeg_entropy.hip) shares with the host's compiles for both
+#if defined(__HIPCC__)
+#define SMJPEG_HD __host__ __device__ __forceinline__
+#else
+#define SMJPEG_HD inline
+#endif
 
 namespace smjpeg {
+
+using sm::align16;
 
 constexpr int FAST_BITS = 9;
 constexpr int MAX_DIM = 65500;  // libjpeg's JPEG_MAX_DIMENSION
@@ -27,11 +37,16 @@ static const uint8_t ZIGZAG[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 2
                                    41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
                                    30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
-struct Huff {
+// One Huffman table, in the form both decoders walk: prepare_scan sends it to the device whole (SM_JPEG_HUFF_BYTES each)
+struct HuffTable {
     uint16_t fast[1 << FAST_BITS];  // (length << 8) | symbol for codes of at most FAST_BITS bits, 0 = longer / none
-    int32_t maxcode[17];            // largest code of each length, -1 = none
-    int32_t valoff[17];             // index of the first symbol of a length minus its first code
+    int32_t maxcode[17];            // largest code of each length, -1 = none; [0] = -1: lengths start at 1
+    int32_t valoff[17];             // index of the first symbol of a length minus its first code; [0] = 0
     uint8_t vals[256];
+};
+static_assert(sizeof(HuffTable) == SM_JPEG_HUFF_BYTES, "sm_jpeg_scan's table size");
+
+struct Huff : HuffTable {
     bool defined;
 };
 
@@ -56,6 +71,7 @@ inline bool build_huff(Huff& h, const uint8_t* counts, const uint8_t* vals, int 
     memset(h.fast, 0, sizeof(h.fast));
     memset(h.vals, 0, sizeof(h.vals));  // the table travels to the device whole (prepare_scan): no byte of it is left undefined
     memcpy(h.vals, vals, (size_t)nvals);
+    h.maxcode[0] = -1, h.valoff[0] = 0;
     int32_t code = 0;
     int k = 0;
     for (int l = 1; l <= 16; ++l) {
@@ -125,29 +141,55 @@ struct Bits {
     int real_bits_left() const { return cnt - fake; }
 };
 
-// one Huffman symbol, or -1 (no code of up to 16 bits matches)
+// One symbol's code on the next 32 bits of the stream, most significant first: -> the symbol, len = the code's length (0: no code of
+// up to 16 bits matches).  THE table walk: the host decoder and the device's kernel both decode with it.  The codes behind the fast
+// table first, on their own: the host decoder reads the fast table with its own 9-bit peek and comes here for the rest.
+SMJPEG_HD int huff_lookup_long(const HuffTable& h, uint32_t bits, int& len) {
+    for (int l = FAST_BITS + 1; l <= 16; ++l) {
+        const int32_t code = (int32_t)(bits >> (32 - l));
+        if (code <= h.maxcode[l]) {
+            const int i = code + h.valoff[l];
+            if (i < 0 || i > 255) break;
+            len = l;
+            return h.vals[i];
+        }
+    }
+    len = 0;
+    return 0;
+}
+
+SMJPEG_HD int huff_lookup(const HuffTable& h, uint32_t bits, int& len) {
+    const uint32_t e = h.fast[bits >> (32 - FAST_BITS)];
+    if (e) {
+        len = (int)(e >> 8);
+        return (int)(e & 255);
+    }
+    return huff_lookup_long(h, bits, len);
+}
+
+// the value of the s >= 1 bits `raw` that follow a symbol (T.81 F.2.2.1 EXTEND)
+SMJPEG_HD int extend(int raw, int s) { return raw < (1 << (s - 1)) ? raw - (1 << s) + 1 : raw; }
+
+// one Huffman symbol, or -1 (no code).  A fast-table hit returns at once - through huff_lookup the host decoder measured 5 - 9 % slower
+// on one thread - and the long codes go through the shared walk: decode_scan refills below 32 valid bits, so 32 bits, fake zeros
+// included, are there to peek
 inline int decode_symbol(Bits& b, const Huff& h) {
     const uint16_t e = h.fast[b.peek(FAST_BITS)];
     if (e) {
         b.drop(e >> 8);
         return e & 255;
     }
-    for (int l = FAST_BITS + 1; l <= 16; ++l) {
-        const int32_t code = (int32_t)b.peek(l);
-        if (code <= h.maxcode[l]) {
-            const int idx = code + h.valoff[l];
-            if (idx < 0 || idx > 255) return -1;
-            b.drop(l);
-            return h.vals[idx];
-        }
-    }
-    return -1;
+    int len;
+    const int sym = huff_lookup_long(h, b.peek(32), len);
+    if (!len) return -1;
+    b.drop(len);
+    return sym;
 }
 
 inline int receive_extend(Bits& b, int s) {
     const int v = (int)b.peek(s);
     b.drop(s);
-    return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
+    return extend(v, s);
 }
 
 inline int be16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
@@ -381,15 +423,6 @@ inline void write_tables(const Frame& f, uint16_t* qt_out) {
 }
 
 // ---- preparation of a scan for the device's entropy decoder (csrc/jpeg_entropy.hip): no Huffman decoding here ---------------------
-struct DevHuff {  // SM_JPEG_HUFF_BYTES: Huff without its flag
-    uint16_t fast[1 << FAST_BITS];
-    int32_t maxcode[17], valoff[17];
-    uint8_t vals[256];
-};
-static_assert(sizeof(DevHuff) == SM_JPEG_HUFF_BYTES, "sm_jpeg_scan's table size");
-
-inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 // restart intervals the header implies; 0 when the header is not one parse_headers accepted
 inline int64_t scan_segments(const sm_jpeg_info& in) {
     const int64_t n_mcu = (int64_t)in.mcus_x * in.mcus_y;
@@ -398,7 +431,7 @@ inline int64_t scan_segments(const sm_jpeg_info& in) {
 }
 
 // bytes of everything in a record but the scan bytes, for `segs` table entries
-inline size_t record_fixed_bytes(int64_t segs) { return align16((size_t)segs * sizeof(sm_jpeg_segment)) + align16(6 * sizeof(DevHuff)) + 384; }
+inline size_t record_fixed_bytes(int64_t segs) { return align16((size_t)segs * sizeof(sm_jpeg_segment)) + align16(6 * sizeof(HuffTable)) + 384; }
 
 inline size_t scan_bound(const sm_jpeg_info& in, size_t len) {
     int64_t segs = scan_segments(in);
@@ -421,7 +454,7 @@ inline int prepare_scan(const uint8_t* p, size_t n, const Frame& f, uint8_t* rec
         if (slot_dc[f.comp[c].td] < 0) slot_dc[f.comp[c].td] = n_huff++;
         if (slot_ac[f.comp[c].ta] < 0) slot_ac[f.comp[c].ta] = n_huff++;
     }
-    const size_t seg_at = 0, huff_at = align16((size_t)segs * sizeof(sm_jpeg_segment)), qt_at = huff_at + align16((size_t)n_huff * sizeof(DevHuff)),
+    const size_t seg_at = 0, huff_at = align16((size_t)segs * sizeof(sm_jpeg_segment)), qt_at = huff_at + align16((size_t)n_huff * sizeof(HuffTable)),
                  scan_at = qt_at + 384;
     if ((uint64_t)scan_at + align16(raw + 8) >= ((uint64_t)1 << 31)) return SM_JPEG_UNSUPPORTED;  // the record's offsets are 32-bit
     if (cap < scan_at + align16(raw + 8)) return SM_ENOSPACE;
@@ -430,14 +463,8 @@ inline int prepare_scan(const uint8_t* p, size_t n, const Frame& f, uint8_t* rec
         for (int k = 0; k < 2; ++k) {
             const int slot = k ? slot_ac[t] : slot_dc[t];
             if (slot < 0) continue;
-            const Huff& h = k ? f.ac[t] : f.dc[t];
-            DevHuff d;
-            memcpy(d.fast, h.fast, sizeof(d.fast));
-            d.maxcode[0] = -1, d.valoff[0] = 0;  // lengths start at 1
-            memcpy(d.maxcode + 1, h.maxcode + 1, 16 * sizeof(int32_t));
-            memcpy(d.valoff + 1, h.valoff + 1, 16 * sizeof(int32_t));
-            memcpy(d.vals, h.vals, sizeof(d.vals));
-            memcpy(rec + huff_at + (size_t)slot * sizeof(DevHuff), &d, sizeof(d));
+            const HuffTable& h = k ? f.ac[t] : f.dc[t];
+            memcpy(rec + huff_at + (size_t)slot * sizeof(HuffTable), &h, sizeof(HuffTable));
         }
     memset(rec + qt_at, 0, 384);
     for (int c = 0; c < nc; ++c) memcpy(rec + qt_at + 128 * c, f.qt[f.comp[c].tq], 128);

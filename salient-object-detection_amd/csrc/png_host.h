@@ -12,8 +12,11 @@
 #include <string.h>
 
 #include "../../include/selfmask_hip.h"
+#include "host_common.h"
 
 namespace smpng {
+
+using sm::align16;
 
 struct CrcTable {
     uint32_t t[256];
@@ -33,7 +36,6 @@ inline uint32_t crc32(const uint8_t* p, size_t n) {
 }
 
 inline uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
-inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 inline bool is_type(const uint8_t* p, const char* name) { return memcmp(p, name, 4) == 0; }
 
 // signature + IHDR; info is filled as far as the header could be read (0 x 0 when it is no PNG).  true: a supported header

@@ -19,48 +19,24 @@ markers and strip the byte stuffing (``sm_jpeg_scan_prepare``), the staging buff
 - about the size of the files instead of 128 bytes per block - and one launch writes the coefficients on the device, the same
 ones with the same verdict.  What that launch flags (anything irregular INSIDE the entropy-coded data) is known only once the
 batch's status words are back: one small copy and a wait on the batch's stream, then Pillow decodes those files into their slots.
+
+The batch machinery itself - thread-pool passes, staging buffer, copy, verdict loop, fallback copy-in - is ``device_decode.DeviceDecodeBatch``,
+shared with png_decode.py; ``HostBatch`` below holds what is JPEG's own.
 """
 import ctypes
-import io
-import os
 from collections import namedtuple
-from concurrent.futures import ThreadPoolExecutor
-from typing import List, Optional, Sequence, Tuple, Union
+from typing import Optional, Sequence
 
-import numpy as np
 import torch
 
 from . import _native as N
+from .device_decode import MAX_THREADS, DeviceDecodeBatch, Source, _pool, _read, default_threads, packed_layout  # noqa: F401 (re-exported)
 
-MAX_THREADS = 16
 DEVICE_ENTROPY_THREADS = 4  # entropy="device": the threads only read files and strip stuffing; more of them cost more than they do
 MAX_DEVICE_PIXELS = 1 << 24  # larger frames (by their header) go to Pillow, which has its own decompression-bomb check
 PROBE_PREFIX = 1 << 16       # bytes read for a header; the whole file only when the scan header lies further in
 JpegHeader = namedtuple("JpegHeader", "height width components sampling supported coef_bytes")
-Source = Union[str, bytes, os.PathLike]
 ENTROPIES = ("host", "device")
-
-_POOLS = {}
-
-
-def default_threads() -> int:
-    from .decode_pool import default_workers
-    return max(1, min(MAX_THREADS, default_workers()))
-
-
-def _pool(threads: Optional[int]) -> ThreadPoolExecutor:
-    n = default_threads() if threads is None else max(1, min(MAX_THREADS, int(threads)))
-    p = _POOLS.get(n)
-    if p is None:
-        p = _POOLS[n] = ThreadPoolExecutor(max_workers=n, thread_name_prefix="sm_jpeg")
-    return p
-
-
-def _read(source: Source) -> bytes:
-    if isinstance(source, (bytes, bytearray, memoryview)):
-        return bytes(source)
-    with open(source, "rb") as f:
-        return f.read()
 
 
 def _header(data: bytes) -> N.JpegInfo:
@@ -86,189 +62,86 @@ def probe_jpeg(source: Source) -> JpegHeader:
     return JpegHeader(info.height, info.width, info.components, info.sampling, bool(info.supported), int(info.coef_bytes))
 
 
-def packed_layout(shapes) -> Tuple[List[int], int]:
-    """-> (byte offset of every image, bytes in all) of the packed pixel buffer: ``pipeline.pack_images``'s layout"""
-    from .pipeline import packed_pixel_offsets
-    shapes = list(shapes)
-    offs = packed_pixel_offsets(shapes)
-    total = offs[-1] + ((shapes[-1][0] * shapes[-1][1] * 3 + 15) & ~15) if shapes else 0
-    return offs, max(total, 16)
-
-
-def _pillow(source: Source, data: bytes) -> np.ndarray:
-    from .decode_pool import decode_item
-    return decode_item(io.BytesIO(data) if isinstance(source, (bytes, bytearray, memoryview)) else os.fspath(source), None)[0]
-
-
-class HostBatch:
-    """The host half of one batch: per image its header (device path) or its Pillow pixels (fallback), and the page-locked staging
-    buffer [coefficients | quantisation tables | descriptor table] ready for its one copy."""
+class HostBatch(DeviceDecodeBatch):
+    """``DeviceDecodeBatch`` for baseline JPEGs: per image its header (device path) or its Pillow pixels (fallback), and the staging
+    buffer [coefficients | quantisation tables | descriptor table], or with ``entropy="device"`` [scan records | quantisation tables |
+    descriptor table | scan descriptor table]."""
+    NAME, KERNELS, LAUNCH = "decode_jpeg_batch", "IDCT / colour", "sm_jpeg_entropy_decode_batch"
+    UNSUPPORTED, ENTRY = N.JPEG_UNSUPPORTED, N.JpegImage
 
     def __init__(self, sources: Sequence[Source], threads: Optional[int] = None, entropy: str = "host", subseq_bits: int = 0,
                  chunk_subseqs: int = 0):
         """``entropy``: "host" = the threads Huffman-decode; "device" = they only prepare the scans and the GPU decodes them
         (``subseq_bits`` / ``chunk_subseqs``: its parameters, 0 = the defaults; see sm_jpeg_entropy_decode_batch)"""
-        from .pipeline import _POOL
         if entropy not in ENTROPIES:
             raise ValueError(f"entropy={entropy!r}: one of {ENTROPIES}")
-        lib = N.load()
         if entropy == "device" and threads is None:
             threads = min(DEVICE_ENTROPY_THREADS, default_threads())
-        pool = _pool(threads)
-        self.B = B = len(sources)
         self.entropy, self.subseq_bits, self.chunk_subseqs = entropy, int(subseq_bits), int(chunk_subseqs)
-        self.queued = False  # to_device has handed the staging buffer to its copy
-        if B == 0:
-            raise ValueError("an empty batch")
-        self._sources = list(sources) if entropy == "device" else None  # files the device flags are Pillow's, after the batch ran
+        super().__init__(sources, threads)
+        if self.scans is not None:
+            self.blit(self.scans, self.scan_at)
 
-        def first(src):  # file read + header; a file that is not ours is decoded right here
-            data = _read(src)
-            info = _header(data)
-            return (data, info, None) if info.supported else (None, None, _pillow(src, data))
+    def probe(self, data):
+        info = _header(data)
+        return info if info.supported else None
 
-        items = list(pool.map(first, sources))
-        device_entropy = entropy == "device"
-        coef_off, rec_off, rec_cap, o, r = [], [], [], 0, 0
-        for data, info, _ in items:
-            coef_off.append(o)
-            rec_off.append(r)
-            rec_cap.append(0)
-            if info is not None:
-                o += int(info.coef_bytes)  # a multiple of 128
-                if device_entropy:
-                    rec_cap[-1] = int(lib.sm_jpeg_scan_bound(info, len(data)))  # a multiple of 16
-                    r += rec_cap[-1]
+    def capacity(self, data, info):  # the coefficients (a multiple of 128), or the record the device decodes (a multiple of 16)
+        return int(self.lib.sm_jpeg_scan_bound(info, len(data))) if self.entropy == "device" else int(info.coef_bytes)
+
+    def layout(self, infos, rec_bytes):
+        B, device_entropy = self.B, self.entropy == "device"
+        self._coef_off, o = [], 0  # entropy="host": the records ARE the coefficients, o ends as rec_bytes
+        for info in infos:
+            self._coef_off.append(o)
+            o += int(info.coef_bytes) if info is not None else 0
         self.coef_bytes = o
-        # entropy="host": [coefficients | tables | descriptors]; "device": [scan records | tables | descriptors | scan descriptors]
-        qt_at = r if device_entropy else o
-        descr_at = qt_at + B * 384
-        scan_at = descr_at + B * ctypes.sizeof(N.JpegImage)
-        self.staging = _POOL.get(scan_at + (B * ctypes.sizeof(N.JpegScan) if device_entropy else 0), torch.uint8)
-        base = self.staging.data_ptr()
+        self.qt_at = rec_bytes
+        self.descr_at = self.qt_at + B * 384
+        self.scan_at = self.descr_at + B * ctypes.sizeof(N.JpegImage)
+        self.scans, self._scan_of = ((N.JpegScan * B)(), {}) if device_entropy else (None, None)
+        return self.scan_at + (B * ctypes.sizeof(N.JpegScan) if device_entropy else 0)
 
-        scan_of = {}  # entropy="device": the descriptor of every prepared scan
+    def prepare(self, b, data, info, base, at, cap):
+        out = N.JpegInfo()
+        if self.entropy == "device":  # markers and byte stuffing only: the record the device decodes
+            scan = N.JpegScan()
+            if not self.taken(self.lib.sm_jpeg_scan_prepare(data, len(data), base + at, cap, scan, base + self.qt_at + 384 * b, out), "sm_jpeg_scan_prepare"):
+                return None
+            scan.rec_off, scan.coef_off = at, self._coef_off[b]
+            self._scan_of[b] = scan
+        elif not self.taken(self.lib.sm_jpeg_entropy_decode(data, len(data), base + at, cap, base + self.qt_at + 384 * b, out), "sm_jpeg_entropy_decode"):
+            return None  # Huffman decode straight into the staging buffer; anything irregular -> Pillow
+        return out, (out.height, out.width)
 
-        def second(b):  # Huffman decode straight into the staging buffer; anything irregular -> Pillow
-            data, info, rgb = items[b]
-            if info is None:
-                return None, rgb
-            out = N.JpegInfo()
-            if device_entropy:  # markers and byte stuffing only: the record the device decodes
-                scan = N.JpegScan()
-                rc = lib.sm_jpeg_scan_prepare(data, len(data), base + rec_off[b], rec_cap[b], scan, base + qt_at + 384 * b, out)
-                if rc == N.JPEG_UNSUPPORTED:
-                    return None, _pillow(sources[b], data)
-                N.check(rc, "sm_jpeg_scan_prepare")
-                scan.rec_off, scan.coef_off = rec_off[b], coef_off[b]
-                scan_of[b] = scan
-                return out, None
-            rc = lib.sm_jpeg_entropy_decode(data, len(data), base + coef_off[b], int(info.coef_bytes), base + qt_at + 384 * b, out)
-            if rc == N.JPEG_UNSUPPORTED:
-                return None, _pillow(sources[b], data)
-            N.check(rc, "sm_jpeg_entropy_decode")
-            return out, None
+    def fill_table(self, n, b, info):
+        if self.scans is not None:
+            self.scans[n] = self._scan_of[b]
+        e = self.table[n]
+        e.coef_off, e.out_off, e.qt_off, e.H, e.W, e.sampling = self._coef_off[b], self.offsets[b], 192 * b, info.height, info.width, info.sampling
+        nc = info.components
+        for c in range(3):
+            e.blocks_w[c], e.blocks_h[c] = (info.blocks_w[c], info.blocks_h[c]) if c < nc else (0, 0)
 
-        try:
-            done = list(pool.map(second, range(B)))
-        except BaseException:
-            _POOL.release((self.staging,))  # Pillow raised on a damaged file: the batch never reaches a copy
-            raise
-        self.fallback = {b: rgb for b, (info, rgb) in enumerate(done) if info is None}
-        self.shapes = [(int(rgb.shape[0]), int(rgb.shape[1])) if info is None else (int(info.height), int(info.width)) for info, rgb in done]
-        self.offsets, self.out_bytes = packed_layout(self.shapes)
-        self.flags = ["fallback" if info is None else "device" for info, _ in done]
-        table = (N.JpegImage * B)()
-        scans = (N.JpegScan * B)() if device_entropy else None
-        self.device_slots = []  # batch position of every table entry
-        n = 0
-        for b, (info, _) in enumerate(done):
-            if info is None:
-                continue
-            self.device_slots.append(b)
-            if device_entropy:
-                scans[n] = scan_of[b]
-            e = table[n]
-            e.coef_off, e.out_off, e.qt_off, e.H, e.W, e.sampling = coef_off[b], self.offsets[b], 192 * b, info.height, info.width, info.sampling
-            nc = info.components
-            for c in range(3):
-                e.blocks_w[c], e.blocks_h[c] = (info.blocks_w[c], info.blocks_h[c]) if c < nc else (0, 0)
-            n += 1
-        self.n_device, self.table, self.scans = n, table, scans
-        self.qt_at, self.descr_at, self.scan_at = qt_at, descr_at, scan_at
-        self.copy_bytes = self.staging.numel()  # what to_device sends in its one copy
-        if n:
-            self.staging.numpy()[descr_at:descr_at + n * ctypes.sizeof(N.JpegImage)] = np.frombuffer(bytes(table), np.uint8)[:n * ctypes.sizeof(N.JpegImage)]
-            if device_entropy:
-                self.staging.numpy()[scan_at:scan_at + n * ctypes.sizeof(N.JpegScan)] = np.frombuffer(bytes(scans), np.uint8)[:n * ctypes.sizeof(N.JpegScan)]
-
-    def discard(self) -> None:
-        """a batch that will never reach ``to_device``: hand its page-locked buffer back"""
-        from .pipeline import _POOL
-        _POOL.release((self.staging,))
-
-    def to_device(self, device) -> torch.Tensor:
-        """the device half on the current stream -> the packed uint8 pixel buffer"""
-        from .pipeline import _POOL
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError(f"decode_jpeg_batch's IDCT / colour kernels run on a HIP device (got {device}); there is no CPU fallback")
-        stream = torch.cuda.current_stream(device)
-        out = torch.empty(self.out_bytes, dtype=torch.uint8, device=device)
-        used = [self.staging]
-        status_h = None
-        if self.n_device:
-            lib = N.load()
-            dev = self.staging.to(device, non_blocking=True)  # coefficients (or scan records), tables and descriptors: one copy
-            p = dev.data_ptr()
-            coef = p
-            if self.entropy == "device":
-                n = self.n_device
-                coef_t = torch.empty(max(self.coef_bytes, 16), dtype=torch.uint8, device=device)  # the kernel zeroes what it does not write
-                ws_bytes = int(lib.sm_jpeg_entropy_workspace_bytes(ctypes.addressof(self.scans), n, self.subseq_bits, self.chunk_subseqs))
-                if ws_bytes == 0:
-                    raise ValueError("sm_jpeg_entropy_workspace_bytes: " + lib.sm_last_error().decode())
-                self.stats = torch.empty(ws_bytes // 4, dtype=torch.int32, device=device)  # [rounds, chunks] per image
-                status = torch.empty(n, dtype=torch.int32, device=device)
-                N.check(lib.sm_jpeg_entropy_decode_batch(ctypes.addressof(self.scans), p + self.scan_at, n, p, coef_t.data_ptr(), status.data_ptr(),
-                                                         self.stats.data_ptr(), ws_bytes, self.subseq_bits, self.chunk_subseqs,
-                                                         stream.cuda_stream), "sm_jpeg_entropy_decode_batch")
-                coef = coef_t.data_ptr()
-                status_h = _POOL.get(n, torch.int32)
-                status_h.copy_(status, non_blocking=True)
-                verdicts = torch.cuda.Event()
-                verdicts.record(stream)  # the back half below is queued behind it and runs while the host reads the verdicts
-            N.check(lib.sm_jpeg_decode_batch_u8(ctypes.addressof(self.table), p + self.descr_at, self.n_device, coef, p + self.qt_at,
-                                                out.data_ptr(), stream.cuda_stream), "sm_jpeg_decode_batch_u8")
-        if status_h is not None:
-            # what the device flagged is Pillow's: known only now, so the copy of the verdicts is waited for (the back half is queued already)
-            verdicts.synchronize()
-            codes = status_h.tolist()
-            _POOL.release((status_h,))
-            try:
-                for k, rc in enumerate(codes):
-                    if rc == N.JPEG_UNSUPPORTED:
-                        b = self.device_slots[k]
-                        rgb = _pillow(self._sources[b], _read(self._sources[b]))
-                        if (int(rgb.shape[0]), int(rgb.shape[1])) != tuple(self.shapes[b]):
-                            raise ValueError(f"decode_jpeg_batch: file {b}: Pillow decodes {rgb.shape[:2]}, its header says {self.shapes[b]}")
-                        self.fallback[b] = rgb
-                        self.flags[b] = "fallback"
-                    elif rc != 0:
-                        raise RuntimeError(f"sm_jpeg_entropy_decode_batch: file {self.device_slots[k]}: status {rc} (a record the prepare step did not write)")
-            except BaseException:
-                _POOL.release_after(used, stream)  # Pillow raised on a damaged file: the copy has been waited for
-                self.queued = True
-                raise
-        for b, rgb in self.fallback.items():
-            n = rgb.size
-            h = _POOL.get(n, torch.uint8)
-            h.numpy()[:] = rgb.reshape(-1)
-            out[self.offsets[b]:self.offsets[b] + n].copy_(h, non_blocking=True)
-            used.append(h)
-        _POOL.release_after(used, stream)
-        self.queued = True
-        return out
+    def launch(self, p, out, stream):
+        lib, n, coef, verdicts = self.lib, self.n_device, p, None
+        if self.entropy == "device":
+            coef_t = torch.empty(max(self.coef_bytes, 16), dtype=torch.uint8, device=out.device)  # the kernel zeroes what it does not write
+            ws_bytes = int(lib.sm_jpeg_entropy_workspace_bytes(ctypes.addressof(self.scans), n, self.subseq_bits, self.chunk_subseqs))
+            if ws_bytes == 0:
+                raise ValueError("sm_jpeg_entropy_workspace_bytes: " + lib.sm_last_error().decode())
+            self.stats = torch.empty(ws_bytes // 4, dtype=torch.int32, device=out.device)  # [rounds, chunks] per image
+            status = torch.empty(n, dtype=torch.int32, device=out.device)
+            N.check(lib.sm_jpeg_entropy_decode_batch(ctypes.addressof(self.scans), p + self.scan_at, n, p, coef_t.data_ptr(), status.data_ptr(),
+                                                     self.stats.data_ptr(), ws_bytes, self.subseq_bits, self.chunk_subseqs,
+                                                     stream.cuda_stream), "sm_jpeg_entropy_decode_batch")
+            coef = coef_t.data_ptr()
+            event = torch.cuda.Event()
+            verdicts = self.read_back(status), event.synchronize
+            event.record(stream)  # the back half below is queued behind it and runs while the host reads the verdicts
+        N.check(lib.sm_jpeg_decode_batch_u8(ctypes.addressof(self.table), p + self.descr_at, n, coef, p + self.qt_at, out.data_ptr(),
+                                            stream.cuda_stream), "sm_jpeg_decode_batch_u8")
+        return verdicts
 
 
 def decode_jpeg_batch(sources: Sequence[Source], device, threads: Optional[int] = None, return_info: bool = False, entropy: str = "host"):

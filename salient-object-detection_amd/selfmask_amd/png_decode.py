@@ -23,10 +23,11 @@ go to Pillow as well: the device's time per file grows with the length of its da
 Where it pays and where it does not (scripts/png_decode_bench.py, profiles/png_decode_bench.log): one lane walks the symbols of an
 image, so the cost follows the number of deflate symbols.  A ground-truth mask is a few thousand of them; a photo stored as PNG has
 a few hundred thousand, and there the single-lane walk loses to 16 host threads running Pillow.  The path is opt-in everywhere.
+
+The batch machinery itself - thread-pool passes, staging buffer, copy, verdict loop, fallback copy-in - is ``device_decode.DeviceDecodeBatch``,
+shared with jpeg.py (one thread pool for both decoders); ``PngHostBatch`` below holds what is PNG's own.
 """
 import ctypes
-import io
-import os
 from collections import namedtuple
 from typing import Optional, Sequence
 
@@ -34,7 +35,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .jpeg import Source, _pool, _read, packed_layout  # one thread pool for both decoders
+from .device_decode import DeviceDecodeBatch, Source, _openable, _pool, _read, packed_layout, plane_layout  # noqa: F401 (re-exported)
 
 PngHeader = namedtuple("PngHeader", "height width colour_type bit_depth supported inflated_bytes")
 MODES = ("rgb", "l", "gt")
@@ -58,153 +59,65 @@ def probe_png(source: Source) -> PngHeader:
     return PngHeader(info.height, info.width, info.colour_type, info.bit_depth, bool(info.supported), int(info.inflated_bytes))
 
 
-def _pillow(source: Source, data: bytes, mode: str) -> np.ndarray:
-    from .decode_pool import decode_item
-    src = io.BytesIO(data) if isinstance(source, (bytes, bytearray, memoryview)) else os.fspath(source)
-    if mode == "rgb":
-        return decode_item(src, None)[0]
-    from PIL import Image
-    m = np.asarray(Image.open(src).convert("L"))
-    if mode == "gt" and m.max() > 1:  # decode_item's ground-truth half
-        m = m > 0
-    return np.ascontiguousarray(m.astype(np.uint8))
-
-
-def plane_layout(shapes):
-    """-> (byte offset of every image, bytes in all) of a one-byte-per-pixel buffer: planes end to end, each at a multiple of 16"""
-    offs, o = [], 0
-    for h, w in shapes:
-        offs.append(o)
-        o += (h * w + 15) & ~15
-    return offs, max(o, 16)
-
-
-class PngHostBatch:
-    """The host half of one batch: per image its record (device path) or its Pillow pixels (fallback), and the page-locked staging
-    buffer [records | descriptor table] ready for its one copy."""
+class PngHostBatch(DeviceDecodeBatch):
+    """``DeviceDecodeBatch`` for PNG files: per image its record (device path) or its Pillow pixels (fallback), and the staging buffer
+    [records | descriptor table].  ``to_device`` waits on the stream for the verdicts."""
+    NAME, KERNELS, LAUNCH = "decode_png_batch", "inflate / unfilter", "sm_png_decode_batch_u8"
+    UNSUPPORTED, ENTRY = N.PNG_UNSUPPORTED, N.PngStream
+    ZEROED = True
 
     def __init__(self, sources: Sequence[Source], threads: Optional[int] = None, mode: str = "rgb"):
-        from .pipeline import _POOL
         if mode not in MODES:
             raise ValueError(f"mode={mode!r}: one of {MODES}")
-        lib = N.load()
-        pool = _pool(threads)
-        self.B = B = len(sources)
         self.mode = mode
-        self.queued = False  # to_device has handed the staging buffer to its copy
-        if B == 0:
-            raise ValueError("an empty batch")
-        self._sources = list(sources)  # files the device flags are Pillow's, after the batch ran
+        super().__init__(sources, threads)
 
-        def first(src):  # file read + header; a file that is not ours is decoded right here
-            data = _read(src)
-            info = N.PngInfo()
-            N.check(lib.sm_png_probe(data, len(data), info), "sm_png_probe")
-            ours = info.supported and len(data) <= MAX_DEVICE_FILE_BYTES and info.height * info.width <= MAX_DEVICE_PIXELS
-            return (data, info, None) if ours else (None, None, _pillow(src, data, mode))
+    def probe(self, data):
+        info = N.PngInfo()
+        N.check(self.lib.sm_png_probe(data, len(data), info), "sm_png_probe")
+        ours = info.supported and len(data) <= MAX_DEVICE_FILE_BYTES and info.height * info.width <= MAX_DEVICE_PIXELS
+        return info if ours else None
 
-        items = list(pool.map(first, sources))
-        rec_off, rec_cap, r = [], [], 0
-        for data, info, _ in items:
-            rec_off.append(r)
-            rec_cap.append(int(lib.sm_png_stream_bound(info, len(data))) if info is not None else 0)  # a multiple of 16
-            r += rec_cap[-1]
-        descr_at = r
-        self.staging = _POOL.get(descr_at + B * ctypes.sizeof(N.PngStream), torch.uint8)
-        base = self.staging.data_ptr()
+    def pillow(self, source, data):
+        if self.mode == "rgb":
+            return super().pillow(source, data)
+        from PIL import Image
+        m = np.asarray(Image.open(_openable(source, data)).convert("L"))
+        if self.mode == "gt" and m.max() > 1:  # decode_item's ground-truth half
+            m = m > 0
+        return np.ascontiguousarray(m.astype(np.uint8))
 
-        def second(b):  # chunk walk + concatenation straight into the staging buffer; anything irregular -> Pillow
-            data, info, px = items[b]
-            if info is None:
-                return None, px
-            st, out = N.PngStream(), N.PngInfo()
-            rc = lib.sm_png_stream_prepare(data, len(data), base + rec_off[b], rec_cap[b], st, out)
-            if rc == N.PNG_UNSUPPORTED:
-                return None, _pillow(sources[b], data, mode)
-            N.check(rc, "sm_png_stream_prepare")
-            return st, None
+    def capacity(self, data, info):
+        return int(self.lib.sm_png_stream_bound(info, len(data)))  # a multiple of 16
 
-        try:
-            done = list(pool.map(second, range(B)))
-        except BaseException:
-            _POOL.release((self.staging,))  # Pillow raised on a damaged file: the batch never reaches a copy
-            raise
-        self.fallback = {b: px for b, (st, px) in enumerate(done) if st is None}
-        self.shapes = [(int(px.shape[0]), int(px.shape[1])) if st is None else (int(st.H), int(st.W)) for st, px in done]
-        self.offsets, self.out_bytes = packed_layout(self.shapes) if mode == "rgb" else plane_layout(self.shapes)
-        self.flags = ["fallback" if st is None else "device" for st, _ in done]
-        table = (N.PngStream * B)()
-        self.device_slots = []  # batch position of every table entry
-        n, ws = 0, 0
-        for b, (st, _) in enumerate(done):
-            if st is None:
-                continue
-            self.device_slots.append(b)
-            st.rec_off, st.ws_off, st.out_off = rec_off[b], ws, self.offsets[b]
-            ws += (int(st.inflated_bytes) + 15) & ~15
-            table[n] = st
-            n += 1
-        self.n_device, self.table, self.descr_at, self.ws_bytes = n, table, descr_at, ws
-        self.copy_bytes = self.staging.numel()  # what to_device sends in its one copy
-        if n:
-            self.staging.numpy()[descr_at:descr_at + n * ctypes.sizeof(N.PngStream)] = np.frombuffer(bytes(table), np.uint8)[:n * ctypes.sizeof(N.PngStream)]
+    def layout(self, infos, rec_bytes):
+        self.descr_at, self.ws_bytes = rec_bytes, 0
+        return rec_bytes + self.B * ctypes.sizeof(N.PngStream)
 
-    def discard(self) -> None:
-        """a batch that will never reach ``to_device``: hand its page-locked buffer back"""
-        from .pipeline import _POOL
-        _POOL.release((self.staging,))
+    def prepare(self, b, data, info, base, at, cap):  # chunk walk + concatenation straight into the staging buffer
+        st, out = N.PngStream(), N.PngInfo()
+        if not self.taken(self.lib.sm_png_stream_prepare(data, len(data), base + at, cap, st, out), "sm_png_stream_prepare"):
+            return None
+        return st, (st.H, st.W)
 
-    def to_device(self, device) -> torch.Tensor:
-        """the device half on the current stream -> the uint8 pixel buffer: one copy, the two launches, the status read-back and a wait
-        on the stream, Pillow for what the device flagged"""
-        from .pipeline import _POOL
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError(f"decode_png_batch's inflate / unfilter kernels run on a HIP device (got {device}); there is no CPU fallback")
-        stream = torch.cuda.current_stream(device)
-        out = torch.zeros(self.out_bytes, dtype=torch.uint8, device=device)  # the padding between the slots is part of what is returned
-        used = [self.staging]
-        if self.n_device:
-            lib = N.load()
-            n = self.n_device
-            dev = self.staging.to(device, non_blocking=True)  # records and descriptors: one copy
-            p = dev.data_ptr()
-            ws_bytes = int(lib.sm_png_decode_workspace_bytes(ctypes.addressof(self.table), n))
-            if ws_bytes == 0:
-                raise ValueError("sm_png_decode_workspace_bytes: " + lib.sm_last_error().decode())
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
-            status = torch.empty(n, dtype=torch.int32, device=device)
-            N.check(lib.sm_png_decode_batch_u8(ctypes.addressof(self.table), p + self.descr_at, n, p, ws.data_ptr(), ws_bytes, out.data_ptr(),
-                                               status.data_ptr(), MODES.index(self.mode), stream.cuda_stream), "sm_png_decode_batch_u8")
-            status_h = _POOL.get(n, torch.int32)
-            status_h.copy_(status, non_blocking=True)
-            stream.synchronize()  # what the device flagged is Pillow's: known only now
-            codes = status_h.tolist()
-            _POOL.release((status_h,))
-            try:
-                for k, rc in enumerate(codes):
-                    if rc == N.PNG_UNSUPPORTED:
-                        b = self.device_slots[k]
-                        px = _pillow(self._sources[b], _read(self._sources[b]), self.mode)
-                        if (int(px.shape[0]), int(px.shape[1])) != tuple(self.shapes[b]):
-                            raise ValueError(f"decode_png_batch: file {b}: Pillow decodes {px.shape[:2]}, its header says {self.shapes[b]}")
-                        self.fallback[b] = px
-                        self.flags[b] = "fallback"
-                    elif rc != 0:
-                        raise RuntimeError(f"sm_png_decode_batch_u8: file {self.device_slots[k]}: status {rc} (a record the prepare step did not write)")
-            except BaseException:
-                _POOL.release_after(used, stream)  # Pillow raised on a damaged file: the copy has been waited for
-                self.queued = True
-                raise
-        for b, px in self.fallback.items():
-            n = px.size
-            h = _POOL.get(n, torch.uint8)
-            h.numpy()[:] = px.reshape(-1)
-            out[self.offsets[b]:self.offsets[b] + n].copy_(h, non_blocking=True)
-            used.append(h)
-        _POOL.release_after(used, stream)
-        self.queued = True
-        return out
+    def out_layout(self, shapes):
+        return packed_layout(shapes) if self.mode == "rgb" else plane_layout(shapes)
+
+    def fill_table(self, n, b, st):
+        st.rec_off, st.ws_off, st.out_off = self._rec_off[b], self.ws_bytes, self.offsets[b]
+        self.ws_bytes += (int(st.inflated_bytes) + 15) & ~15
+        self.table[n] = st
+
+    def launch(self, p, out, stream):
+        lib, n = self.lib, self.n_device
+        ws_bytes = int(lib.sm_png_decode_workspace_bytes(ctypes.addressof(self.table), n))
+        if ws_bytes == 0:
+            raise ValueError("sm_png_decode_workspace_bytes: " + lib.sm_last_error().decode())
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=out.device)
+        status = torch.empty(n, dtype=torch.int32, device=out.device)
+        N.check(lib.sm_png_decode_batch_u8(ctypes.addressof(self.table), p + self.descr_at, n, p, ws.data_ptr(), ws_bytes, out.data_ptr(),
+                                           status.data_ptr(), MODES.index(self.mode), stream.cuda_stream), "sm_png_decode_batch_u8")
+        return self.read_back(status), stream.synchronize
 
 
 def decode_png_batch(sources: Sequence[Source], device, mode: str = "rgb", threads: Optional[int] = None, return_info: bool = False):

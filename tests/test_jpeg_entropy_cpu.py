@@ -197,3 +197,56 @@ def test_entropy_option_is_validated():
     assert build_parser().parse_args(base + ["--decode", "device", "--entropy", "device"]).entropy == "device"
     with pytest.raises(SystemExit):
         build_parser().parse_args(base + ["--entropy", "gpu"])
+
+
+def _dht_tables(data):
+    """{(class, id): (counts[16], symbols)} from the file's DHT segments, read here byte by byte"""
+    tables, pos = {}, 2
+    while data[pos + 1] != 0xDA:
+        length = (data[pos + 2] << 8) | data[pos + 3]
+        if data[pos + 1] == 0xC4:
+            o, end = pos + 4, pos + 2 + length
+            while o < end:
+                counts = list(data[o + 1:o + 17])
+                tables[(data[o] >> 4, data[o] & 15)] = (counts, list(data[o + 17:o + 17 + sum(counts)]))
+                o += 17 + sum(counts)
+        pos += 2 + length
+    return tables
+
+
+def test_the_one_symbol_lookup_equals_a_canonical_code_decode_on_every_16_bit_prefix():
+    """The table walk that the host decoder and the kernel share (jpeg_host.h's huff_lookup, restated as ``_Huff.symbol`` on the very
+    table bytes the library builds and sends) against a decode that knows no tables: the canonical code of T.81 Annex C laid out over
+    all 65 536 sixteen-bit prefixes, straight from the file's DHT segments.  Every table of a grey, a 4:2:0 and a restart-interval file."""
+    cases = dict(CASES)
+    long_codes = no_code = tables = 0
+    for cid in ("37x53-sL-q85-optimize", "37x53-s2-q85-optimize", "37x53-s0-q85-restart"):
+        data = cases[cid]
+        rc, info, scan, rec, _ = E.prepare(data)
+        assert rc == 0 and (info.components, info.sampling, info.restart_interval > 0) == {"L": (1, N.JPEG_GRAY, False), "2": (3, N.JPEG_420, False),
+                                                                                         "0": (3, N.JPEG_444, True)}[cid[7]], cid
+        dht = _dht_tables(data)
+        slots = {}
+        for c in range(info.components):
+            slots[scan.dc[c]], slots[scan.ac[c]] = (0, scan.td[c]), (1, scan.ta[c])
+        assert sorted(slots) == list(range(scan.n_huff)), cid
+        for slot, key in slots.items():
+            counts, symbols = dht[key]
+            want_len, want_sym = np.zeros(1 << 16, np.int64), np.zeros(1 << 16, np.int64)
+            code = k = 0
+            for length in range(1, 17):  # C.2: codes of a length are consecutive, the first one follows the last shorter one, doubled
+                for _ in range(counts[length - 1]):
+                    a = code << (16 - length)
+                    assert not want_len[a:a + (1 << (16 - length))].any(), "a prefix code"
+                    want_len[a:a + (1 << (16 - length))], want_sym[a:a + (1 << (16 - length))] = length, symbols[k]
+                    code, k = code + 1, k + 1
+                code <<= 1
+            huff = E._Huff(rec[scan.huff_off + N.JPEG_HUFF_BYTES * slot:scan.huff_off + N.JPEG_HUFF_BYTES * (slot + 1)])
+            got = np.array([huff.symbol(p << 16) for p in range(1 << 16)], np.int64)
+            assert np.array_equal(got[:, 0], want_len) and np.array_equal(got[:, 1], want_sym), (cid, key)
+            # the 16 bits behind the prefix never matter
+            assert all(huff.symbol((p << 16) | 0xFFFF) == tuple(got[p]) for p in range(0, 1 << 16, 257)), (cid, key)
+            long_codes += int((want_len > 9).any())
+            no_code += int((want_len == 0).any())
+            tables += 1
+    assert tables >= 2 + 2 + 2 and long_codes and no_code, "codes behind the fast table and prefixes without a code must both occur"
