@@ -578,7 +578,7 @@ int sm_mask_objects(const sm_objects_args* args, const sm_bilateral_image* image
  *   m8    = (uint8)(m * 255.0f), truncating, NaN -> 0 (masks hold values in [0, 1]: what the serving selection leaves)
  *   pass  = clip8((sum m8 * tap + 2^21) >> 22): horizontal mw -> W_b into a uint8 intermediate, then vertical mh -> H_b on it; a pass
  *           whose lengths agree is skipped (ks = 0), as Pillow skips it.  Taps: Pillow's precompute_coeffs + normalize_coeffs_8bpc
- *           for the Lanczos-3 filter, computed by the host (selfmask_amd/present.py: pil_lanczos_coeffs)
+ *           for the Lanczos-3 filter, computed by the host (selfmask_amd/resample.py: pil_coeffs(..., "lanczos"), laid out by CoefTable)
  *   heat  = per channel of (R, G, B, 255) of the upload against lut_rgba[mask byte]: blend = (uint8)(o + alpha * (l - o)), then
  *           t = d + brightness * (blend - d) with d = 0 (R, G, B) / the blend's alpha (A), t <= 0 -> 0, t >= 255 -> 255, else
  *           truncated; every fp32 multiply and add rounded on its own, as Pillow's Blend.c

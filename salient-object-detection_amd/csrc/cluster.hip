@@ -6,41 +6,12 @@
 // deterministic farthest-point initialisation (the reference's cluster_type="kmeans" option in spirit; its default "spectral"
 // - faiss k-NN affinity + eigen-decomposition - stays absent), restated in oracle/cluster_oracle.py and compared with
 // scikit-learn from the same initial centres.  The two interpolations are PyTorch's, pinned against F.interpolate.
-#include "common.h"
-
-// torch-CPU arithmetic reproduced as written: no a*b+c -> fma contraction (with it, lambda = scale * o - floor(.) is formed
-// from the UNROUNDED product and the interpolation weights move by an ulp of the source coordinate: 3e-6 on the features)
-#pragma clang fp contract(off)
+// upsample_aligned_kernel; the header switches a*b+c -> fma contraction off for this file: torch-CPU arithmetic is reproduced as
+// written (with contraction, lambda = scale * o - floor(.) is formed from the UNROUNDED product and the interpolation weights move
+// by an ulp of the source coordinate: 3e-6 on the features)
+#include "upsample.h"
 
 namespace sm {
-
-// bilinear, align_corners=True, channels-last: up[(oy, ox)][c] - source coordinate o * (in - 1) / (out - 1) (ATen
-// area_pixel_compute_scale / _source_index with align_corners: the scale is formed in fp32)
-__global__ __launch_bounds__(256) void upsample_ac_kernel(const float* __restrict__ tok, int64_t strideb, float* __restrict__ up, int gh,
-                                                         int gw, int sf, int64_t total4) {
-    const int oh = sf * gh, ow = sf * gw, C4 = SM_EMBED / 4;
-    const float sy = oh > 1 ? (float)(gh - 1) / (float)(oh - 1) : 0.f, sx = ow > 1 ? (float)(gw - 1) / (float)(ow - 1) : 0.f;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total4; t += (int64_t)gridDim.x * 256) {
-        const int c = (int)(t % C4) * 4;
-        const int64_t px = t / C4;
-        const int ox = (int)(px % ow), oy = (int)((px / ow) % oh), b = (int)(px / ((int64_t)ow * oh));
-        const float syf = sy * oy, sxf = sx * ox;
-        const int y0 = (int)syf, x0 = (int)sxf;
-        const int y1 = y0 + (y0 < gh - 1 ? 1 : 0), x1 = x0 + (x0 < gw - 1 ? 1 : 0);
-        const float ly1 = syf - y0, ly0 = 1.f - ly1, lx1 = sxf - x0, lx0 = 1.f - lx1;
-        const float* base = tok + (int64_t)b * strideb + c;
-        const float4 p00 = *reinterpret_cast<const float4*>(base + ((int64_t)y0 * gw + x0) * SM_EMBED);
-        const float4 p01 = *reinterpret_cast<const float4*>(base + ((int64_t)y0 * gw + x1) * SM_EMBED);
-        const float4 p10 = *reinterpret_cast<const float4*>(base + ((int64_t)y1 * gw + x0) * SM_EMBED);
-        const float4 p11 = *reinterpret_cast<const float4*>(base + ((int64_t)y1 * gw + x1) * SM_EMBED);
-        float4 o;
-        o.x = ly0 * (lx0 * p00.x + lx1 * p01.x) + ly1 * (lx0 * p10.x + lx1 * p11.x);
-        o.y = ly0 * (lx0 * p00.y + lx1 * p01.y) + ly1 * (lx0 * p10.y + lx1 * p11.y);
-        o.z = ly0 * (lx0 * p00.z + lx1 * p01.z) + ly1 * (lx0 * p10.z + lx1 * p11.z);
-        o.w = ly0 * (lx0 * p00.w + lx1 * p01.w) + ly1 * (lx0 * p10.w + lx1 * p11.w);
-        *reinterpret_cast<float4*>(up + px * SM_EMBED + c) = o;
-    }
-}
 
 constexpr int KM_MAXK = 8, KM_THREADS = 1024, KM_WAVES = KM_THREADS / 64;
 
@@ -216,7 +187,8 @@ extern "C" int sm_upsample_tokens_aligned_f32(const float* tok, int64_t strideb,
     const int64_t total4 = (int64_t)B * scale * scale * gh * gw * (SM_EMBED / 4);
     int64_t grid = (total4 + 255) / 256;
     if (grid > 4096) grid = 4096;
-    hipLaunchKernelGGL(sm::upsample_ac_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, tok, strideb, up, gh, gw, scale, total4);
+    hipLaunchKernelGGL(sm::upsample_aligned_kernel<SM_EMBED>, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, tok, strideb, up, gh, gw, SM_EMBED,
+                       scale, total4);
     return sm::check_launch("sm_upsample_tokens_aligned_f32");
 }
 

@@ -5,10 +5,8 @@
 // weight and a bias (resnet.py of the package, fp64 on the host).  What is hand-written here are the streaming kernels between the
 // GEMMs - 16-byte accesses per lane, no LDS: tap gather, stem gather, max-pool, ReLU + split, a channel-count-general bilinear
 // up-sampler - and the launch sequence.
-#include "common.h"
-
-// the up-sampler reproduces torch-CPU arithmetic as written (see cluster.hip): no a*b+c -> fma contraction
-#pragma clang fp contract(off)
+// upsample_aligned_kernel: torch-CPU arithmetic as written (the header switches a*b+c -> fma contraction off for this file)
+#include "upsample.h"
 
 #define TRY_RC(x)             \
     do {                      \
@@ -135,35 +133,6 @@ __global__ __launch_bounds__(256) void relu_split_kernel(const float* src, float
             *reinterpret_cast<f16x8*>(q) = hi;
             *reinterpret_cast<f16x8*>(q + 16) = lo;
         }
-    }
-}
-
-// ---- bilinear, align_corners=True, channels last, any C % 4 == 0 (upsample_ac_kernel of cluster.hip with the channel count a
-// parameter): source coordinate o * (in - 1) / (out - 1), the scale formed in fp32 as ATen does
-__global__ __launch_bounds__(256) void upsample_nhwc_kernel(const float* __restrict__ in, float* __restrict__ up, int gh, int gw, int C, int sf,
-                                                            int64_t total4) {
-    const int oh = sf * gh, ow = sf * gw, C4 = C / 4;
-    const float sy = oh > 1 ? (float)(gh - 1) / (float)(oh - 1) : 0.f, sx = ow > 1 ? (float)(gw - 1) / (float)(ow - 1) : 0.f;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total4; t += (int64_t)gridDim.x * 256) {
-        const int c = (int)(t % C4) * 4;
-        const int64_t px = t / C4;
-        const int ox = (int)(px % ow), oy = (int)((px / ow) % oh);
-        const int64_t b = px / ((int64_t)ow * oh);
-        const float syf = sy * oy, sxf = sx * ox;
-        const int y0 = (int)syf, x0 = (int)sxf;
-        const int y1 = y0 + (y0 < gh - 1 ? 1 : 0), x1 = x0 + (x0 < gw - 1 ? 1 : 0);
-        const float ly1 = syf - y0, ly0 = 1.f - ly1, lx1 = sxf - x0, lx0 = 1.f - lx1;
-        const float* base = in + b * gh * gw * C + c;
-        const float4 p00 = *reinterpret_cast<const float4*>(base + ((int64_t)y0 * gw + x0) * C);
-        const float4 p01 = *reinterpret_cast<const float4*>(base + ((int64_t)y0 * gw + x1) * C);
-        const float4 p10 = *reinterpret_cast<const float4*>(base + ((int64_t)y1 * gw + x0) * C);
-        const float4 p11 = *reinterpret_cast<const float4*>(base + ((int64_t)y1 * gw + x1) * C);
-        float4 o;
-        o.x = ly0 * (lx0 * p00.x + lx1 * p01.x) + ly1 * (lx0 * p10.x + lx1 * p11.x);
-        o.y = ly0 * (lx0 * p00.y + lx1 * p01.y) + ly1 * (lx0 * p10.y + lx1 * p11.y);
-        o.z = ly0 * (lx0 * p00.z + lx1 * p01.z) + ly1 * (lx0 * p10.z + lx1 * p11.z);
-        o.w = ly0 * (lx0 * p00.w + lx1 * p01.w) + ly1 * (lx0 * p10.w + lx1 * p11.w);
-        *reinterpret_cast<float4*>(up + px * C + c) = o;
     }
 }
 
@@ -301,8 +270,9 @@ extern "C" int sm_upsample_nhwc_aligned_f32(const float* in, float* up, int32_t 
                    ((uintptr_t)up % 16) == 0,
                "sm_upsample_nhwc_aligned_f32: bad arguments (C %% 4 == 0, scale 1..16, 16-B aligned pointers)");
     const int64_t total4 = (int64_t)B * scale * scale * gh * gw * (C / 4);
-    sm::TapGuard tap(stream, "upsample_nhwc_kernel", 0.0, 16.0 * total4 * 5);
-    hipLaunchKernelGGL(sm::upsample_nhwc_kernel, dim3(sm::grid_for(total4)), dim3(256), 0, (hipStream_t)stream, in, up, gh, gw, C, scale, total4);
+    sm::TapGuard tap(stream, "upsample_aligned_kernel", 0.0, 16.0 * total4 * 5);
+    hipLaunchKernelGGL(sm::upsample_aligned_kernel<0>, dim3(sm::grid_for(total4)), dim3(256), 0, (hipStream_t)stream, in, (int64_t)gh * gw * C, up, gh,
+                       gw, C, scale, total4);
     return sm::check_launch("sm_upsample_nhwc_aligned_f32");
 }
 

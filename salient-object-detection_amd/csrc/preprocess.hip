@@ -8,19 +8,13 @@
 // widened by the down-scale factor (anti-aliasing), coefficients in 22-bit fixed point, horizontal pass first, the
 // intermediate image rounded and clipped to uint8, then the vertical pass.  The coefficient tables depend only on
 // (input size, output size); the host computes them in double exactly as Pillow's precompute_coeffs /
-// normalize_coeffs_8bpc do (pipeline.pil_resize_coeffs) and the kernels apply them in int32 - bit-exact with PIL.
+// normalize_coeffs_8bpc do (resample.pil_coeffs, bound as pipeline.pil_resize_coeffs) and the kernels apply them in int32
+// through resample.h - bit-exact with PIL.
 // ToTensor + Normalize of a uint8 value has 256 outcomes per channel: a 768-entry fp32 table computed by the host with
 // the reference's own fp32 expressions ((v / 255 - mean) / std), looked up here - bit-exact by construction.
-#include "common.h"
+#include "resample.h"
 
 namespace sm {
-
-constexpr int PP_PRECISION_BITS = 32 - 8 - 2;  // Pillow: PRECISION_BITS
-
-__device__ __forceinline__ unsigned char pp_clip8(int v) {
-    v >>= PP_PRECISION_BITS;  // arithmetic shift, as the C code's table index
-    return (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v));
-}
 
 // horizontal pass: tmp[b][y][xx][c] = clip8(2^21 + sum_x in[b][y][xmin + x][c] * k[xx][x])
 __global__ __launch_bounds__(256) void pp_resize_h_kernel(const unsigned char* __restrict__ in, const sm_pre_image* __restrict__ imgs,
@@ -32,17 +26,15 @@ __global__ __launch_bounds__(256) void pp_resize_h_kernel(const unsigned char* _
     if (y >= im.H) return;
     const int xx = blockIdx.x * 256 + threadIdx.x;
     if (xx >= S) return;
-    const int* cb = coef + im.coef_x;           // [S][2] bounds then [S][ksx] coefficients
-    const int xmin = cb[2 * xx], xmax = cb[2 * xx + 1];
-    const int* k = cb + 2 * S + xx * im.ksx;
-    const unsigned char* row = in + im.off + ((int64_t)y * im.W + xmin) * 3;
-    int s0 = 1 << (PP_PRECISION_BITS - 1), s1 = s0, s2 = s0;
-    for (int x = 0; x < xmax; ++x) {
-        const int w = k[x];
+    const RsTaps t = rs_taps(coef, im.coef_x, im.ksx, S, im.W, xx);  // (the host always sends a table: ksx > 0)
+    const unsigned char* row = in + im.off + ((int64_t)y * im.W + t.first) * 3;
+    int s0 = RS_HALF, s1 = s0, s2 = s0;
+    for (int x = 0; x < t.n; ++x) {
+        const int w = t.k[x];
         s0 += row[3 * x] * w; s1 += row[3 * x + 1] * w; s2 += row[3 * x + 2] * w;
     }
     unsigned char* o = tmp + b * tmp_stride + ((int64_t)y * S + xx) * 3;
-    o[0] = pp_clip8(s0); o[1] = pp_clip8(s1); o[2] = pp_clip8(s2);
+    o[0] = (unsigned char)rs_clip8_plain(s0); o[1] = (unsigned char)rs_clip8_plain(s1); o[2] = (unsigned char)rs_clip8_plain(s2);
 }
 
 // vertical pass + ToTensor + Normalize: out[b][c][yy][xx] = lut[c][clip8(2^21 + sum_y tmp[b][ymin + y][xx][c] * k[yy][y])]
@@ -57,25 +49,23 @@ __global__ __launch_bounds__(256) void pp_resize_v_norm_kernel(const unsigned ch
     const int xx = blockIdx.x * 256 + threadIdx.x;
     if (xx >= S) return;
     const sm_pre_image im = imgs[b];
-    const int* cb = coef + im.coef_y;
-    const int ymin = cb[2 * yy], ymax = cb[2 * yy + 1];
-    const int* k = cb + 2 * S + yy * im.ksy;
-    const unsigned char* col = tmp + b * tmp_stride + ((int64_t)ymin * S + xx) * 3;
-    int s0 = 1 << (PP_PRECISION_BITS - 1), s1 = s0, s2 = s0;
-    for (int y = 0; y < ymax; ++y) {
-        const int w = k[y];
+    const RsTaps t = rs_taps(coef, im.coef_y, im.ksy, S, im.H, yy);
+    const unsigned char* col = tmp + b * tmp_stride + ((int64_t)t.first * S + xx) * 3;
+    int s0 = RS_HALF, s1 = s0, s2 = s0;
+    for (int y = 0; y < t.n; ++y) {
+        const int w = t.k[y];
         const unsigned char* p = col + (int64_t)y * S * 3;
         s0 += p[0] * w; s1 += p[1] * w; s2 += p[2] * w;
     }
     const int64_t plane = (int64_t)S * S;
     float* o = out + (int64_t)b * 3 * plane + (int64_t)yy * S + xx;
-    const unsigned char r0 = pp_clip8(s0), r1 = pp_clip8(s1), r2 = pp_clip8(s2);
+    const int r0 = rs_clip8_plain(s0), r1 = rs_clip8_plain(s1), r2 = rs_clip8_plain(s2);
     o[0] = slut[r0];
     o[plane] = slut[256 + r1];
     o[2 * plane] = slut[512 + r2];
     if (u8_out) {  // the resized RGB image itself (H, W, 3): reference image of the bilateral solver
         unsigned char* u = u8_out + ((int64_t)b * plane + (int64_t)yy * S + xx) * 3;
-        u[0] = r0; u[1] = r1; u[2] = r2;
+        u[0] = (unsigned char)r0; u[1] = (unsigned char)r1; u[2] = (unsigned char)r2;
     }
 }
 

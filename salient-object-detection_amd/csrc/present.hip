@@ -5,7 +5,7 @@
 // Resize = Pillow's ImagingResample on one 8-bit band, as preprocess.hip applies it to RGB: horizontal pass first, the
 // intermediate rounded and clipped to uint8, then the vertical pass; a pass whose input and output lengths agree is skipped
 // (ks = 0 in the image's descriptor), as Pillow's need_horizontal / need_vertical skip it.  The 22-bit taps come from the
-// host (present.pil_lanczos_coeffs), the kernels apply them in int32 as Resample.c does.
+// host (resample.pil_coeffs, bound as present.pil_lanczos_coeffs), the kernels apply them in int32 through resample.h.
 //   P1  present_h_kernel   one workgroup per (row of the low-resolution mask, 256 output columns): the row is quantised into LDS
 //                          once, every lane runs the tap loop of its output column -> uint8 intermediate (mh x W) in the workspace
 //   P2  present_v_kernel   one lane per four consecutive pixels of the packed output, cut so that the lane's 4-byte mask store and
@@ -16,28 +16,17 @@
 // the ABI's limits), every output row reads up to ks of its rows, and a per-tile recomputation would run the horizontal tap loop once
 // per output row instead of once per mask row.  It is written once and read from the L2.
 // Blend.c does not fuse its multiply and add: contraction is off for this file.
-#include "common.h"
+#include "resample.h"
 
 #pragma clang fp contract(off)
 
 namespace sm {
 
 constexpr int PR_THREADS = 256;
-constexpr int PR_PRECISION_BITS = 32 - 8 - 2;  // Pillow: PRECISION_BITS
 constexpr int PR_MAX_MASK = 512;
 constexpr int PR_MAX_PIXELS = 1 << 24;
 
 __host__ __device__ __forceinline__ int pr_pitch(int max_w) { return (max_w + 3) & ~3; }
-
-// The empty asm keeps the clipped value opaque: left to itself hipcc fuses two shift-and-clip results that are packed into neighbouring
-// bytes into one v_ashr_pk_u8_i32 and ORs further bytes on top as if the instruction had cleared bits 16-31 of its destination, which
-// gfx950 leaves as they were (seen on the MI355X: bytes 0 and 1 of a packed group right, 2 and 3 ORed with stale register bits).
-__device__ __forceinline__ int pr_clip8(int v) {
-    v >>= PR_PRECISION_BITS;  // arithmetic shift, as the C code's table index
-    v = v < 0 ? 0 : (v > 255 ? 255 : v);
-    asm volatile("" : "+v"(v));
-    return v;
-}
 
 // (uint8)(m * 255.0f) of a value in [0, 1]; NaN gives 0
 __device__ __forceinline__ int pr_quant(float m) {
@@ -83,62 +72,38 @@ __global__ __launch_bounds__(PR_THREADS) void present_h_kernel(const float* __re
     const int xx = blockIdx.x * PR_THREADS + threadIdx.x;
     if (xx >= W) return;
     unsigned char* __restrict__ o = ws + ((int64_t)b * mh + y) * pitch;
-    if (im.ksx == 0) {  // pass skipped: W == mw
-        o[xx] = (unsigned char)row[xx < mw ? xx : mw - 1];
+    const RsTaps t = rs_taps(coef, im.coef_x, im.ksx, W, mw, xx);
+    if (!t.k) {  // pass skipped: W == mw
+        o[xx] = (unsigned char)row[t.first];
         return;
     }
-    const int* __restrict__ cb = coef + im.coef_x;  // [W][2] bounds, then [W][ksx] taps
-    int x0 = cb[2 * xx], n = cb[2 * xx + 1];
-    x0 = x0 < 0 ? 0 : (x0 > mw ? mw : x0);          // nothing is read past the row, whatever the table holds
-    n = n < mw - x0 ? n : mw - x0;
-    n = n < im.ksx ? n : im.ksx;
-    const int* __restrict__ k = cb + 2 * (int64_t)W + (int64_t)xx * im.ksx;
-    int s = 1 << (PR_PRECISION_BITS - 1);
-    for (int i = 0; i < n; ++i) s += row[x0 + i] * k[i];
-    o[xx] = (unsigned char)pr_clip8(s);
+    int s = RS_HALF;
+    for (int i = 0; i < t.n; ++i) s += row[t.first + i] * t.k[i];
+    o[xx] = (unsigned char)rs_clip8(s);
 }
 
-struct PrTaps {  // the vertical taps of one output row
-    const int* k;
-    int y0, n;
-};
-__device__ __forceinline__ PrTaps pr_taps(const sm_present_image& im, const int* __restrict__ coef, int mh, int y) {
-    PrTaps t;
-    if (im.ksy == 0) {  // pass skipped: H == mh
-        t.k = nullptr;
-        t.y0 = y < mh ? y : mh - 1;
-        t.n = 0;
-        return t;
-    }
-    const int* __restrict__ cb = coef + im.coef_y;  // [H][2] bounds, then [H][ksy] taps
-    int y0 = cb[2 * y], n = cb[2 * y + 1];
-    y0 = y0 < 0 ? 0 : (y0 > mh ? mh : y0);
-    n = n < mh - y0 ? n : mh - y0;
-    n = n < im.ksy ? n : im.ksy;
-    t.k = cb + 2 * (int64_t)im.H + (int64_t)y * im.ksy;
-    t.y0 = y0;
-    t.n = n;
-    return t;
+// the vertical taps of output row y (k == nullptr: pass skipped, H == mh)
+__device__ __forceinline__ RsTaps pr_taps(const sm_present_image& im, const int* __restrict__ coef, int mh, int y) {
+    return rs_taps(coef, im.coef_y, im.ksy, im.H, mh, y);
 }
 
-__device__ __forceinline__ int pr_vertical_1(const PrTaps& t, const unsigned char* __restrict__ tmp, int pitch, int x) {
-    const unsigned char* __restrict__ p = tmp + (int64_t)t.y0 * pitch + x;
+__device__ __forceinline__ int pr_vertical_1(const RsTaps& t, const unsigned char* __restrict__ tmp, int pitch, int x) {
+    const unsigned char* __restrict__ p = tmp + (int64_t)t.first * pitch + x;
     if (!t.k) return p[0];
-    int s = 1 << (PR_PRECISION_BITS - 1);
+    int s = RS_HALF;
     for (int i = 0; i < t.n; ++i) s += (int)p[(int64_t)i * pitch] * t.k[i];
-    return pr_clip8(s);
+    return rs_clip8(s);
 }
 
 // columns x .. x + 3 of one output row (x + 3 < W <= pitch): four intermediate bytes per load -> the four mask bytes, packed
-__device__ __forceinline__ unsigned pr_vertical_4(const PrTaps& t, const unsigned char* __restrict__ tmp, int pitch, int x) {
-    const unsigned char* __restrict__ p = tmp + (int64_t)t.y0 * pitch + x;
+__device__ __forceinline__ unsigned pr_vertical_4(const RsTaps& t, const unsigned char* __restrict__ tmp, int pitch, int x) {
+    const unsigned char* __restrict__ p = tmp + (int64_t)t.first * pitch + x;
     unsigned w;
     if (!t.k) {
         __builtin_memcpy(&w, p, 4);
         return w;
     }
-    const int half = 1 << (PR_PRECISION_BITS - 1);
-    int s0 = half, s1 = half, s2 = half, s3 = half;
+    int s0 = RS_HALF, s1 = s0, s2 = s0, s3 = s0;
     for (int i = 0; i < t.n; ++i) {
         __builtin_memcpy(&w, p + (int64_t)i * pitch, 4);
         const int c = t.k[i];
@@ -147,7 +112,7 @@ __device__ __forceinline__ unsigned pr_vertical_4(const PrTaps& t, const unsigne
         s2 += (int)((w >> 16) & 255u) * c;
         s3 += (int)(w >> 24) * c;
     }
-    return (unsigned)pr_clip8(s0) | ((unsigned)pr_clip8(s1) << 8) | ((unsigned)pr_clip8(s2) << 16) | ((unsigned)pr_clip8(s3) << 24);
+    return (unsigned)rs_clip8(s0) | ((unsigned)rs_clip8(s1) << 8) | ((unsigned)rs_clip8(s2) << 16) | ((unsigned)rs_clip8(s3) << 24);
 }
 
 __global__ __launch_bounds__(PR_THREADS) void present_v_kernel(const unsigned char* __restrict__ ws, int mh, int pitch,

@@ -1,5 +1,6 @@
-// The bilinear up-sample of one query mask, shared by the evaluator's metric kernels (eval.hip) and the predictor's finish
-// (predict.hip): both must give a pixel the same bits, so both evaluate it with these functions.
+// The bilinear up-samples that more than one file needs.  align_corners=False on one query mask, shared by the evaluator's metric
+// kernels (eval.hip) and the predictor's finish (predict.hip): both must give a pixel the same bits, so both evaluate it with these
+// functions.  align_corners=True on channels-last features (upsample_aligned_kernel): one kernel for cluster.hip and conv.hip.
 #pragma once
 #include "common.h"
 
@@ -48,6 +49,40 @@ struct MaskSrc {
     }
     __device__ __forceinline__ bool operator()(int y, int x) const { return value(y, x) > 0.5f; }
 };
+
+// F.interpolate(mode="bilinear", align_corners=True) by an integer factor on channels-last data, C % 4 == 0: image b's (gh, gw, C)
+// rows start at in + b * strideb, up is dense (B, sf gh, sf gw, C).  Source coordinate o * (in - 1) / (out - 1) (ATen
+// area_pixel_compute_scale / _source_index with align_corners: the scale is formed in fp32), the taps as torch-CPU writes them.
+// Launched by the token up-sample of cluster.hip (strided batch) and the feature-map up-sample of conv.hip.  CT: the channel count
+// when the caller knows it at compile time (cluster.hip's 384: the index split divides by a constant), 0 = the argument C.
+template <int CT>
+__global__ __launch_bounds__(256) void upsample_aligned_kernel(const float* __restrict__ in, int64_t strideb, float* __restrict__ up, int gh,
+                                                               int gw, int c_arg, int sf, int64_t total4) {
+    const int C = CT ? CT : c_arg;
+    const int oh = sf * gh, ow = sf * gw, C4 = C / 4;
+    const float sy = oh > 1 ? (float)(gh - 1) / (float)(oh - 1) : 0.f, sx = ow > 1 ? (float)(gw - 1) / (float)(ow - 1) : 0.f;
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total4; t += (int64_t)gridDim.x * 256) {
+        const int c = (int)(t % C4) * 4;
+        const int64_t px = t / C4;
+        const int ox = (int)(px % ow), oy = (int)((px / ow) % oh);
+        const int64_t b = px / ((int64_t)ow * oh);
+        const float syf = sy * oy, sxf = sx * ox;
+        const int y0 = (int)syf, x0 = (int)sxf;
+        const int y1 = y0 + (y0 < gh - 1 ? 1 : 0), x1 = x0 + (x0 < gw - 1 ? 1 : 0);
+        const float ly1 = syf - y0, ly0 = 1.f - ly1, lx1 = sxf - x0, lx0 = 1.f - lx1;
+        const float* base = in + b * strideb + c;
+        const float4 p00 = *reinterpret_cast<const float4*>(base + ((int64_t)y0 * gw + x0) * C);
+        const float4 p01 = *reinterpret_cast<const float4*>(base + ((int64_t)y0 * gw + x1) * C);
+        const float4 p10 = *reinterpret_cast<const float4*>(base + ((int64_t)y1 * gw + x0) * C);
+        const float4 p11 = *reinterpret_cast<const float4*>(base + ((int64_t)y1 * gw + x1) * C);
+        float4 o;
+        o.x = ly0 * (lx0 * p00.x + lx1 * p01.x) + ly1 * (lx0 * p10.x + lx1 * p11.x);
+        o.y = ly0 * (lx0 * p00.y + lx1 * p01.y) + ly1 * (lx0 * p10.y + lx1 * p11.y);
+        o.z = ly0 * (lx0 * p00.z + lx1 * p01.z) + ly1 * (lx0 * p10.z + lx1 * p11.z);
+        o.w = ly0 * (lx0 * p00.w + lx1 * p01.w) + ly1 * (lx0 * p10.w + lx1 * p11.w);
+        *reinterpret_cast<float4*>(up + px * C + c) = o;
+    }
+}
 
 // the 8-bit soft value of a pixel: (mask * 255).astype(np.uint8) after clip(0, 1), truncating
 __device__ __forceinline__ unsigned up_soft_u8(float v) { return (unsigned)(int)(fminf(fmaxf(v, 0.f), 1.f) * 255.0f); }

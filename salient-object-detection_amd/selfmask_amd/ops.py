@@ -648,12 +648,11 @@ class _PresentTables:
     orders another stream's first use behind that upload).  Image b's pixels start at ``px_off[b]``, a multiple of 4."""
 
     def __init__(self, mh, mw, items, device):
-        import numpy as np
         from .pipeline import upload_tables
-        from .present import pil_lanczos_coeffs
+        from .resample import CoefTable
         B = len(items)
         self.host = (N.PresentImage * B)()
-        parts, index, ci, po, self.px_off = [], {}, 0, 0, []
+        table, po, self.px_off = CoefTable("lanczos"), 0, []
         for b, (h, w, img_off) in enumerate(items):
             if h < 1 or w < 1 or h * w > N.PRESENT_MAX_PIXELS:
                 raise ValueError(f"image {b} is {h} x {w} (1 .. {N.PRESENT_MAX_PIXELS} pixels)")
@@ -661,22 +660,12 @@ class _PresentTables:
             d.img_off, d.px_off, d.H, d.W = img_off, po, h, w
             self.px_off.append(po)
             po += (h * w + 3) & ~3
-            for n_in, n_out, key in ((mw, w, "x"), (mh, h, "y")):
-                o, ks = 0, 0  # a pass between equal lengths is skipped
-                if n_in != n_out:
-                    if (n_in, n_out) not in index:
-                        bounds, taps, ks = pil_lanczos_coeffs(n_in, n_out)
-                        index[(n_in, n_out)] = (ci, ks)
-                        parts += [bounds.reshape(-1), taps.reshape(-1)]
-                        ci += bounds.size + taps.size
-                    o, ks = index[(n_in, n_out)]
-                if key == "x":
-                    d.coef_x, d.ksx = o, ks
-                else:
-                    d.coef_y, d.ksy = o, ks
+            # a pass between equal lengths is skipped: ks = 0
+            d.coef_x, d.ksx = table.add(mw, w) if w != mw else (0, 0)
+            d.coef_y, d.ksy = table.add(mh, h) if h != mh else (0, 0)
         self.B, self.n_pixels, self.max_w = B, po, max(w for _, w, _ in items)
         self.shapes = [(h, w) for h, w, _ in items]
-        (self.coef, self.dev), self.ready = upload_tables([np.concatenate(parts) if parts else np.zeros(1, np.int32), self.host], device)
+        (self.coef, self.dev), self.ready = upload_tables([table.array(), self.host], device)
 
 
 def _present_tables(mh, mw, items, device) -> _PresentTables:

@@ -8,10 +8,8 @@ after each pass); ``/255``; mean (0.485, 0.456, 0.406) / std (0.229, 0.224, 0.22
 exceeds 1.  The host computes only what depends on sizes (tap tables) or on nothing (the 768-entry normalisation table);
 per-pixel arithmetic is the device's.
 """
-import math
 import os
 from concurrent.futures import ThreadPoolExecutor
-from functools import lru_cache
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -20,8 +18,7 @@ from PIL import Image
 
 from . import _native as N
 from .datasets import MEAN, STD
-
-PRECISION_BITS = 32 - 8 - 2  # Pillow, libImaging/Resample.c
+from .resample import PRECISION_BITS, CoefTable, pil_coeffs, resample_pass  # noqa: F401  (PRECISION_BITS: re-exported)
 
 
 def normalize_lut() -> np.ndarray:
@@ -31,59 +28,17 @@ def normalize_lut() -> np.ndarray:
     return np.concatenate([((v - np.float32(MEAN[c])) / np.float32(STD[c])).astype(np.float32) for c in range(3)])
 
 
-@lru_cache(maxsize=4096)
 def pil_resize_coeffs(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray, int]:
-    """Pillow's precompute_coeffs + normalize_coeffs_8bpc for the BILINEAR filter (support 1.0), box = the whole axis.
-    Returns (bounds int32 (out, 2) = first input index / tap count, taps int32 (out, ks), ks).  Plain Python floats are
-    IEEE doubles evaluated in the C code's order, so the fixed-point taps are Pillow's bit for bit."""
-    scale = in_size / out_size
-    filterscale = scale if scale >= 1.0 else 1.0
-    support = 1.0 * filterscale
-    ks = int(math.ceil(support)) * 2 + 1
-    bounds = np.zeros((out_size, 2), np.int32)
-    taps = np.zeros((out_size, ks), np.int32)
-    ss = 1.0 / filterscale
-    for xx in range(out_size):
-        center = (xx + 0.5) * scale
-        xmin = int(center - support + 0.5)
-        if xmin < 0:
-            xmin = 0
-        xmax = int(center + support + 0.5)
-        if xmax > in_size:
-            xmax = in_size
-        xmax -= xmin
-        w = []
-        ww = 0.0
-        for x in range(xmax):
-            t = (x + xmin - center + 0.5) * ss
-            if t < 0.0:
-                t = -t
-            wv = 1.0 - t if t < 1.0 else 0.0
-            w.append(wv)
-            ww += wv
-        for x in range(xmax):
-            k = w[x] / ww if ww != 0.0 else w[x]
-            taps[xx, x] = int(-0.5 + k * (1 << PRECISION_BITS)) if k < 0 else int(0.5 + k * (1 << PRECISION_BITS))
-        bounds[xx] = (xmin, xmax)
-    return bounds, taps, ks
+    """``resample.pil_coeffs`` for the BILINEAR filter (support 1.0): (bounds, taps, ks), cached there"""
+    return pil_coeffs(in_size, out_size, "bilinear")
 
 
 def resize_reference_numpy(img: np.ndarray, S: int) -> np.ndarray:
-    """The same integer arithmetic on the host (numpy): used by the CPU tests to pin ``pil_resize_coeffs`` against
-    ``PIL.Image.resize`` without a GPU.  img (H, W, 3) uint8 -> (S, S, 3) uint8."""
-    H, W, _ = img.shape
-
-    def one_pass(a, n_in, axis_len):  # a: (rows, n_in, 3) -> (rows, S, 3)
-        bounds, taps, ks = pil_resize_coeffs(n_in, S)
-        out = np.empty((a.shape[0], S, 3), np.uint8)
-        for xx in range(S):
-            x0, n = int(bounds[xx, 0]), int(bounds[xx, 1])
-            acc = (a[:, x0:x0 + n, :].astype(np.int64) * taps[xx, :n].astype(np.int64)[None, :, None]).sum(1) + (1 << (PRECISION_BITS - 1))
-            out[:, xx, :] = np.clip(acc >> PRECISION_BITS, 0, 255).astype(np.uint8)
-        return out
-
-    tmp = one_pass(img, W, S)                                       # horizontal first (Resample.c: ImagingResampleInner)
-    return one_pass(tmp.transpose(1, 0, 2), H, S).transpose(1, 0, 2)  # then vertical on the uint8 intermediate
+    """The device's integer arithmetic on the host (numpy): used by the CPU tests to pin ``pil_resize_coeffs`` against
+    ``PIL.Image.resize`` without a GPU.  img (H, W, 3) uint8 -> (S, S, 3) uint8.  Both passes always run, as on the device: one
+    between equal lengths applies the one-tap identity table."""
+    tmp = resample_pass(img, S, "bilinear")                                       # horizontal first (Resample.c: ImagingResampleInner)
+    return resample_pass(tmp.transpose(1, 0, 2), S, "bilinear").transpose(1, 0, 2)  # then vertical on the uint8 intermediate
 
 
 class PinnedPool:
@@ -164,27 +119,17 @@ def pack_tables(shapes, S: Optional[int], pinned: bool = False):
     descr = (N.PreImage * B)()
     offs = packed_pixel_offsets(shapes)
     mk = (lambda n, dt: _POOL.get(n, dt)) if pinned else (lambda n, dt: torch.empty(n, dtype=dt))
-    coef_parts, coef_index, ci = [], {}, 0
+    table = CoefTable("bilinear")
     out_off = 0
     for b, (h, w) in enumerate(shapes):
         d = descr[b]
         d.off, d.H, d.W, d.out_off = offs[b], h, w, out_off
         out_off += 3 * h * w
-        if S is not None:
-            for n_in, key in ((w, "x"), (h, "y")):
-                if n_in not in coef_index:
-                    bounds, taps, ks = pil_resize_coeffs(n_in, S)
-                    coef_index[n_in] = (ci, ks)
-                    coef_parts += [bounds.reshape(-1), taps.reshape(-1)]
-                    ci += bounds.size + taps.size
-                o, ks = coef_index[n_in]
-                if key == "x":
-                    d.coef_x, d.ksx = o, ks
-                else:
-                    d.coef_y, d.ksy = o, ks
-    coef = mk(max(ci, 1), torch.int32)
-    if ci:
-        coef.numpy()[:ci] = np.concatenate(coef_parts)
+        if S is not None:  # both passes always have a table: the identity's single tap when the length is S already
+            (d.coef_x, d.ksx), (d.coef_y, d.ksy) = table.add(w, S), table.add(h, S)
+    ca = table.array()
+    coef = mk(ca.size, torch.int32)
+    coef.numpy()[:] = ca
     dt = mk(ctypes.sizeof(descr), torch.uint8)
     dt.numpy()[:] = np.frombuffer(bytes(descr), np.uint8)
     return coef, dt, out_off

@@ -17,13 +17,11 @@ at 1.1).  Every step is determined to the bit:
 ``present_reference_numpy`` is the restatement the CPU tests pin against Pillow and matplotlib and the GPU tests hold the kernels to -
 the role ``pipeline.resize_reference_numpy`` plays for the input pipeline.
 """
-import math
-from functools import lru_cache
 from typing import Tuple
 
 import numpy as np
 
-from .pipeline import PRECISION_BITS
+from .resample import pil_coeffs, resample_pass
 
 BLEND_ALPHA = 0.5   # Image.blend(original, heat, alpha=0.5), app.py:309
 BRIGHTNESS = 1.1    # ImageEnhance.Brightness(...).enhance(1.1), app.py:310-311
@@ -50,50 +48,10 @@ JET_RGBA = np.frombuffer(bytes.fromhex(
 ), np.uint8).reshape(256, 4)
 
 
-def _lanczos(x: float) -> float:
-    """Resample.c: lanczos_filter, truncated to -3 <= x < 3"""
-    def sinc(v):
-        if v == 0.0:
-            return 1.0
-        v = v * math.pi
-        return math.sin(v) / v
-    if -3.0 <= x < 3.0:
-        return sinc(x) * sinc(x / 3)
-    return 0.0
-
-
-@lru_cache(maxsize=4096)
 def pil_lanczos_coeffs(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray, int]:
-    """Pillow's precompute_coeffs + normalize_coeffs_8bpc for the LANCZOS filter (support 3.0), box = the whole axis: as
-    ``pipeline.pil_resize_coeffs`` (same return value: bounds int32 (out, 2) = first input index / tap count, taps int32 (out, ks),
-    ks) with the other filter.  ks = 7 when up-scaling, ceil(3 in / out) * 2 + 1 when the output is the smaller one."""
-    scale = in_size / out_size
-    filterscale = scale if scale >= 1.0 else 1.0
-    support = 3.0 * filterscale
-    ks = int(math.ceil(support)) * 2 + 1
-    bounds = np.zeros((out_size, 2), np.int32)
-    taps = np.zeros((out_size, ks), np.int32)
-    ss = 1.0 / filterscale
-    for xx in range(out_size):
-        center = (xx + 0.5) * scale
-        xmin = int(center - support + 0.5)
-        if xmin < 0:
-            xmin = 0
-        xmax = int(center + support + 0.5)
-        if xmax > in_size:
-            xmax = in_size
-        xmax -= xmin
-        w = []
-        ww = 0.0
-        for x in range(xmax):
-            wv = _lanczos((x + xmin - center + 0.5) * ss)
-            w.append(wv)
-            ww += wv
-        for x in range(xmax):
-            k = w[x] / ww if ww != 0.0 else w[x]
-            taps[xx, x] = int(-0.5 + k * (1 << PRECISION_BITS)) if k < 0 else int(0.5 + k * (1 << PRECISION_BITS))
-        bounds[xx] = (xmin, xmax)
-    return bounds, taps, ks
+    """``resample.pil_coeffs`` for the LANCZOS filter (support 3.0): (bounds, taps, ks), cached there.  ks = 7 when up-scaling,
+    ceil(3 in / out) * 2 + 1 when the output is the smaller one."""
+    return pil_coeffs(in_size, out_size, "lanczos")
 
 
 def quantize_mask(mask_f32: np.ndarray) -> np.ndarray:
@@ -102,24 +60,15 @@ def quantize_mask(mask_f32: np.ndarray) -> np.ndarray:
     return np.where(np.isnan(t), np.float32(0.0), np.clip(t, 0, 255)).astype(np.uint8)
 
 
-def _one_pass(a: np.ndarray, n_out: int) -> np.ndarray:
-    """(rows, n_in) uint8 -> (rows, n_out) uint8 along axis 1; the array itself when the lengths agree (the pass is skipped)"""
-    n_in = a.shape[1]
-    if n_in == n_out:
-        return a
-    bounds, taps, _ = pil_lanczos_coeffs(n_in, n_out)
-    out = np.empty((a.shape[0], n_out), np.uint8)
-    for xx in range(n_out):
-        x0, n = int(bounds[xx, 0]), int(bounds[xx, 1])
-        acc = (a[:, x0:x0 + n].astype(np.int64) * taps[xx, :n].astype(np.int64)[None]).sum(1) + (1 << (PRECISION_BITS - 1))
-        out[:, xx] = np.clip(acc >> PRECISION_BITS, 0, 255).astype(np.uint8)
-    return out
-
-
 def resize_mask_reference_numpy(m8: np.ndarray, H: int, W: int) -> np.ndarray:
-    """``Image.fromarray(m8).resize((W, H), LANCZOS)`` in numpy integers: horizontal pass, then vertical on the uint8 intermediate"""
-    tmp = _one_pass(np.ascontiguousarray(m8, np.uint8), W)
-    return np.ascontiguousarray(_one_pass(np.ascontiguousarray(tmp.T), H).T)
+    """``Image.fromarray(m8).resize((W, H), LANCZOS)`` in numpy integers: horizontal pass, then vertical on the uint8 intermediate;
+    a pass between equal lengths is skipped, as Pillow's need_horizontal / need_vertical skip it"""
+    a = np.ascontiguousarray(m8, np.uint8)
+    if a.shape[1] != W:
+        a = resample_pass(a, W, "lanczos")
+    if a.shape[0] != H:
+        a = resample_pass(np.ascontiguousarray(a.T), H, "lanczos").T
+    return np.ascontiguousarray(a)
 
 
 def _blend(a: np.ndarray, b: np.ndarray, alpha: float) -> np.ndarray:

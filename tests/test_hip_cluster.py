@@ -16,12 +16,35 @@ from selfmask_amd import voting as VT  # noqa: E402
 DEV = "cuda:0"
 
 
-@pytest.mark.parametrize("gh,gw,scale", [(14, 14, 2), (13, 21, 2), (1, 7, 2), (5, 1, 3), (28, 28, 2)])
+@pytest.mark.parametrize("gh,gw,scale", [(14, 14, 2), (13, 21, 2), (1, 7, 2), (5, 1, 3), (28, 28, 2), (1, 1, 1), (1, 1, 2), (1, 3, 2)])
 def test_upsample_aligned_matches_torch(gh, gw, scale):
     tok = torch.randn(2, gh * gw, 384, generator=torch.Generator().manual_seed(gh * 100 + gw))
     got = VT.upsample_tokens_aligned(tok.to(DEV), gh, gw, scale).cpu()
     ref = CO.upsample_aligned(tok, gh, gw, scale)
     assert got.shape == ref.shape and (got - ref).abs().max().item() <= 2e-6
+
+
+def test_upsample_aligned_entry_points_agree():
+    """sm_upsample_tokens_aligned_f32 (384 channels, a batch stride) and sm_upsample_nhwc_aligned_f32 (any C % 4 == 0, dense) launch
+    one kernel: the same bits at C = 384, a strided batch equals the dense one, other widths stay within 1e-6 of F.interpolate"""
+    import torch.nn.functional as F
+    from selfmask_amd import _native as N, resnet as R
+    for gh, gw, scale in [(1, 1, 2), (2, 5, 3), (5, 1, 3), (13, 21, 2)]:
+        tok = torch.randn(2, gh * gw, 384, generator=torch.Generator().manual_seed(gh * 100 + gw + scale)).to(DEV)
+        dense = VT.upsample_tokens_aligned(tok, gh, gw, scale)
+        assert torch.equal(dense, R.upsample_nhwc_aligned(tok.view(2, gh, gw, 384), scale))
+    gh, gw, scale, pad = 2, 5, 3, 3 * 384                         # each image's rows followed by three rows of NaN
+    wide = torch.full((2, gh * gw * 384 + pad), float("nan"), device=DEV)
+    wide[:, :gh * gw * 384] = torch.randn(2, gh * gw * 384, generator=torch.Generator().manual_seed(7)).to(DEV)
+    up = torch.empty(2, scale * gh, scale * gw, 384, device=DEV)
+    N.check(N.load().sm_upsample_tokens_aligned_f32(wide.data_ptr(), wide.stride(0), up.data_ptr(), 2, gh, gw, scale,
+                                                    torch.cuda.current_stream().cuda_stream), "sm_upsample_tokens_aligned_f32")
+    assert wide.stride(0) > gh * gw * 384
+    assert torch.equal(up, VT.upsample_tokens_aligned(wide[:, :gh * gw * 384].reshape(2, gh * gw, 384), gh, gw, scale))
+    for C in (4, 2048):
+        f = torch.randn(2, 3, 5, C, generator=torch.Generator().manual_seed(C))
+        ref = F.interpolate(f.permute(0, 3, 1, 2), scale_factor=2, mode="bilinear", align_corners=True).permute(0, 2, 3, 1)
+        assert (R.upsample_nhwc_aligned(f.to(DEV), 2).cpu() - ref).abs().max().item() <= 1e-6
 
 
 @pytest.mark.parametrize("lh,lw,k,scale,H,W", [(28, 28, 4, 8, 224, 224), (26, 42, 3, 8, 200, 333), (9, 5, 2, 4, 33, 17)])

@@ -24,15 +24,20 @@ def _host(img, S):
     return np.ascontiguousarray(x.transpose(2, 0, 1))
 
 
-@pytest.mark.parametrize("S", [224, 384])
+@pytest.mark.parametrize("S", [224, 384, 8, 1])
 def test_resize_normalise_bit_exact_vs_pil(S):
+    """every image keeps H <= 100 W: beyond that some Pillow versions run the vertical pass first"""
     rng = np.random.Generator(np.random.PCG64(S))
-    imgs = [rng.integers(0, 256, size=(h, w, 3), dtype=np.uint8) for (h, w) in
-            [(300, 400), (371, 262), (224, 224), (97, 61), (400, 400), (S, S + 1), (1000, 333)]]
-    imgs[1][:100] = 255
-    x = P.preprocess_on_device(imgs, S, DEV).cpu().numpy()
+    sizes = {8: [(1, 1), (1, 7), (7, 1), (2, 3), (8, 8), (8, 9), (25, 2), (5, 35)],  # one-pixel axes, identity, thin rows and columns
+             1: [(1, 1), (3, 2)]}.get(S, [(300, 400), (371, 262), (224, 224), (97, 61), (400, 400), (S, S + 1), (1000, 333)])
+    imgs = [rng.integers(0, 256, size=(h, w, 3), dtype=np.uint8) for (h, w) in sizes]
+    if S >= 224:
+        imgs[1][:100] = 255
+    x, u8 = P.preprocess_on_device(imgs, S, DEV, return_u8=True)
+    x, u8 = x.cpu().numpy(), u8.cpu().numpy()
     for b, im in enumerate(imgs):
         assert np.array_equal(x[b], _host(im, S)), b
+        assert np.array_equal(u8[b], np.asarray(Image.fromarray(im).resize((S, S), Image.BILINEAR))), b
 
 
 def test_native_resolution_bit_exact():

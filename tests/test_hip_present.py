@@ -155,6 +155,18 @@ def test_ops_present_masks_host_and_device():
         ops.present_masks(masks.cpu(), rgbs)
 
 
+def test_skipped_passes_share_a_batch_with_resampled_ones():
+    """one call, a 4 x 6 mask onto sizes that skip both passes, either one and neither (ks = 0 markers beside shared tables)"""
+    rng = np.random.Generator(np.random.PCG64(46))
+    mask = rng.random((4, 6), dtype=np.float32)
+    rgbs = [rng.integers(0, 256, (h, w, 3), dtype=np.uint8) for h, w in [(4, 6), (4, 9), (7, 6), (1, 1), (9, 13)]]
+    got = ops.present_masks(torch.from_numpy(np.stack([mask] * len(rgbs))).to(DEV), rgbs)
+    for (gm, gh), rgb in zip(got, rgbs):
+        wm, wh = P.present_reference_numpy(mask, rgb)
+        assert np.array_equal(gm, wm) and np.array_equal(gh, wh), rgb.shape
+    assert np.array_equal(got[0][0], P.quantize_mask(mask))  # both passes skipped: the quantised mask itself
+
+
 # ---- the serving class --------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def inference():

@@ -1,5 +1,6 @@
 """Host side of the input pipeline (selfmask_amd/pipeline.py) pinned against Pillow and against the reference's
 ToTensor + Normalize expressions - no GPU needed: the device kernels apply exactly these tables in int32 / by look-up."""
+import hashlib
 import os
 import sys
 
@@ -12,12 +13,22 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "salient-object-detection_amd"))
 
 from selfmask_amd import pipeline as P  # noqa: E402
+from selfmask_amd import resample as RS  # noqa: E402
 from selfmask_amd.datasets import MEAN, STD  # noqa: E402
 
 
-@pytest.mark.parametrize("h,w,S", [(300, 400, 224), (371, 262, 224), (224, 224, 224), (97, 61, 224), (400, 300, 384),
-                                   (1000, 333, 224), (225, 223, 224), (30, 500, 64)])
+# the edges of the tables: one-pixel axes, the identity, one past it, a long thin row - and a long thin column where H <= 100 W
+# (beyond that some Pillow versions run the vertical pass first, which the uint8 intermediate makes visible: DESIGN.md)
+EDGES = [(h, w, S) for S in (1, 2, 8, 224) for h, w in [(1, 1), (1, 7), (7, 1), (2, 3), (S, S), (S, S + 1), (5, 4 * S + 3)]]
+EDGES += [(3 * S + 1, 2, S) for S in (1, 2, 8)]
+SIZES = [(300, 400, 224), (371, 262, 224), (224, 224, 224), (97, 61, 224), (400, 300, 384), (1000, 333, 224), (225, 223, 224),
+         (30, 500, 64)]
+SIZES += [e for e in dict.fromkeys(EDGES) if e not in SIZES]  # each case once ((S, S) is (1, 1) at S = 1): the ids stay as they are
+
+
+@pytest.mark.parametrize("h,w,S", SIZES)
 def test_fixed_point_resize_is_pillow_bit_for_bit(h, w, S):
+    assert h <= 100 * w
     rng = np.random.Generator(np.random.PCG64(h * 1000 + w))
     img = rng.integers(0, 256, size=(h, w, 3), dtype=np.uint8)
     img[: h // 3] = (img[: h // 3] // 64) * 64          # flat areas, saturated edges
@@ -34,6 +45,57 @@ def test_tap_tables_shape_and_normalisation():
     assert (b[:, 0] >= 0).all() and (b[:, 0] + b[:, 1] <= 400).all()
     b1, k1, _ = P.pil_resize_coeffs(224, 224)                                 # identity resize: one tap of 1.0
     assert (k1[:, 0] == 1 << P.PRECISION_BITS).all() and (b1[:, 0] == np.arange(224)).all()
+
+
+def _digest(bounds, taps, ks):
+    return hashlib.sha256(bounds.tobytes() + taps.tobytes() + str(ks).encode()).hexdigest()[:16], ks
+
+
+@pytest.mark.parametrize("n_in,n_out,want", [(400, 224, ("3995c8c291a8935c", 5)), (224, 224, ("7ef62fbf725a3365", 3)),
+                                             (1, 8, ("28ba11286a160756", 3)), (7, 1, ("dad034b37fb5e8b8", 15)),
+                                             (2, 224, ("3a9d6ba639bc04d1", 3)), (673, 224, ("209c553951977a5b", 9)),
+                                             (1000, 384, ("4905a018a09fd3be", 7))])
+def test_bilinear_tables_are_the_recorded_ones(n_in, n_out, want):
+    """digests of the tables as they stood before pil_coeffs became the one builder (and what Pillow's BILINEAR gives: the test above)"""
+    assert _digest(*RS.pil_coeffs(n_in, n_out, "bilinear")) == want
+    old, new = P.pil_resize_coeffs(n_in, n_out), RS.pil_coeffs(n_in, n_out, "bilinear")
+    assert old[2] == new[2] and all(a is b for a, b in zip(old, new))   # the old name is a binding, and shares the cache
+    assert P.PRECISION_BITS == RS.PRECISION_BITS == 22 and set(RS.FILTERS) == {"bilinear", "lanczos"}
+    assert RS.FILTERS["bilinear"][0] == 1.0 and RS.FILTERS["lanczos"][0] == 3.0
+
+
+def test_pack_tables_bytes_are_the_recorded_ones():
+    """what reaches the device for a list of shapes: one table per distinct length (the identity's included), descriptors"""
+    coef, descr, out_elems = P.pack_tables([(300, 400), (371, 262), (224, 224), (97, 61), (1, 7)], 224)
+    assert coef.dtype == torch.int32 and coef.numel() == 11872 and out_elems == 819906
+    assert hashlib.sha256(coef.numpy().tobytes()).hexdigest()[:16] == "9646ae13a5ef68b1"
+    assert hashlib.sha256(descr.numpy().tobytes()).hexdigest()[:16] == "cf40964f105b5dc6"
+    coef, _, _ = P.pack_tables([(5, 7)], None)                                # native resolution: no table, one element to point at
+    assert coef.numel() == 1
+
+
+def test_coef_table_keeps_each_pair_once():
+    t = RS.CoefTable("lanczos")
+    assert t.array().tolist() == [0] and t.array().dtype == np.int32         # empty: one zero
+    a, b, a2 = t.add(28, 300), t.add(28, 17), t.add(28, 300)
+    assert a == a2 == (0, 7) and b == (300 * (2 + 7), 11)
+    arr = t.array()
+    assert arr.dtype == np.int32 and arr.size == 300 * (2 + 7) + 17 * (2 + 11)
+    bounds, taps, ks = RS.pil_coeffs(28, 17, "lanczos")
+    assert np.array_equal(arr[b[0]:b[0] + 34], bounds.reshape(-1)) and np.array_equal(arr[b[0] + 34:], taps.reshape(-1))
+    t.add(300, 28)                                                           # the pair is ordered
+    assert t.array().size == arr.size + 28 * (2 + RS.pil_coeffs(300, 28, "lanczos")[2])
+
+
+def test_resample_pass_takes_one_band_or_interleaved_channels():
+    rng = np.random.Generator(np.random.PCG64(11))
+    a = rng.integers(0, 256, size=(5, 37, 3), dtype=np.uint8)
+    for f in ("bilinear", "lanczos"):
+        got = RS.resample_pass(a, 23, f)
+        assert got.shape == (5, 23, 3) and got.dtype == np.uint8
+        for c in range(3):
+            assert np.array_equal(got[:, :, c], RS.resample_pass(np.ascontiguousarray(a[:, :, c]), 23, f))
+    assert np.array_equal(RS.resample_pass(a, 37, "bilinear"), a)           # the identity table: one tap of 1.0
 
 
 def test_normalisation_table_is_totensor_then_normalize():

@@ -36,6 +36,31 @@ def test_lanczos_tap_counts():
     assert (bounds[:, 0] >= 0).all() and (bounds[:, 0] + bounds[:, 1] <= 28).all() and (bounds[:, 1] <= ks).all()
 
 
+@pytest.mark.parametrize("n_in,n_out,want", [(28, 300, ("abdbff08a826d165", 7)), (28, 17, ("34a24bd360e154c7", 11)),
+                                             (56, 1, ("3d1e8acc2b064e1c", 337)), (1, 9, ("6595c8f17eb42ba3", 7)),
+                                             (28, 29, ("6ef37bf9d90c95c0", 7)), (448, 1, ("82f64c4a315f7bc4", 2689))])
+def test_lanczos_tables_are_the_recorded_ones(n_in, n_out, want):
+    """digests of the tables as they stood before resample.pil_coeffs became the one builder"""
+    from selfmask_amd.resample import pil_coeffs
+    bounds, taps, ks = pil_coeffs(n_in, n_out, "lanczos")
+    assert (hashlib.sha256(bounds.tobytes() + taps.tobytes() + str(ks).encode()).hexdigest()[:16], ks) == want
+    assert all(a is b for a, b in zip(P.pil_lanczos_coeffs(n_in, n_out), (bounds, taps, ks)))  # the old name: a binding, one cache
+
+
+EDGE_MASKS = [(mh, mw, H, W) for mh, mw in [(1, 1), (2, 3), (28, 28)]
+              for H, W in [(1, 1), (1, 9), (9, 1), (mh, mw), (mh, 5), (3, mw), (57, 64)]]
+
+
+@pytest.mark.parametrize("mh,mw,H,W", EDGE_MASKS)
+def test_mask_resize_equals_pillow_lanczos_at_the_edges(mh, mw, H, W):
+    """one-pixel masks and outputs, and each pass skipped alone or with the other (equal lengths, as Pillow skips it)"""
+    from PIL import Image
+    m8 = np.random.Generator(np.random.PCG64([mh, mw, H, W])).integers(0, 256, (mh, mw), dtype=np.uint8)
+    got = P.resize_mask_reference_numpy(m8, H, W)
+    assert got.dtype == np.uint8 and got.flags.c_contiguous
+    assert np.array_equal(got, np.array(Image.fromarray(m8).resize((W, H), Image.Resampling.LANCZOS)))
+
+
 @pytest.mark.parametrize("i,kind", CASES)
 def test_heatmap_equals_the_reference_chain(i, kind):
     pytest.importorskip("matplotlib")
