@@ -13,7 +13,7 @@
 //   K4  eval_finalize        the 7 values with the reference's fp32 operation order
 // K1-K3 walk an image in one of two ways, chosen per image: the BAND walk (below) for up-sampled masks - the evaluator's
 // case - and the RASTER walk (2048-pixel chunks, taps staged in LDS) otherwise.  Bound: vector / scalar issue, not HBM (a batch
-// of 64 reads ~30 MB: its ground truths three times and the 28 x 28 masks; 169 us against 311 us for the raster walk alone).
+// of 64 reads ~30 MB: its ground truths three times and the 28 x 28 masks; 165 us against 310-340 us for the raster walk alone: DESIGN.md, round 3).
 #include "common.h"
 #include <math.h>
 
@@ -40,10 +40,39 @@ constexpr int EV_THREADS = 256;
 constexpr int EV_PPT = 8;                       // pixels per thread
 constexpr int EV_CHUNK = EV_THREADS * EV_PPT;   // pixels per workgroup
 constexpr int EV_MAXQ = 32;                     // queries handled per pass of the query kernel
-constexpr int EV_NACC = 22;                     // fp64 partial sums per (image, which, chunk)
+constexpr int EV_NW = EV_THREADS / 64;          // waves per workgroup
+
+// The fp64 partial sums of an (image, which, slot), EV_NACC of them: sum p (K2, for the adaptive threshold), sum |p - g|, the four
+// S-measure quadrants k = 2 * (y >= Y) + (x >= X) with {sum p, sum g, sum p^2, sum p g} each, the foreground's {sum p, sum p^2}
+// and the background's {sum (1 - p), sum (1 - p)^2}.  In the band walk sum g is an integer count and the foreground's sum p the
+// total of the quadrants' sum p g.
+constexpr int ACC_SUM = 0, ACC_ABS = 1, ACC_QUAD = 2, ACC_FG = 18, ACC_FG2 = 19, ACC_BG = 20, ACC_BG2 = 21, EV_NACC = 22;
+constexpr int Q_P = 0, Q_G = 1, Q_PP = 2, Q_PG = 3;  // a quadrant's four sums
+constexpr int acc_quad(int k, int sum) { return ACC_QUAD + 4 * k + sum; }
+static_assert(acc_quad(3, Q_PG) + 1 == ACC_FG, "the quadrants end where the foreground sums begin");
 
 struct QueryStats { unsigned inter, uni; };
 struct GtStats { unsigned long long sum_g, sum_gx, sum_gy; };
+
+// (r0 + r1) + (r2 + r3) of the four waves' entries k: the one order every fp64 sum of a workgroup is finished in
+template <typename T, int N>
+__device__ __forceinline__ T block_total(T (*red)[N], int k) {
+    static_assert(EV_NW == 4, "four waves");
+    return (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+}
+
+// runs add(slot) over the n slots an image's walk wrote, in index order (fixed-order fp64 sums)
+template <typename Add>
+__device__ __forceinline__ void sum_slots(int n, Add&& add) {
+    #pragma unroll 8  // the loads do not depend on the running sum: keep eight in flight (add order unchanged)
+    for (int c = 0; c < n; ++c) add(c);
+}
+
+// centroid (s_measure.py:13-31): round-half-even of the fp32 quotient of exact integer sums
+struct Centroid { int X, Y; };
+__device__ __forceinline__ Centroid centroid(const GtStats& g) {
+    return {(int)rintf(SM_DIV((float)g.sum_gx, (float)g.sum_g)), (int)rintf(SM_DIV((float)g.sum_gy, (float)g.sum_g))};
+}
 
 // pixel index -> (y, x) without an integer division: float reciprocal + one correction step (idx < 2^24)
 __device__ __forceinline__ void split_idx(int idx, int W, float inv_w, int& y, int& x) {
@@ -66,31 +95,51 @@ constexpr int EV_QS = 32;  // query stride of the transposed mask copy (floats):
 //   * 0/1 counts are ballots + s_bcnt1 on the scalar unit or carry-in adds, not per-lane adds behind wave reductions.
 // The raster walk (2048-pixel chunks, taps staged in LDS) stays for images that are not up-sampled at least twice; the walk is
 // chosen PER IMAGE (a row of results must not depend on its neighbours in the batch): band_walk().
-constexpr int EV_BAND_MIN = 2;  // an image takes the band walk from H >= EV_BAND_MIN * mh (kernel argument band_min; the
-                                // tuning build reads SM_EVAL_BAND_MIN, 0 = raster walk for every image)
-constexpr int EV_NR = 4;        // GT rows per pass over the queries (query kernel)
-constexpr int EV_NW = EV_THREADS / 64;
-
-template <int N> struct IntTag { static constexpr int value = N; };
-
+constexpr int EV_BAND_MIN = 2;  // an image takes the band walk from H >= EV_BAND_MIN * mh (the tuning build reads
+                                // SM_EVAL_BAND_MIN, 0 = raster walk for every image)
+constexpr int EV_NR = 4;        // GT rows per pass of the band walk
 constexpr int EV_UPW = 4;          // work units per wave: a wave ends with cross-lane reductions (16 fp64 sums in the metrics kernel,
                                    // two counts per query in the query kernel) - a third of the instructions of a one-unit wave
 constexpr int EV_BAND_MAX_H = 16383;  // a lane of the query kernel counts rows in 16 bits: EV_UPW units x at most H rows each
 static_assert(EV_UPW * EV_BAND_MAX_H < 65536, "per-lane 16-bit row counts of the query kernel");
-// `walk` (a kernel argument) = band_min | units per wave << 8: EV_BAND_MIN | EV_UPW << 8 in the product, SM_EVAL_BAND_MIN /
+// `walk`, an argument of every kernel = band_min | units per wave << 8: EV_BAND_MIN and EV_UPW in the product, SM_EVAL_BAND_MIN /
 // SM_EVAL_UPW (<= EV_UPW) in the tuning build
+constexpr int walk_pack(int band_min, int upw) { return band_min | upw << 8; }
+constexpr int walk_band_min(int walk) { return walk & 255; }
+constexpr int walk_upw(int walk) { return (walk >> 8) > 0 ? walk >> 8 : 1; }
 __device__ __forceinline__ bool band_walk(const sm_eval_image& im, int mh, int walk) {
-    const int band_min = walk & 255;
+    const int band_min = walk_band_min(walk);
     return band_min > 0 && im.H >= band_min * mh && im.H <= EV_BAND_MAX_H;
 }
 __device__ __forceinline__ int band_units(const sm_eval_image& im, int mh) { return mh * ((im.W + 63) >> 6); }
 // partial-sum slots an image uses (its workgroups blockIdx.x < slots_of write one each): a workgroup's four waves take the
 // units 4 * blockIdx.x + wave, stepping by 4 * slots - `upw` units per wave - or the raster chunk blockIdx.x.
-__device__ __forceinline__ int slots_of(const sm_eval_image& im, int mh, int band_min, int nslot) {
-    if (!band_walk(im, mh, band_min)) return (im.H * im.W + EV_CHUNK - 1) / EV_CHUNK;
-    const int upw = (band_min >> 8) > 0 ? band_min >> 8 : 1;
+__device__ __forceinline__ int slots_of(const sm_eval_image& im, int mh, int walk, int nslot) {
+    if (!band_walk(im, mh, walk)) return (im.H * im.W + EV_CHUNK - 1) / EV_CHUNK;
+    const int upw = walk_upw(walk);
     const int s = (band_units(im, mh) + EV_NW * upw - 1) / (EV_NW * upw);
     return s < nslot ? s : nslot;
+}
+
+// source coordinate per destination pixel: F.interpolate's 1 / scale_factor, or in / out when the mask is resized to the GT
+__device__ __forceinline__ float source_scale(float scale, int in_size, int out_size) {
+    return scale > 0.f ? 1.0f / scale : (float)in_size / (float)out_size;
+}
+
+// What every kernel needs to know about image b, built once at its top; the reducers read `slots` and `npx` alone.  A walk adds
+// the two source scales with scales() behind its `blockIdx.x >= slots` exit: most workgroups of a band-walk image leave there, and
+// two fp32 divisions ahead of that exit cost the batch 5 us.
+struct ImageCtx {
+    sm_eval_image im;
+    const unsigned char* gt;
+    int npx, slots;  // slots: slots_of(); a workgroup with blockIdx.x >= slots has nothing to do
+    bool bands;      // band_walk()
+    float sy, sx;    // scales()
+    __device__ __forceinline__ void scales(const sm_eval_args& a) { sy = source_scale(a.scale, a.mh, im.H); sx = source_scale(a.scale, a.mw, im.W); }
+};
+__device__ __forceinline__ ImageCtx image_ctx(const sm_eval_args& a, int b, int walk, int nslot) {
+    const sm_eval_image im = a.images[b];
+    return {im, a.gt + im.gt_off, im.H * im.W, slots_of(im, a.mh, walk, nslot), band_walk(im, a.mh, walk), 0.f, 0.f};
 }
 
 // first destination index d in [0, n] whose (clamped) upper source tap is >= i: the map d -> tap is monotone, so the rows of
@@ -120,6 +169,28 @@ __device__ __forceinline__ BandCol band_col(int seg, int lane, int W, float sx, 
     c.j0 = ux.i0; c.j1 = ux.i1; c.lx0 = ux.l0; c.lx1 = ux.l1;
     return c;
 }
+// one mask plane's top / bot of a column: its samples on the low-res rows i0 and i1
+__device__ __forceinline__ void band_taps(const float* __restrict__ m, int mw, int i0, int i1, const BandCol& c, float& top, float& bot) {
+    top = __builtin_fmaf(m[i0 * mw + c.j0], c.lx0, m[i0 * mw + c.j1] * c.lx1);
+    bot = __builtin_fmaf(m[i1 * mw + c.j0], c.lx0, m[i1 * mw + c.j1] * c.lx1);
+}
+
+// bit r: the lane's GT pixel of row yg + r (r < EV_GROUP, rows < yb): EV_GROUP independent byte loads in flight
+__device__ __forceinline__ unsigned band_gt_bits(const unsigned char* __restrict__ gt, int W, const BandCol& c, int yg, int yb) {
+    // unconditional loads from clamped addresses, masked afterwards: a predicated load is a basic block of its own and the
+    // compiler waits for it before the next one (measured: sixteen serial round trips per group)
+    const unsigned char* col = gt + (c.in ? c.x : 0);
+    unsigned char v[EV_GROUP];
+#pragma unroll
+    for (int r = 0; r < EV_GROUP; ++r) v[r] = col[(yg + r < yb ? yg + r : yb - 1) * W];
+    unsigned bits = 0;
+#pragma unroll
+    for (int r = 0; r < EV_GROUP; ++r) bits |= (v[r] != 0 ? 1u : 0u) << r;
+    const int nr = yb - yg;
+    return c.in ? (nr >= 32 ? bits : bits & ((1u << nr) - 1u)) : 0u;
+}
+
+template <int N> struct IntTag { static constexpr int value = N; };
 
 // K0: maskT[b][p][q] = mask_pred[b][q][p] (q padded to 32) so the nq queries of one bilinear tap are one cache line
 // (models with more than 32 queries - the reference constructor's default is 100, maskformer.py:13 - take one pass of
@@ -129,7 +200,7 @@ __global__ __launch_bounds__(256) void eval_transpose_kernel(sm_eval_args a, flo
     const int b = blockIdx.y, plane = a.mh * a.mw, qbase = blockIdx.z * EV_MAXQ;
     if (blockIdx.x == 0 && blockIdx.z == 0) {
         const sm_eval_image im = a.images[b];
-        const float sy = a.scale > 0.f ? 1.0f / a.scale : (float)a.mh / (float)im.H;
+        const float sy = source_scale(a.scale, a.mh, im.H);
         for (int i = threadIdx.x; i <= a.mh; i += 256) ytab[b * (a.mh + 1) + i] = i < a.mh ? first_dst(i, sy, im.H, a.mh) : im.H;
     }
     const float* __restrict__ m0 = a.mask_pred + (int64_t)b * a.mask_stride_b;
@@ -150,21 +221,6 @@ constexpr int EV_LDS_ROWS = 8;  // low-res rows staged per chunk (falls back to 
 constexpr int EV_LDS_BYTES = 60 * 1024;  // staging budget: wide masks stage fewer rows (lds_rows = budget / row bytes); with the
                                          // kernel's ~1.1 KiB of static LDS (red_u, red_g) the workgroup stays under the 64-KiB default limit
 
-// bit r: the lane's GT pixel of row yg + r (r < EV_GROUP, rows < yb): EV_GROUP independent byte loads in flight
-__device__ __forceinline__ unsigned band_gt_bits(const unsigned char* __restrict__ gt, int W, const BandCol& c, int yg, int yb) {
-    // unconditional loads from clamped addresses, masked afterwards: a predicated load is a basic block of its own and the
-    // compiler waits for it before the next one (measured: sixteen serial round trips per group)
-    const unsigned char* col = gt + (c.in ? c.x : 0);
-    unsigned char v[EV_GROUP];
-#pragma unroll
-    for (int r = 0; r < EV_GROUP; ++r) v[r] = col[(yg + r < yb ? yg + r : yb - 1) * W];
-    unsigned bits = 0;
-#pragma unroll
-    for (int r = 0; r < EV_GROUP; ++r) bits |= (v[r] != 0 ? 1u : 0u) << r;
-    const int nr = yb - yg;
-    return c.in ? (nr >= 32 ? bits : bits & ((1u << nr) - 1u)) : 0u;
-}
-
 // K1, band walk (see above).  Per unit: top / bot of every query of this pass for the lane's column (4 x 16-byte loads per 4
 // queries, once).  Per GT row and query pair one packed mul and one packed fma, per query one compare and one carry-in add that
 // shifts the outcome into a per-lane bit word (word = 2 word + bin): no scalar instruction, no cross-lane traffic per pixel.
@@ -172,48 +228,46 @@ __device__ __forceinline__ unsigned band_gt_bits(const unsigned char* __restrict
 // 16 + 16 bits in one register per query (band_walk() bounds the rows a lane can see); the waves reduce the counts across
 // lanes once, at their end.  BQ4 = groups of four queries the registers are sized for (5: the shipped 20 queries, 8: a full pass).
 template <int BQ4>
-__device__ __forceinline__ void query_bands(const sm_eval_args& a, const sm_eval_image& im, const float* __restrict__ mt,
-                                            const unsigned char* __restrict__ gt, const int* __restrict__ ytab, int nqp,
-                                            bool first_pass, float sy, float sx, int slots, QueryStats* qslot, GtStats* gslot) {
+__device__ __forceinline__ void query_bands(const sm_eval_args& a, const ImageCtx& ic, const float* __restrict__ mt,
+                                            const int* __restrict__ ytab, int nqp, bool first_pass, QueryStats* qslot,
+                                            GtStats* gslot) {
     constexpr int BQ = BQ4 * 4;
     __shared__ unsigned wc[EV_NW][2 * EV_MAXQ + 1];  // per wave: |bin & g|, |bin| per query; [2 * EV_MAXQ] = |g|
     __shared__ unsigned long long wg[EV_NW][2];
     static_assert(BQ <= EV_MAXQ && EV_MAXQ <= 64, "lane q of a wave carries the counts of query q");
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nseg = (im.W + 63) >> 6, units = a.mh * nseg;
     const int nq4 = (nqp + 3) >> 2;
     unsigned cnt[BQ];  // this lane: |bin| in the low, |bin & g| in the high 16 bits
 #pragma unroll
     for (int q = 0; q < BQ; ++q) cnt[q] = 0;
     unsigned ngw = 0, sgx = 0;
     unsigned long long sgy = 0;  // wave-uniform
-    for (int u = blockIdx.x * EV_NW + wv; u < units; u += slots * EV_NW) {
+    const int nseg = (ic.im.W + 63) >> 6, units = a.mh * nseg;
+    for (int u = blockIdx.x * EV_NW + wv; u < units; u += ic.slots * EV_NW) {  // written out per walk: a shared iterator cost 3-4 us a batch
         const int i0 = u / nseg, seg = u - i0 * nseg, i1 = i0 + (i0 < a.mh - 1 ? 1 : 0);
         const int ya = ytab[i0], yb = ytab[i0 + 1];
         if (ya >= yb) continue;
-        const BandCol c = band_col(seg, lane, im.W, sx, a.mw);
+        const BandCol c = band_col(seg, lane, ic.im.W, ic.sx, a.mw);
         f32x2 top[BQ / 2], bot[BQ / 2];  // query pairs: the per-pixel mul and fma are packed (v_pk_mul_f32 / v_pk_fma_f32)
-        {
-            const float4* __restrict__ t00 = reinterpret_cast<const float4*>(mt + (i0 * a.mw + c.j0) * EV_QS);
-            const float4* __restrict__ t01 = reinterpret_cast<const float4*>(mt + (i0 * a.mw + c.j1) * EV_QS);
-            const float4* __restrict__ t10 = reinterpret_cast<const float4*>(mt + (i1 * a.mw + c.j0) * EV_QS);
-            const float4* __restrict__ t11 = reinterpret_cast<const float4*>(mt + (i1 * a.mw + c.j1) * EV_QS);
+        const float4* __restrict__ t00 = reinterpret_cast<const float4*>(mt + (i0 * a.mw + c.j0) * EV_QS);
+        const float4* __restrict__ t01 = reinterpret_cast<const float4*>(mt + (i0 * a.mw + c.j1) * EV_QS);
+        const float4* __restrict__ t10 = reinterpret_cast<const float4*>(mt + (i1 * a.mw + c.j0) * EV_QS);
+        const float4* __restrict__ t11 = reinterpret_cast<const float4*>(mt + (i1 * a.mw + c.j1) * EV_QS);
 #pragma unroll
-            for (int q4 = 0; q4 < BQ4; ++q4) {
-                if (q4 < nq4) {
-                    const float4 p00 = t00[q4], p01 = t01[q4], p10 = t10[q4], p11 = t11[q4];
-                    const float v00[4] = {p00.x, p00.y, p00.z, p00.w}, v01[4] = {p01.x, p01.y, p01.z, p01.w};
-                    const float v10[4] = {p10.x, p10.y, p10.z, p10.w}, v11[4] = {p11.x, p11.y, p11.z, p11.w};
+        for (int q4 = 0; q4 < BQ4; ++q4) {
+            if (q4 < nq4) {
+                const float4 p00 = t00[q4], p01 = t01[q4], p10 = t10[q4], p11 = t11[q4];
+                const float v00[4] = {p00.x, p00.y, p00.z, p00.w}, v01[4] = {p01.x, p01.y, p01.z, p01.w};
+                const float v10[4] = {p10.x, p10.y, p10.z, p10.w}, v11[4] = {p11.x, p11.y, p11.z, p11.w};
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {  // a column past the image's width carries zeros: never above 0.5
-                        top[q4 * 2 + (e >> 1)][e & 1] = c.in ? __builtin_fmaf(v00[e], c.lx0, v01[e] * c.lx1) : 0.f;
-                        bot[q4 * 2 + (e >> 1)][e & 1] = c.in ? __builtin_fmaf(v10[e], c.lx0, v11[e] * c.lx1) : 0.f;
-                    }
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) { top[q4 * 2 + e] = f32x2{0.f, 0.f}; bot[q4 * 2 + e] = f32x2{0.f, 0.f}; }
+                for (int e = 0; e < 4; ++e) {  // a column past the image's width carries zeros: never above 0.5
+                    top[q4 * 2 + (e >> 1)][e & 1] = c.in ? __builtin_fmaf(v00[e], c.lx0, v01[e] * c.lx1) : 0.f;
+                    bot[q4 * 2 + (e >> 1)][e & 1] = c.in ? __builtin_fmaf(v10[e], c.lx0, v11[e] * c.lx1) : 0.f;
                 }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 2; ++e) { top[q4 * 2 + e] = f32x2{0.f, 0.f}; bot[q4 * 2 + e] = f32x2{0.f, 0.f}; }
             }
         }
         unsigned word[BQ], gword = 0, cnt_g = 0;  // bit r of word[q] / gword: bin of query q / GT, r rows ago
@@ -242,7 +296,7 @@ __device__ __forceinline__ void query_bands(const sm_eval_args& a, const sm_eval
 #pragma unroll
             for (int r = 0; r < NR; ++r) {
                 const int y = y0 + r;
-                const UpIdx uy = up_index(y, sy, a.mh);
+                const UpIdx uy = up_index(y, ic.sy, a.mh);
                 ly0[r] = uy.l0; ly1[r] = uy.l1;
                 const bool g = ((gb >> r) & 1u) != 0;
                 gword = gword + gword + (g ? 1u : 0u);
@@ -272,11 +326,13 @@ __device__ __forceinline__ void query_bands(const sm_eval_args& a, const sm_eval
             }
             nbits += NR;
         };
-        // The GT bytes of EV_GROUP rows are requested together, ahead of the passes that use them: a wave is a chain of
-        // dependent global loads (band table -> taps, GT -> counts) and with one load per pass its latency, not its
-        // instructions, set the kernel's time.
+        static_assert(EV_NR == 4 && 32 % EV_NR == 0 && EV_GROUP % EV_NR == 0, "the remainder switch covers 1..3 rows; a word holds whole passes");
+        // The GT bytes of EV_GROUP rows are requested together, ahead of the passes that use them: a wave is a chain of dependent
+        // global loads (band table -> taps, GT -> counts) and with one load per pass its latency, not its instructions, set the
+        // kernel's time.  (This loop and the taps above stay written out here and in metrics_bands: shared with the other walk
+        // through function templates they cost 0.8 us per batch at 28 x 28 masks: DESIGN.md, round 3.)
         for (int yg = ya; yg < yb; yg += EV_GROUP) {
-            const unsigned gbits = band_gt_bits(gt, im.W, c, yg, yb);
+            const unsigned gbits = band_gt_bits(ic.gt, ic.im.W, c, yg, yb);
             const int ye = yg + EV_GROUP < yb ? yg + EV_GROUP : yb;
             int y = yg;
             for (; y + EV_NR <= ye; y += EV_NR) {
@@ -290,7 +346,6 @@ __device__ __forceinline__ void query_bands(const sm_eval_args& a, const sm_eval
                 default: break;
             }
         }
-        static_assert(EV_NR == 4 && 32 % EV_NR == 0 && EV_GROUP % EV_NR == 0, "the remainder switch covers 1..3 rows; a word holds whole passes");
         flush();
         if (first_pass) sgx += cnt_g * (unsigned)c.x;
     }
@@ -310,51 +365,40 @@ __device__ __forceinline__ void query_bands(const sm_eval_args& a, const sm_eval
         if (lane == 0) { wg[wv][0] = tx; wg[wv][1] = sgy; }
     }
     __syncthreads();
-    unsigned ng = 0;
-    for (int k = 0; k < EV_NW; ++k) ng += wc[k][2 * EV_MAXQ];
+    const unsigned ng = block_total(wc, 2 * EV_MAXQ);
     if (tid < nqp) {
-        unsigned in = 0, tot = 0;
-        for (int k = 0; k < EV_NW; ++k) { in += wc[k][2 * tid]; tot += wc[k][2 * tid + 1]; }
-        QueryStats o; o.inter = in; o.uni = tot + ng - in;  // |bin | g| = |bin| + |g| - |bin & g|
-        qslot[tid] = o;
+        const unsigned in = block_total(wc, 2 * tid), tot = block_total(wc, 2 * tid + 1);
+        qslot[tid] = QueryStats{in, tot + ng - in};  // |bin | g| = |bin| + |g| - |bin & g|
     }
-    if (tid == 0 && first_pass) {
-        GtStats o; o.sum_g = ng; o.sum_gx = 0; o.sum_gy = 0;
-        for (int k = 0; k < EV_NW; ++k) { o.sum_gx += wg[k][0]; o.sum_gy += wg[k][1]; }
-        *gslot = o;
-    }
+    if (tid == 0 && first_pass) *gslot = GtStats{ng, block_total(wg, 0), block_total(wg, 1)};
 }
 
 template <int BQ4>
 __global__ __launch_bounds__(EV_THREADS) void eval_query_kernel(sm_eval_args a, const float* __restrict__ maskT_all,
                                                                 const int* __restrict__ ytab, QueryStats* qpart, GtStats* gpart,
-                                                                int nslot, int lds_rows, int band_min) {
+                                                                int nslot, int lds_rows, int walk) {
     extern __shared__ __attribute__((aligned(16))) float taps[];  // [rows][mw][EV_QS] (raster walk)
-    __shared__ unsigned red_u[EV_THREADS / 64][2 * EV_MAXQ];
-    __shared__ unsigned long long red_g[EV_THREADS / 64][3];
+    __shared__ unsigned red_u[EV_NW][2 * EV_MAXQ];
+    __shared__ unsigned long long red_g[EV_NW][3];
     const int b = blockIdx.y;
     const int qbase = blockIdx.z * EV_MAXQ, nqp = min(EV_MAXQ, a.nq - qbase);  // this pass: queries qbase .. qbase+nqp-1
     const float* __restrict__ maskT = maskT_all + (int64_t)blockIdx.z * a.B * a.mh * a.mw * EV_QS;
-    const sm_eval_image im = a.images[b];
-    const int slots = slots_of(im, a.mh, band_min, nslot);
-    if ((int)blockIdx.x >= slots) return;  // the reducers stop at slots_of() too
-    const int npx = im.H * im.W;
+    ImageCtx ic = image_ctx(a, b, walk, nslot);
+    if ((int)blockIdx.x >= ic.slots) return;  // the reducers stop at the image's slots too
     const int base = blockIdx.x * EV_CHUNK;
     QueryStats* qslot = qpart + ((int64_t)b * nslot + blockIdx.x) * a.nq + qbase;  // per-slot partials: no atomics (thousands
     GtStats* gslot = gpart + (int64_t)b * nslot + blockIdx.x;                      // of adds on two cache lines serialise in L2)
-    const unsigned char* __restrict__ gt = a.gt + im.gt_off;
     const float* __restrict__ mt = maskT + (int64_t)b * a.mh * a.mw * EV_QS;
-    const float sy = a.scale > 0.f ? 1.0f / a.scale : (float)a.mh / (float)im.H;
-    const float sx = a.scale > 0.f ? 1.0f / a.scale : (float)a.mw / (float)im.W;
-    if (band_walk(im, a.mh, band_min)) {
-        query_bands<BQ4>(a, im, mt, gt, ytab + b * (a.mh + 1), nqp, qbase == 0, sy, sx, slots, qslot, gslot);
+    ic.scales(a);  // here, not straight behind the exit: eval_query_kernel<8> spills two more scalars there
+    if (ic.bands) {
+        query_bands<BQ4>(a, ic, mt, ytab + b * (a.mh + 1), nqp, qbase == 0, qslot, gslot);
         return;
     }
-    const float inv_w = 1.0f / (float)im.W;
+    const float inv_w = 1.0f / (float)ic.im.W;
     const int nq4 = (nqp + 3) >> 2;
     // low-res rows touched by this chunk
-    const int last = min(base + EV_CHUNK, npx) - 1;
-    const int r_lo = up_index(base / im.W, sy, a.mh).i0, r_hi = up_index(last / im.W, sy, a.mh).i1;
+    const int last = min(base + EV_CHUNK, ic.npx) - 1;
+    const int r_lo = up_index(base / ic.im.W, ic.sy, a.mh).i0, r_hi = up_index(last / ic.im.W, ic.sy, a.mh).i1;
     const bool staged = (r_hi - r_lo + 1) <= lds_rows;
     if (staged) {
         const int n4 = (r_hi - r_lo + 1) * a.mw * (EV_QS / 4);
@@ -371,11 +415,11 @@ __global__ __launch_bounds__(EV_THREADS) void eval_query_kernel(sm_eval_args a, 
     auto body = [&](const float* tb, int row0) {
         for (int k = 0; k < EV_PPT; ++k) {
             const int idx = base + k * EV_THREADS + threadIdx.x;
-            if (idx >= npx) break;
+            if (idx >= ic.npx) break;
             int y, x;
-            split_idx(idx, im.W, inv_w, y, x);
-            const UpIdx uy = up_index(y, sy, a.mh), ux = up_index(x, sx, a.mw);
-            const unsigned g = gt[idx] != 0;
+            split_idx(idx, ic.im.W, inv_w, y, x);
+            const UpIdx uy = up_index(y, ic.sy, a.mh), ux = up_index(x, ic.sx, a.mw);
+            const unsigned g = ic.gt[idx] != 0;
             if (g) { sg += 1; sgx += (unsigned)x; sgy += (unsigned)y; }
             const float4* t00 = reinterpret_cast<const float4*>(tb + ((uy.i0 - row0) * a.mw + ux.i0) * EV_QS);
             const float4* t01 = reinterpret_cast<const float4*>(tb + ((uy.i0 - row0) * a.mw + ux.i1) * EV_QS);
@@ -414,62 +458,10 @@ __global__ __launch_bounds__(EV_THREADS) void eval_query_kernel(sm_eval_args a, 
     __syncthreads();
     if (threadIdx.x < nqp) {
         const int q = threadIdx.x;
-        QueryStats o;
-        o.inter = red_u[0][2 * q] + red_u[1][2 * q] + red_u[2][2 * q] + red_u[3][2 * q];
-        o.uni = red_u[0][2 * q + 1] + red_u[1][2 * q + 1] + red_u[2][2 * q + 1] + red_u[3][2 * q + 1];
-        qslot[q] = o;
+        qslot[q] = QueryStats{block_total(red_u, 2 * q), block_total(red_u, 2 * q + 1)};
     }
-    if (threadIdx.x == 0 && qbase == 0) {  // the ground-truth sums do not depend on the query pass
-        GtStats o;
-        o.sum_g = red_g[0][0] + red_g[1][0] + red_g[2][0] + red_g[3][0];
-        o.sum_gx = red_g[0][1] + red_g[1][1] + red_g[2][1] + red_g[3][1];
-        o.sum_gy = red_g[0][2] + red_g[1][2] + red_g[2][2] + red_g[3][2];
-        *gslot = o;
-    }
-}
-
-// K1b: sum the per-chunk partials of an image (one thread per query)
-__device__ int select_query(const sm_eval_args& a, const QueryStats* qs, int b, int which, bool write_ious);
-
-__global__ __launch_bounds__(1024) void eval_reduce_query_kernel(sm_eval_args a, const QueryStats* qpart, const GtStats* gpart,
-                                                               QueryStats* qs, GtStats* gs, int* sel, int nslot, int band_min) {
-    const int b = blockIdx.x, t = threadIdx.x;
-    const int nchunk = slots_of(a.images[b], a.mh, band_min, nslot);  // the slots this image's walk wrote
-    if (t < a.nq) {
-        QueryStats o; o.inter = 0; o.uni = 0;
-        #pragma unroll 8  // the loads do not depend on the running sum: keep eight in flight (add order unchanged)
-        for (int c = 0; c < nchunk; ++c) {
-            const QueryStats p = qpart[((int64_t)b * nslot + c) * a.nq + t];
-            o.inter += p.inter; o.uni += p.uni;
-        }
-        qs[b * a.nq + t] = o;
-    }
-    if (t == (int)blockDim.x - 1) {  // blockDim.x = nq + 1 rounded up to whole waves: the last lane is always spare
-        GtStats o; o.sum_g = 0; o.sum_gx = 0; o.sum_gy = 0;
-        #pragma unroll 8  // the loads do not depend on the running sum: keep eight in flight (add order unchanged)
-        for (int c = 0; c < nchunk; ++c) {
-            const GtStats p = gpart[(int64_t)b * nslot + c];
-            o.sum_g += p.sum_g; o.sum_gx += p.sum_gx; o.sum_gy += p.sum_gy;
-        }
-        gs[b] = o;
-    }
-    // the two selected queries of the image, once, for every later kernel (each of their ~10^4 workgroups used to
-    // repeat this 20-load chain on one thread before starting)
-    __syncthreads();
-    if (t < 2) sel[b * 2 + t] = select_query(a, qs, b, t, true);
-}
-
-// K2b: adaptive threshold 2 * mean(p) of the selected masks (f_measure.py:76): fixed-order fp64 sum of K2's partials
-__global__ __launch_bounds__(64) void eval_adapt_kernel(sm_eval_args a, const double* part, float* thr_adapt, int nslot, int band_min) {
-    const int which = blockIdx.x, b = blockIdx.y;
-    if (threadIdx.x != 0) return;
-    const sm_eval_image im = a.images[b];
-    const int nchunk = slots_of(im, a.mh, band_min, nslot);
-    double sp = 0.0;
-    const double* p0 = part + (int64_t)(b * 2 + which) * nslot * EV_NACC;
-    #pragma unroll 8  // the loads do not depend on the running sum: keep eight in flight (add order unchanged)
-    for (int k = 0; k < nchunk; ++k) sp += p0[(int64_t)k * EV_NACC];
-    thr_adapt[b * 2 + which] = SM_MUL(2.0f, (float)(sp / (double)(im.H * im.W)));
+    if (threadIdx.x == 0 && qbase == 0)  // the ground-truth sums do not depend on the query pass
+        *gslot = GtStats{block_total(red_g, 0), block_total(red_g, 1), block_total(red_g, 2)};
 }
 
 // selection (evaluator.pyc@L216-221): which = 0 arg-max objectness, which = 1 arg-max IoU (first maximum)
@@ -488,6 +480,44 @@ __device__ int select_query(const sm_eval_args& a, const QueryStats* qs, int b, 
         }
     }
     return best;
+}
+
+// K1b: sum the per-chunk partials of an image (one thread per query)
+__global__ __launch_bounds__(1024) void eval_reduce_query_kernel(sm_eval_args a, const QueryStats* qpart, const GtStats* gpart,
+                                                               QueryStats* qs, GtStats* gs, int* sel, int nslot, int walk) {
+    const int b = blockIdx.x, t = threadIdx.x;
+    const int slots = image_ctx(a, b, walk, nslot).slots;
+    if (t < a.nq) {
+        QueryStats o{0, 0};
+        sum_slots(slots, [&](int c) {
+            const QueryStats p = qpart[((int64_t)b * nslot + c) * a.nq + t];
+            o.inter += p.inter; o.uni += p.uni;
+        });
+        qs[b * a.nq + t] = o;
+    }
+    if (t == (int)blockDim.x - 1) {  // blockDim.x = nq + 1 rounded up to whole waves: the last lane is always spare
+        GtStats o{0, 0, 0};
+        sum_slots(slots, [&](int c) {
+            const GtStats p = gpart[(int64_t)b * nslot + c];
+            o.sum_g += p.sum_g; o.sum_gx += p.sum_gx; o.sum_gy += p.sum_gy;
+        });
+        gs[b] = o;
+    }
+    // the two selected queries of the image, once, for every later kernel (each of their ~10^4 workgroups used to
+    // repeat this 20-load chain on one thread before starting)
+    __syncthreads();
+    if (t < 2) sel[b * 2 + t] = select_query(a, qs, b, t, true);
+}
+
+// K2b: adaptive threshold 2 * mean(p) of the selected masks (f_measure.py:76): fixed-order fp64 sum of K2's partials
+__global__ __launch_bounds__(64) void eval_adapt_kernel(sm_eval_args a, const double* part, float* thr_adapt, int nslot, int walk) {
+    const int which = blockIdx.x, b = blockIdx.y;
+    if (threadIdx.x != 0) return;
+    const ImageCtx ic = image_ctx(a, b, walk, nslot);
+    double sp = 0.0;
+    const double* p0 = part + (int64_t)(b * 2 + which) * nslot * EV_NACC + ACC_SUM;
+    sum_slots(ic.slots, [&](int k) { sp += p0[(int64_t)k * EV_NACC]; });
+    thr_adapt[b * 2 + which] = SM_MUL(2.0f, (float)(sp / (double)ic.npx));
 }
 
 // fp32 ratios exactly as torch evaluates them (int64 counts -> float32, python scalars -> float32, no fma)
@@ -525,37 +555,32 @@ __device__ float object_score(double n, double s, double ss) {
 
 // K2: sum of the selected mask's probabilities per chunk (needed for the adaptive threshold 2*mean before K3)
 __global__ __launch_bounds__(EV_THREADS) void eval_sum_kernel(sm_eval_args a, const int* __restrict__ sel, const int* __restrict__ ytab_all,
-                                                              double* part, int nslot, int band_min) {
-    __shared__ double red[EV_THREADS / 64];
+                                                              double* part, int nslot, int walk) {
+    __shared__ double red[EV_NW][1];
     const int which = blockIdx.y, b = blockIdx.z, c = blockIdx.x;
-    const sm_eval_image im = a.images[b];
-    const int slots = slots_of(im, a.mh, band_min, nslot);
-    if (c >= slots) return;
-    const int npx = im.H * im.W, base = c * EV_CHUNK;
+    ImageCtx ic = image_ctx(a, b, walk, nslot);
+    if (c >= ic.slots) return;
+    ic.scales(a);
     double* slot = part + ((int64_t)(b * 2 + which) * nslot + c) * EV_NACC;
-    const int sel_q = sel[b * 2 + which];
-    const float* __restrict__ m = a.mask_pred + (int64_t)b * a.mask_stride_b + (int64_t)sel_q * a.mh * a.mw;
-    const float sy = a.scale > 0.f ? 1.0f / a.scale : (float)a.mh / (float)im.H;
-    const float sx = a.scale > 0.f ? 1.0f / a.scale : (float)a.mw / (float)im.W;
-    if (band_walk(im, a.mh, band_min)) {  // both selected queries in one walk (blockIdx.y = 1 has nothing to do)
+    const float* __restrict__ m = a.mask_pred + (int64_t)b * a.mask_stride_b + (int64_t)sel[b * 2 + which] * a.mh * a.mw;
+    if (ic.bands) {  // both selected queries in one walk (blockIdx.y = 1 has nothing to do)
         if (which != 0) return;
         __shared__ double red2[EV_NW][2];
         const float* __restrict__ m1 = a.mask_pred + (int64_t)b * a.mask_stride_b + (int64_t)sel[b * 2 + 1] * a.mh * a.mw;
-        const int* __restrict__ ytab = ytab_all + b * (a.mh + 1);
         const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        const int nseg = (im.W + 63) >> 6, units = a.mh * nseg;
         double s0 = 0.0, s1 = 0.0;
-        for (int u = c * EV_NW + wv; u < units; u += slots * EV_NW) {
+        const int* __restrict__ ytab = ytab_all + b * (a.mh + 1);
+        const int nseg = (ic.im.W + 63) >> 6, units = a.mh * nseg;
+        for (int u = blockIdx.x * EV_NW + wv; u < units; u += ic.slots * EV_NW) {
             const int i0 = u / nseg, seg = u - i0 * nseg, i1 = i0 + (i0 < a.mh - 1 ? 1 : 0);
             const int ya = ytab[i0], yb = ytab[i0 + 1];
-            const BandCol k = band_col(seg, lane, im.W, sx, a.mw);
+            const BandCol k = band_col(seg, lane, ic.im.W, ic.sx, a.mw);
             if (ya >= yb || !k.in) continue;
-            const float top0 = __builtin_fmaf(m[i0 * a.mw + k.j0], k.lx0, m[i0 * a.mw + k.j1] * k.lx1);
-            const float bot0 = __builtin_fmaf(m[i1 * a.mw + k.j0], k.lx0, m[i1 * a.mw + k.j1] * k.lx1);
-            const float top1 = __builtin_fmaf(m1[i0 * a.mw + k.j0], k.lx0, m1[i0 * a.mw + k.j1] * k.lx1);
-            const float bot1 = __builtin_fmaf(m1[i1 * a.mw + k.j0], k.lx0, m1[i1 * a.mw + k.j1] * k.lx1);
+            float top0, bot0, top1, bot1;
+            band_taps(m, a.mw, i0, i1, k, top0, bot0);
+            band_taps(m1, a.mw, i0, i1, k, top1, bot1);
             for (int y = ya; y < yb; ++y) {
-                const UpIdx uy = up_index(y, sy, a.mh);
+                const UpIdx uy = up_index(y, ic.sy, a.mh);
                 s0 += (double)__builtin_fmaf(top0, uy.l0, bot0 * uy.l1);
                 s1 += (double)__builtin_fmaf(top1, uy.l0, bot1 * uy.l1);
             }
@@ -563,23 +588,22 @@ __global__ __launch_bounds__(EV_THREADS) void eval_sum_kernel(sm_eval_args a, co
         s0 = wave_total(s0); s1 = wave_total(s1);
         if (lane == 0) { red2[wv][0] = s0; red2[wv][1] = s1; }
         __syncthreads();
-        if (threadIdx.x < 2)
-            (slot + (int64_t)threadIdx.x * nslot * EV_NACC)[0] = (red2[0][threadIdx.x] + red2[1][threadIdx.x]) + (red2[2][threadIdx.x] + red2[3][threadIdx.x]);
+        if (threadIdx.x < 2) (slot + (int64_t)threadIdx.x * nslot * EV_NACC)[ACC_SUM] = block_total(red2, threadIdx.x);
         return;
     }
-    const float inv_w = 1.0f / (float)im.W;
+    const float inv_w = 1.0f / (float)ic.im.W;
     double sp = 0.0;
     for (int k = 0; k < EV_PPT; ++k) {
-        const int idx = base + k * EV_THREADS + threadIdx.x;
-        if (idx >= npx) break;
+        const int idx = c * EV_CHUNK + k * EV_THREADS + threadIdx.x;
+        if (idx >= ic.npx) break;
         int y, x;
-        split_idx(idx, im.W, inv_w, y, x);
-        sp += (double)up_sample(m, a.mw, up_index(y, sy, a.mh), up_index(x, sx, a.mw));
+        split_idx(idx, ic.im.W, inv_w, y, x);
+        sp += (double)up_sample(m, a.mw, up_index(y, ic.sy, a.mh), up_index(x, ic.sx, a.mw));
     }
     sp = wave_total(sp);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sp;
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][0] = sp;
     __syncthreads();
-    if (threadIdx.x == 0) slot[0] = (red[0] + red[1]) + (red[2] + red[3]);
+    if (threadIdx.x == 0) slot[ACC_SUM] = block_total(red, 0);
 }
 
 struct MetricCounts { unsigned tp5, np5, ng, eq5, tpa, npa; unsigned hist[2][256]; };
@@ -607,72 +631,67 @@ __device__ __forceinline__ int thresholds_below_window(const float* thrp, float 
 // K3, band walk: the selected query's top / bot per lane once per unit, p = fma(top, ly0, bot * ly1) per pixel; every 0/1 count
 // a ballot; the S-measure moments of a unit's rows above / below the centroid row accumulate per lane (the row side is
 // wave-uniform: two loops) and are folded into the four quadrants by the lane's column side when the unit ends.
-__device__ __forceinline__ void metrics_bands(const sm_eval_args& a, const sm_eval_image& im, const float* __restrict__ m,
-                                              const unsigned char* __restrict__ gt, const int* __restrict__ ytab, float sy, float sx,
-                                              float thr_adapt, int X, int Y, int slots, unsigned (*hist)[256], const float* thr,
-                                              double (*red)[EV_NACC], double* slot, MetricCounts* mc) {
-    constexpr int NW = EV_NW;
-    __shared__ unsigned wcnt[NW][6], gq[4];
+__device__ __forceinline__ void metrics_bands(const sm_eval_args& a, const ImageCtx& ic, const float* __restrict__ m,
+                                              const int* __restrict__ ytab, float thr_adapt, int X, int Y, unsigned (*hist)[256],
+                                              const float* thr, double (*red)[EV_NACC], double* slot, MetricCounts* mc) {
+    __shared__ unsigned wcnt[EV_NW][6], gq[4];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     __shared__ float thrp[EV_THRP];  // thrp[i] = thr[i - 2], -inf before, +inf after: thresholds_below_window()
     for (int i = tid; i < EV_THRP; i += EV_THREADS) thrp[i] = i < 2 ? -INFINITY : (i - 2 < 255 ? thr[i - 2] : INFINITY);
     if (tid < 4) gq[tid] = 0;
     __syncthreads();
-    const int nseg = (im.W + 63) >> 6, units = a.mh * nseg;
     unsigned tp5 = 0, np5 = 0, ng = 0, eq5 = 0, tpa = 0, npa = 0, g0 = 0, g1 = 0, g2 = 0, g3 = 0;  // wave-uniform (scalar registers)
     double aabs = 0.0, fpp = 0.0, bo = 0.0, boo = 0.0;
     double qp[4] = {0.0, 0.0, 0.0, 0.0}, qpp[4] = {0.0, 0.0, 0.0, 0.0}, qpg[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int u = blockIdx.x * NW + wv; u < units; u += slots * NW) {
+    const int nseg = (ic.im.W + 63) >> 6, units = a.mh * nseg;
+    for (int u = blockIdx.x * EV_NW + wv; u < units; u += ic.slots * EV_NW) {
         const int i0 = u / nseg, seg = u - i0 * nseg, i1 = i0 + (i0 < a.mh - 1 ? 1 : 0);
         const int ya = ytab[i0], yb = ytab[i0 + 1];
         if (ya >= yb) continue;
-        const BandCol c = band_col(seg, lane, im.W, sx, a.mw);
+        const BandCol c = band_col(seg, lane, ic.im.W, ic.sx, a.mw);
         float top = 0.f, bot = 0.f;
-        if (c.in) {
-            top = __builtin_fmaf(m[i0 * a.mw + c.j0], c.lx0, m[i0 * a.mw + c.j1] * c.lx1);
-            bot = __builtin_fmaf(m[i1 * a.mw + c.j0], c.lx0, m[i1 * a.mw + c.j1] * c.lx1);
-        }
+        if (c.in) band_taps(m, a.mw, i0, i1, c, top, bot);
         const bool right = c.x >= X;
         const unsigned long long vm = __ballot(c.in), rm = __ballot(c.in && right);
-        // NR rows of the unit from y0, all on one side of the centroid row: sums into (sp, spp, spg), GT counts left / right.
+        // The unit's rows [y_from, y_to), all on one side of the centroid row: sums into (sp, spp, spg), GT counts left / right.
         // The rows of a pass are independent chains (GT byte, table window, histogram add): their latencies overlap.
-        auto rows = [&](auto nr_tag, int y0, unsigned gb, double& sp, double& spp, double& spg, unsigned& gl, unsigned& gr) {
-            constexpr int NR = decltype(nr_tag)::value;
-            float p[NR];
-            bool g[NR];
-#pragma unroll
-            for (int r = 0; r < NR; ++r) {
-                const UpIdx uy = up_index(y0 + r, sy, a.mh);
-                p[r] = __builtin_fmaf(top, uy.l0, bot * uy.l1);  // columns past the width: top = bot = 0 -> p = 0
-                g[r] = ((gb >> r) & 1u) != 0;
-            }
-#pragma unroll
-            for (int r = 0; r < NR; ++r) {
-                const unsigned long long gm = __ballot(g[r]);
-                const unsigned long long b5 = __ballot(c.in && p[r] > 0.5f), ba = __ballot(c.in && p[r] > thr_adapt);
-                tp5 += (unsigned)__popcll(b5 & gm); np5 += (unsigned)__popcll(b5); ng += (unsigned)__popcll(gm);
-                eq5 += (unsigned)__popcll(~(b5 ^ gm) & vm); tpa += (unsigned)__popcll(ba & gm); npa += (unsigned)__popcll(ba);
-                gr += (unsigned)__popcll(gm & rm); gl += (unsigned)__popcll(gm & ~rm);
-                if (c.in) atomicAdd(&hist[g[r] ? 1 : 0][thresholds_below_window(thrp, p[r])], 1u);
-                // absent columns carry p = 0, g = 0: they add 0 to every sum below except the background's (masked)
-                const float gf = g[r] ? 1.0f : 0.0f;
-                const double pd = (double)p[r], pp = pd * pd;
-                aabs += (double)fabsf(p[r] - gf);
-                sp += pd; spp += pp; spg += g[r] ? pd : 0.0;
-                fpp += g[r] ? pp : 0.0;
-                const double o = (double)(1.0f - p[r]);
-                const bool bg = c.in && !g[r];
-                bo += bg ? o : 0.0; boo += bg ? o * o : 0.0;
-            }
-        };
         auto walk = [&](int y_from, int y_to, double& sp, double& spp, double& spg, unsigned& gl, unsigned& gr) {
+            auto rows = [&](auto nr_tag, int y0, unsigned gb) {
+                constexpr int NR = decltype(nr_tag)::value;
+                float p[NR];
+                bool g[NR];
+#pragma unroll
+                for (int r = 0; r < NR; ++r) {
+                    const UpIdx uy = up_index(y0 + r, ic.sy, a.mh);
+                    p[r] = __builtin_fmaf(top, uy.l0, bot * uy.l1);  // columns past the width: top = bot = 0 -> p = 0
+                    g[r] = ((gb >> r) & 1u) != 0;
+                }
+#pragma unroll
+                for (int r = 0; r < NR; ++r) {
+                    const unsigned long long gm = __ballot(g[r]);
+                    const unsigned long long b5 = __ballot(c.in && p[r] > 0.5f), ba = __ballot(c.in && p[r] > thr_adapt);
+                    tp5 += (unsigned)__popcll(b5 & gm); np5 += (unsigned)__popcll(b5); ng += (unsigned)__popcll(gm);
+                    eq5 += (unsigned)__popcll(~(b5 ^ gm) & vm); tpa += (unsigned)__popcll(ba & gm); npa += (unsigned)__popcll(ba);
+                    gr += (unsigned)__popcll(gm & rm); gl += (unsigned)__popcll(gm & ~rm);
+                    if (c.in) atomicAdd(&hist[g[r] ? 1 : 0][thresholds_below_window(thrp, p[r])], 1u);
+                    // absent columns carry p = 0, g = 0: they add 0 to every sum below except the background's (masked)
+                    const float gf = g[r] ? 1.0f : 0.0f;
+                    const double pd = (double)p[r], pp = pd * pd;
+                    aabs += (double)fabsf(p[r] - gf);
+                    sp += pd; spp += pp; spg += g[r] ? pd : 0.0;
+                    fpp += g[r] ? pp : 0.0;
+                    const double o = (double)(1.0f - p[r]);
+                    const bool bg = c.in && !g[r];
+                    bo += bg ? o : 0.0; boo += bg ? o * o : 0.0;
+                }
+            };
             for (int yg = y_from; yg < y_to; yg += EV_GROUP) {  // the GT bytes of EV_GROUP rows are requested together (query_bands)
-                const unsigned gbits = band_gt_bits(gt, im.W, c, yg, y_to);
+                const unsigned gbits = band_gt_bits(ic.gt, ic.im.W, c, yg, y_to);
                 const int ye = yg + EV_GROUP < y_to ? yg + EV_GROUP : y_to;
                 int y = yg;
-                for (; y + EV_NR <= ye; y += EV_NR) rows(IntTag<EV_NR>{}, y, gbits >> (y - yg), sp, spp, spg, gl, gr);
-                for (; y < ye; ++y) rows(IntTag<1>{}, y, gbits >> (y - yg), sp, spp, spg, gl, gr);
+                for (; y + EV_NR <= ye; y += EV_NR) rows(IntTag<EV_NR>{}, y, gbits >> (y - yg));
+                for (; y < ye; ++y) rows(IntTag<1>{}, y, gbits >> (y - yg));
             }
         };
         double tp = 0.0, tpp = 0.0, tpg = 0.0, bp = 0.0, bpp = 0.0, bpg = 0.0;  // top rows (y < Y) / bottom rows (y >= Y)
@@ -684,40 +703,35 @@ __device__ __forceinline__ void metrics_bands(const sm_eval_args& a, const sm_ev
         qp[2] += right ? 0.0 : bp; qpp[2] += right ? 0.0 : bpp; qpg[2] += right ? 0.0 : bpg;
         qp[3] += right ? bp : 0.0; qpp[3] += right ? bpp : 0.0; qpg[3] += right ? bpg : 0.0;
     }
-    // acc layout of the raster walk (EV_NACC): 1 = sum|p-g|; 2+4k.. = quadrant k {sum p, sum g, sum p^2, sum p g}; 18, 19 = fg
-    // {sum p, sum p^2}; 20, 21 = bg {sum (1-p), sum (1-p)^2}.  sum g is an integer count (gq), fg sum p the total of sum p g.
-    {
+    {   // every sum of the layout but the quadrants' sum g (the integer counts gq) and ACC_FG (the total of their sum p g)
         double v;
-        v = wave_total(aabs); if (lane == 0) red[wv][1] = v;
+        v = wave_total(aabs); if (lane == 0) red[wv][ACC_ABS] = v;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            v = wave_total(qp[k]); if (lane == 0) red[wv][2 + 4 * k] = v;
-            v = wave_total(qpp[k]); if (lane == 0) red[wv][4 + 4 * k] = v;
-            v = wave_total(qpg[k]); if (lane == 0) red[wv][5 + 4 * k] = v;
+            v = wave_total(qp[k]); if (lane == 0) red[wv][acc_quad(k, Q_P)] = v;
+            v = wave_total(qpp[k]); if (lane == 0) red[wv][acc_quad(k, Q_PP)] = v;
+            v = wave_total(qpg[k]); if (lane == 0) red[wv][acc_quad(k, Q_PG)] = v;
         }
-        v = wave_total(fpp); if (lane == 0) red[wv][19] = v;
-        v = wave_total(bo); if (lane == 0) red[wv][20] = v;
-        v = wave_total(boo); if (lane == 0) red[wv][21] = v;
+        v = wave_total(fpp); if (lane == 0) red[wv][ACC_FG2] = v;
+        v = wave_total(bo); if (lane == 0) red[wv][ACC_BG] = v;
+        v = wave_total(boo); if (lane == 0) red[wv][ACC_BG2] = v;
     }
     if (lane == 0) {
         wcnt[wv][0] = tp5; wcnt[wv][1] = np5; wcnt[wv][2] = ng; wcnt[wv][3] = eq5; wcnt[wv][4] = tpa; wcnt[wv][5] = npa;
         atomicAdd(&gq[0], g0); atomicAdd(&gq[1], g1); atomicAdd(&gq[2], g2); atomicAdd(&gq[3], g3);
     }
     __syncthreads();
-    if (tid > 0 && tid < EV_NACC) {
+    if (tid > ACC_SUM && tid < EV_NACC && tid != ACC_FG) {
         const int k = tid;
-        double v;
-        if (k >= 2 && k < 18 && ((k - 2) & 3) == 1) v = (double)gq[(k - 2) >> 2];
-        else if (k == 18) v = 0.0;  // filled below from the four sums of p g
-        else v = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
-        if (k != 18) slot[k] = v;
+        const bool sum_g = k >= ACC_QUAD && k < ACC_FG && ((k - ACC_QUAD) & 3) == Q_G;
+        slot[k] = sum_g ? (double)gq[(k - ACC_QUAD) >> 2] : block_total(red, k);
     }
     if (tid == 0) {
         double t = 0.0;
-        for (int k = 0; k < 4; ++k) t += (red[0][5 + 4 * k] + red[1][5 + 4 * k]) + (red[2][5 + 4 * k] + red[3][5 + 4 * k]);
-        slot[18] = t;
+        for (int k = 0; k < 4; ++k) t += block_total(red, acc_quad(k, Q_PG));
+        slot[ACC_FG] = t;
     }
-    if (tid < 6) (&mc->tp5)[tid] = wcnt[0][tid] + wcnt[1][tid] + wcnt[2][tid] + wcnt[3][tid];
+    if (tid < 6) (&mc->tp5)[tid] = block_total(wcnt, tid);
     mc->hist[0][tid] = hist[0][tid];
     mc->hist[1][tid] = hist[1][tid];
 }
@@ -726,63 +740,49 @@ __device__ __forceinline__ void metrics_bands(const sm_eval_args& a, const sm_ev
 // the fp64 moments are written as per-chunk partials and summed in a fixed order by K4 (bit-reproducible).
 __global__ __launch_bounds__(EV_THREADS) void eval_metrics_kernel(sm_eval_args a, const int* __restrict__ sel, const float* __restrict__ thr_adapt_all,
                                                                   const GtStats* gs, const int* __restrict__ ytab_all, double* part, MetricCounts* cnt,
-                                                                  int nslot, int band_min) {
+                                                                  int nslot, int walk) {
     __shared__ unsigned hist[2][256];
     __shared__ float thr[256];
-    __shared__ double red[EV_THREADS / 64][EV_NACC];
+    __shared__ double red[EV_NW][EV_NACC];
     const int which = blockIdx.y, b = blockIdx.z, c = blockIdx.x, tid = threadIdx.x;
-    const sm_eval_image im = a.images[b];
-    const int slots = slots_of(im, a.mh, band_min, nslot);
-    if (c >= slots) return;
-    const int npx = im.H * im.W, base = c * EV_CHUNK;
+    ImageCtx ic = image_ctx(a, b, walk, nslot);
+    if (c >= ic.slots) return;
+    ic.scales(a);
     double* slot = part + ((int64_t)(b * 2 + which) * nslot + c) * EV_NACC;
     MetricCounts* mc = cnt + ((int64_t)(b * 2 + which) * nslot + c);
-    const int sel_q = sel[b * 2 + which];
     hist[0][tid] = 0; hist[1][tid] = 0;
     thr[tid] = tid < 255 ? a.thresholds[tid] : INFINITY;
     __syncthreads();
-    const float* __restrict__ m = a.mask_pred + (int64_t)b * a.mask_stride_b + (int64_t)sel_q * a.mh * a.mw;
-    const unsigned char* __restrict__ gt = a.gt + im.gt_off;
-    const float sy = a.scale > 0.f ? 1.0f / a.scale : (float)a.mh / (float)im.H;
-    const float sx = a.scale > 0.f ? 1.0f / a.scale : (float)a.mw / (float)im.W;
-    const float inv_w = 1.0f / (float)im.W;
+    const float* __restrict__ m = a.mask_pred + (int64_t)b * a.mask_stride_b + (int64_t)sel[b * 2 + which] * a.mh * a.mw;
     const float thr_adapt = thr_adapt_all[b * 2 + which];
-    const GtStats g0 = gs[b];
-    // centroid (s_measure.py:13-31): round-half-even of the fp32 quotient of exact integer sums
-    const int X = (int)rintf(SM_DIV((float)g0.sum_gx, (float)g0.sum_g)), Y = (int)rintf(SM_DIV((float)g0.sum_gy, (float)g0.sum_g));
-    if (band_walk(im, a.mh, band_min)) {
-        metrics_bands(a, im, m, gt, ytab_all + b * (a.mh + 1), sy, sx, thr_adapt, X, Y, slots, hist, thr, red, slot, mc);
+    const auto [X, Y] = centroid(gs[b]);
+    if (ic.bands) {
+        metrics_bands(a, ic, m, ytab_all + b * (a.mh + 1), thr_adapt, X, Y, hist, thr, red, slot, mc);
         return;
     }
-
+    const float inv_w = 1.0f / (float)ic.im.W;
     unsigned tp5 = 0, np5 = 0, ng = 0, eq5 = 0, tpa = 0, npa = 0;
     double acc[EV_NACC];
 #pragma unroll
     for (int k = 0; k < EV_NACC; ++k) acc[k] = 0.0;
-    // acc: 1 = sum|p-g|; 2+4k.. = quadrant k {sum p, sum g, sum p^2, sum p g}; 18,19 = fg {sum p, sum p^2};
-    //      20,21 = bg {sum (1-p), sum (1-p)^2}
     for (int k = 0; k < EV_PPT; ++k) {
-        const int idx = base + k * EV_THREADS + tid;
-        const bool valid = idx < npx;
+        const int idx = c * EV_CHUNK + k * EV_THREADS + tid;
+        const bool valid = idx < ic.npx;
         if (__ballot(valid) == 0) break;  // wave-uniform exit: the ballots below need every lane here
         int y = 0, x = 0;
         float p = 0.f;
         unsigned g = 0;
         if (valid) {
-            split_idx(idx, im.W, inv_w, y, x);
-            p = up_sample(m, a.mw, up_index(y, sy, a.mh), up_index(x, sx, a.mw));
-            g = gt[idx] != 0;
+            split_idx(idx, ic.im.W, inv_w, y, x);
+            p = up_sample(m, a.mw, up_index(y, ic.sy, a.mh), up_index(x, ic.sx, a.mw));
+            g = ic.gt[idx] != 0;
         }
         const unsigned b5 = valid && p > 0.5f, ba = valid && p > thr_adapt;
         g = valid ? g : 0;
         tp5 += b5 & g; np5 += b5; ng += g; eq5 += (valid && b5 == g); tpa += ba & g; npa += ba;
         const float gf = (float)g;
-        if (valid) acc[1] += (double)fabsf(p - gf);
-        // number of thresholds strictly below p: start from floor(p*255) and correct (the table is ascending, ~k/255)
-        int lo = (int)(p * 255.0f);
-        lo = lo < 0 ? 0 : (lo > 255 ? 255 : lo);
-        while (lo > 0 && !(thr[lo - 1] < p)) --lo;
-        while (lo < 255 && thr[lo] < p) ++lo;
+        if (valid) acc[ACC_ABS] += (double)fabsf(p - gf);
+        const int lo = thresholds_below(thr, p);
         // LDS histogram split by GT.  (Tried and rejected, measured on the B=64 bench: ballot-counting the saturated bins
         // 0/255 is neutral, peeling one distinct key per round with ballots is 1.5x SLOWER - bilinear ramps put ~50
         // distinct bins into a 64-pixel wave.)
@@ -792,24 +792,26 @@ __global__ __launch_bounds__(EV_THREADS) void eval_metrics_kernel(sm_eval_args a
         const int quad = (y >= Y ? 2 : 0) + (x >= X ? 1 : 0);
 #pragma unroll
         for (int qd = 0; qd < 4; ++qd) {
-            if (quad == qd) { acc[2 + 4 * qd] += pd; acc[3 + 4 * qd] += gd; acc[4 + 4 * qd] += pd * pd; acc[5 + 4 * qd] += pd * gd; }
+            if (quad == qd) {
+                acc[acc_quad(qd, Q_P)] += pd; acc[acc_quad(qd, Q_G)] += gd; acc[acc_quad(qd, Q_PP)] += pd * pd; acc[acc_quad(qd, Q_PG)] += pd * gd;
+            }
         }
-        if (g) { acc[18] += pd; acc[19] += pd * pd; } else { const double o = (double)(1.0f - p); acc[20] += o; acc[21] += o * o; }
+        if (g) { acc[ACC_FG] += pd; acc[ACC_FG2] += pd * pd; } else { const double o = (double)(1.0f - p); acc[ACC_BG] += o; acc[ACC_BG2] += o * o; }
     }
     const int lane = tid & 63, wv = tid >> 6;
 #pragma unroll
-    for (int k = 1; k < EV_NACC; ++k) {
+    for (int k = ACC_ABS; k < EV_NACC; ++k) {
         const double v = wave_total(acc[k]);
         if (lane == 0) red[wv][k] = v;
     }
     tp5 = wave_total(tp5); np5 = wave_total(np5); ng = wave_total(ng); eq5 = wave_total(eq5);
     tpa = wave_total(tpa); npa = wave_total(npa);
-    __shared__ unsigned redc[EV_THREADS / 64][6];
+    __shared__ unsigned redc[EV_NW][6];
     if (lane == 0) { redc[wv][0] = tp5; redc[wv][1] = np5; redc[wv][2] = ng; redc[wv][3] = eq5; redc[wv][4] = tpa; redc[wv][5] = npa; }
     __syncthreads();
     // per-chunk partial counts + histogram, plain stores (K4 sums them): no same-line atomic storms
-    if (tid > 0 && tid < EV_NACC) slot[tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-    if (tid < 6) (&mc->tp5)[tid] = redc[0][tid] + redc[1][tid] + redc[2][tid] + redc[3][tid];
+    if (tid > ACC_SUM && tid < EV_NACC) slot[tid] = block_total(red, tid);
+    if (tid < 6) (&mc->tp5)[tid] = block_total(redc, tid);
     mc->hist[0][tid] = hist[0][tid];
     mc->hist[1][tid] = hist[1][tid];
 }
@@ -817,25 +819,22 @@ __global__ __launch_bounds__(EV_THREADS) void eval_metrics_kernel(sm_eval_args a
 // K4: finalise the 7 metrics of (image, which) with the reference's fp32 operation order; 256 threads: fixed-order
 // partial sums, suffix sums of the histogram and the 255 F-measures in parallel, the scalar tail on thread 0
 __global__ __launch_bounds__(256) void eval_finalize_kernel(sm_eval_args a, const int* __restrict__ sel, const GtStats* gs,
-                                                            const double* part, const MetricCounts* cnt, int nslot, int band_min) {
+                                                            const double* part, const MetricCounts* cnt, int nslot, int walk) {
     __shared__ double accs[EV_NACC];
     __shared__ unsigned s_tp[257], s_np[257];
     __shared__ float s_f[256];
     const int which = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-    const sm_eval_image im = a.images[b];
-    const int npx = im.H * im.W;
-    const int nchunk = slots_of(im, a.mh, band_min, nslot);  // the slots this image's walk wrote
+    const ImageCtx ic = image_ctx(a, b, walk, nslot);
+    const int npx = ic.npx, W = ic.im.W, H = ic.im.H;
     const MetricCounts* mcp = cnt + (int64_t)(b * 2 + which) * nslot;
     __shared__ unsigned h0[256], h1[256], cts[6];
     {
         unsigned s0 = 0, s1 = 0;
-        #pragma unroll 8  // the loads do not depend on the running sum: keep eight in flight (add order unchanged)
-        for (int c = 0; c < nchunk; ++c) { s0 += mcp[c].hist[0][tid]; s1 += mcp[c].hist[1][tid]; }
+        sum_slots(ic.slots, [&](int c) { s0 += mcp[c].hist[0][tid]; s1 += mcp[c].hist[1][tid]; });
         h0[tid] = s0; h1[tid] = s1;
         if (tid < 6) {
             unsigned v = 0;
-            #pragma unroll 8  // the loads do not depend on the running sum: keep eight in flight (add order unchanged)
-            for (int c = 0; c < nchunk; ++c) v += (&mcp[c].tp5)[tid];
+            sum_slots(ic.slots, [&](int c) { v += (&mcp[c].tp5)[tid]; });
             cts[tid] = v;
         }
     }
@@ -843,8 +842,7 @@ __global__ __launch_bounds__(256) void eval_finalize_kernel(sm_eval_args a, cons
     if (tid < EV_NACC) {
         const double* p0 = part + (int64_t)(b * 2 + which) * nslot * EV_NACC + tid;
         double sacc = 0.0;
-        #pragma unroll 8  // the loads do not depend on the running sum: keep eight in flight (add order unchanged)
-        for (int c = 0; c < nchunk; ++c) sacc += p0[(int64_t)c * EV_NACC];  // chunk order: deterministic
+        sum_slots(ic.slots, [&](int c) { sacc += p0[(int64_t)c * EV_NACC]; });
         accs[tid] = sacc;
     }
     // suffix sums: s_tp[k] = sum_{b > k} hist1[b], s_np[k] = sum_{b > k} (hist0 + hist1)[b]   (k = tid)
@@ -869,8 +867,7 @@ __global__ __launch_bounds__(256) void eval_finalize_kernel(sm_eval_args a, cons
     double acc[EV_NACC];
     for (int k = 0; k < EV_NACC; ++k) acc[k] = accs[k];
     const unsigned tp5 = cts[0], np5 = cts[1], eq5 = cts[3], tpa = cts[4], npa = cts[5];
-    const GtStats g0 = gs[b];
-    const int X = (int)rintf(SM_DIV((float)g0.sum_gx, (float)g0.sum_g)), Y = (int)rintf(SM_DIV((float)g0.sum_gy, (float)g0.sum_g));
+    const auto [X, Y] = centroid(gs[b]);
     const int q = sel[b * 2 + which];
 
     float* row = a.rows + (int64_t)b * 16 + which * 7;
@@ -880,10 +877,10 @@ __global__ __launch_bounds__(256) void eval_finalize_kernel(sm_eval_args a, cons
     row[2] = f_measure_from_counts(tp5, np5, ng);                                  // f_measure.py:44-50
     row[3] = s_f[0];                                                               // f_measure.py:52-69
     row[4] = f_measure_from_counts(tpa, npa, ng);                                  // f_measure.py:71-81
-    row[5] = (float)(acc[1] / (double)npx);                                        // mae.py:9
+    row[5] = (float)(acc[ACC_ABS] / (double)npx);                                  // mae.py:9
     {   // S-measure (s_measure.py:105-124)
         const double n1 = (double)ng, n0 = (double)npx - (double)ng;
-        const double sum_p = acc[2] + acc[6] + acc[10] + acc[14];
+        const double sum_p = acc[acc_quad(0, Q_P)] + acc[acc_quad(1, Q_P)] + acc[acc_quad(2, Q_P)] + acc[acc_quad(3, Q_P)];
         float Q;
         if (ng == 0) {
             Q = 1.0f - (float)(sum_p / (double)npx);
@@ -891,16 +888,16 @@ __global__ __launch_bounds__(256) void eval_finalize_kernel(sm_eval_args a, cons
             Q = (float)(sum_p / (double)npx);
         } else {
             const float u = SM_DIV((float)ng, N);
-            const float s_obj = u * object_score(n1, acc[18], acc[19]) + (1.0f - u) * object_score(n0, acc[20], acc[21]);
+            const float s_obj = u * object_score(n1, acc[ACC_FG], acc[ACC_FG2]) + (1.0f - u) * object_score(n0, acc[ACC_BG], acc[ACC_BG2]);
             const float area = (float)npx, Xf = (float)X, Yf = (float)Y;
-            const float w1 = Xf * Yf / area, w2 = ((float)im.W - Xf) * Yf / area, w3 = Xf * ((float)im.H - Yf) / area;
+            const float w1 = Xf * Yf / area, w2 = ((float)W - Xf) * Yf / area, w3 = Xf * ((float)H - Yf) / area;
             const float w4 = 1.0f - w1 - w2 - w3;
-            const double nLT = (double)X * Y, nRT = (double)(im.W - X) * Y, nLB = (double)X * (im.H - Y),
-                         nRB = (double)(im.W - X) * (im.H - Y);
-            const float s_reg = w1 * ssim_quadrant(nLT, acc[2], acc[3], acc[4], acc[5]) +
-                                w2 * ssim_quadrant(nRT, acc[6], acc[7], acc[8], acc[9]) +
-                                w3 * ssim_quadrant(nLB, acc[10], acc[11], acc[12], acc[13]) +
-                                w4 * ssim_quadrant(nRB, acc[14], acc[15], acc[16], acc[17]);
+            const double nLT = (double)X * Y, nRT = (double)(W - X) * Y, nLB = (double)X * (H - Y),
+                         nRB = (double)(W - X) * (H - Y);
+            auto ssim = [&](int k, double n) {
+                return ssim_quadrant(n, acc[acc_quad(k, Q_P)], acc[acc_quad(k, Q_G)], acc[acc_quad(k, Q_PP)], acc[acc_quad(k, Q_PG)]);
+            };
+            const float s_reg = w1 * ssim(0, nLT) + w2 * ssim(1, nRT) + w3 * ssim(2, nLB) + w4 * ssim(3, nRB);
             Q = 0.5f * s_obj + 0.5f * s_reg;
             if (Q < 0.f) Q = 0.f;
         }
@@ -1059,28 +1056,28 @@ extern "C" int sm_evaluate_masks_f32(const sm_eval_args* a, void* stream) {
     // wide for even one row (mw > 480) read their taps from global memory (the kernel's fallback path)
     const size_t row_bytes = (size_t)a->mw * sm::EV_QS * sizeof(float);
     const int lds_rows = (int)(sm::EV_LDS_BYTES / row_bytes) < sm::EV_LDS_ROWS ? (int)(sm::EV_LDS_BYTES / row_bytes) : sm::EV_LDS_ROWS;
-    int band_min = sm::EV_BAND_MIN | sm::EV_UPW << 8;  // the kernels' `walk` argument
+    int walk = sm::walk_pack(sm::EV_BAND_MIN, sm::EV_UPW);
 #ifdef SM_TUNING
     {
         int bm = sm::EV_BAND_MIN, upw = sm::EV_UPW;
         if (const char* e = getenv("SM_EVAL_BAND_MIN")) bm = atoi(e) & 255;  // 0: raster walk for every image
         if (const char* e = getenv("SM_EVAL_UPW")) upw = atoi(e) < 1 ? 1 : (atoi(e) > sm::EV_UPW ? sm::EV_UPW : atoi(e));
-        band_min = bm | upw << 8;
+        walk = sm::walk_pack(bm, upw);
     }
 #endif
     const int red_threads = ((a->nq + 1 + 63) / 64) * 64;  // one thread per query + a spare last lane for the GT sums
     hipLaunchKernelGGL(sm::eval_transpose_kernel, dim3((a->mh * a->mw * sm::EV_QS + 255) / 256, a->B, npass), dim3(256), 0, st, *a, w.maskT, w.ytab);
-    if (a->nq <= 20)  // the band walk's registers sized for the shipped 20 queries (4 waves per SIMD instead of 3)
+    if (a->nq <= 20)  // the band walk's registers sized for the shipped 20 queries (3 waves per SIMD instead of 2)
         hipLaunchKernelGGL(sm::eval_query_kernel<5>, dim3(nslot, a->B, npass), dim3(sm::EV_THREADS), lds_rows * row_bytes, st, *a,
-                           w.maskT, w.ytab, w.qpart, w.gpart, nslot, lds_rows, band_min);
+                           w.maskT, w.ytab, w.qpart, w.gpart, nslot, lds_rows, walk);
     else
         hipLaunchKernelGGL(sm::eval_query_kernel<8>, dim3(nslot, a->B, npass), dim3(sm::EV_THREADS), lds_rows * row_bytes, st, *a,
-                           w.maskT, w.ytab, w.qpart, w.gpart, nslot, lds_rows, band_min);
-    hipLaunchKernelGGL(sm::eval_reduce_query_kernel, dim3(a->B), dim3(red_threads), 0, st, *a, w.qpart, w.gpart, w.qs, w.gs, w.sel, nslot, band_min);
-    hipLaunchKernelGGL(sm::eval_sum_kernel, dim3(nslot, 2, a->B), dim3(sm::EV_THREADS), 0, st, *a, w.sel, w.ytab, w.part, nslot, band_min);
-    hipLaunchKernelGGL(sm::eval_adapt_kernel, dim3(2, a->B), dim3(64), 0, st, *a, w.part, w.thr_adapt, nslot, band_min);
+                           w.maskT, w.ytab, w.qpart, w.gpart, nslot, lds_rows, walk);
+    hipLaunchKernelGGL(sm::eval_reduce_query_kernel, dim3(a->B), dim3(red_threads), 0, st, *a, w.qpart, w.gpart, w.qs, w.gs, w.sel, nslot, walk);
+    hipLaunchKernelGGL(sm::eval_sum_kernel, dim3(nslot, 2, a->B), dim3(sm::EV_THREADS), 0, st, *a, w.sel, w.ytab, w.part, nslot, walk);
+    hipLaunchKernelGGL(sm::eval_adapt_kernel, dim3(2, a->B), dim3(64), 0, st, *a, w.part, w.thr_adapt, nslot, walk);
     hipLaunchKernelGGL(sm::eval_metrics_kernel, dim3(nslot, 2, a->B), dim3(sm::EV_THREADS), 0, st, *a, w.sel, w.thr_adapt, w.gs,
-                       w.ytab, w.part, w.cnt, nslot, band_min);
-    hipLaunchKernelGGL(sm::eval_finalize_kernel, dim3(2, a->B), dim3(256), 0, st, *a, w.sel, w.gs, w.part, w.cnt, nslot, band_min);
+                       w.ytab, w.part, w.cnt, nslot, walk);
+    hipLaunchKernelGGL(sm::eval_finalize_kernel, dim3(2, a->B), dim3(256), 0, st, *a, w.sel, w.gs, w.part, w.cnt, nslot, walk);
     return sm::check_launch("sm_evaluate_masks_f32");
 }
