@@ -2,30 +2,22 @@
 // Same role as attention.hip (vision_transformer.py:122-130, nn.MultiheadAttention core), used when the projections
 // run in the F16X2 mode: Q, K and V arrive already split (the QKV GEMM writes F16X2), so no conversion pass exists.
 //
-//   S^T = K Q^T    : 3 x v_mfma_f32_32x32x16_f16 per 16 head-dims (hi*hi into `main`; hi*lo + lo*hi into `cross`),
-//                    s = (main + cross / 2048) * scale * log2(e); keys on the accumulator rows, the query on the lane:
-//                    softmax is register-local + one cross-half shuffle (as in attention.hip);
+//   S^T = K Q^T    : hat_scores32 (attention_split.h), s = (main + cross / 2048) * scale * log2(e); keys on the accumulator
+//                    rows, the query on the lane: softmax is register-local + one cross-half shuffle (as in attention.hip);
 //   P              : exp2(s - max) split on the fly into hi / lo f16; the accumulator registers 8u..8u+7 of a block ARE
 //                    the B operand of 16-key step u (k order 16u + 8(j>>2) + 4h + (j&3));
 //   O^T = V^T P^T  : V stays row-major [key][d] in LDS exactly as the GEMM wrote it; the transposed A operand comes
 //                    from ds_read_b64_tr_b16 (4 keys x 16 dims per 16-lane group, delivered column-major), whose
 //                    4-row blocks match the permuted k order above.
 //
-// Staging: K and V rows travel as raw 256-B head slices of the F16X2 rows, 64 keys per chunk, by LDS-DMA into a
-// two-deep ring (2 x 32 KiB = two workgroups per CU): the DMA of chunk c+1 flies under the MFMAs of chunk c and costs
-// neither registers nor ds_writes.  An LDS-DMA writes 64 consecutive 16-B pieces, so rows cannot be padded; instead
-// piece p of row r sits at slot p ^ swz(r), swz a bit permutation of r & 15 chosen so that both the b128 key reads
-// (16 rows, one piece index) and the transposed value reads (4 consecutive rows x 4 alternate pieces) hit 64 banks.
-#include "common.h"
-#include <math.h>
+// Staging: the two-deep ring of raw 256-B head slices of attention_split.h, K and V per slot (2 x 32 KiB = two workgroups per CU).
+#include "attention_split.h"
 #include <stdlib.h>
 #include <mutex>
 
 namespace sm {
 
-constexpr int HAT_CH = 64;                  // keys per ring slot
-constexpr int HAT_TENSOR = HAT_CH * 256;    // bytes of K (or V) per slot
-constexpr int HAT_SLOT = 2 * HAT_TENSOR;
+constexpr int HAT_SLOT = 2 * HAT_TENSOR;  // K and V of a chunk
 
 // ds_read_b64_tr_b16 through the compiler's builtin (round 3): hipcc then counts the read in lgkmcnt and may keep several in
 // flight under the MFMAs of the previous group - the inline-asm form needed an s_waitcnt lgkmcnt(0) + sched_barrier before every
@@ -35,8 +27,6 @@ __device__ __forceinline__ f16x4 tr_read4(unsigned addr) {
     const fp16x4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4f16(reinterpret_cast<__attribute__((address_space(3))) fp16x4_t*>((uintptr_t)addr));
     return __builtin_bit_cast(f16x4, v);
 }
-// slot permutation of row r: bits (r0, r1, r2, r3) -> XOR mask bits (0, 3, 1, 2)
-__device__ __forceinline__ int hat_swz(int r) { return (r & 1) | ((r & 2) << 2) | ((r & 4) >> 1) | ((r & 8) >> 1); }
 
 // The keys stream through a ring of two chunk slots.  Staging every chunk at once (at most one workgroup per CU, n_k <= 256)
 // was measured and rejected: batch-1 forward 1.209 -> 1.250 ms, batch 8 1.43 -> 1.48 ms (profiles/r04_attn_all_ab.log) - the
@@ -75,36 +65,15 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_f16x2_kernel(sm_attn_arg
     const char* Kp = reinterpret_cast<const char*>(a.K + b * a.sKb + head * SM_HEAD_DIM);
     const char* Vp = reinterpret_cast<const char*>(a.V + b * a.sVb + head * SM_HEAD_DIM);
 
-    // ring fill: 32 one-KiB pieces per chunk (16 of K, 16 of V; a piece = 4 rows), dealt round-robin over the waves
     const int n_k = a.n_k;
-    const int srow = lane >> 4;                       // row of the piece this lane fetches
     auto issue = [&](int chunk, int slot) {
-#pragma unroll
-        for (int j = 0; j < (32 + NW - 1) / NW; ++j) {
-            const int i = wave + NW * j;
-            if (i < 32) {
-                const int g = i & 15, row = 4 * g + srow;
-                int key = chunk * HAT_CH + row;
-                key = key < n_k ? key : n_k - 1;      // tail rows repeat the last key (finite data; masked below)
-                const int piece = (lane & 15) ^ hat_swz(row);
-                const char* src = (i < 16 ? Kp + (int64_t)key * a.sKr * 4 : Vp + (int64_t)key * a.sVr * 4) + piece * 16;
-                lds_dma16(src, __builtin_amdgcn_readfirstlane(lds0 + slot * HAT_SLOT + (i >> 4) * HAT_TENSOR + g * 1024));
-            }
-        }
+        hat_feed<NW, true>(Kp, a.sKr, Vp, a.sVr, n_k, chunk, lds0 + slot * HAT_SLOT, wave, lane);
     };
     const int nch = (n_k + HAT_CH - 1) / HAT_CH;
     issue(0, 0);
 
-    // Q fragments (B operand of S^T = K Q^T): lane (r,h), 16-dim step t -> k-group 2t+h: hi chunk, lo chunk
-    int qrow = q0 + r;
-    qrow = qrow < a.n_q ? qrow : a.n_q - 1;
-    f16x8 qh[4], ql[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const char* p = Qp + (int64_t)qrow * a.sQr * 4 + (2 * t + h) * 32;
-        qh[t] = *reinterpret_cast<const f16x8*>(p);
-        ql[t] = *reinterpret_cast<const f16x8*>(p + 16);
-    }
+    f16x8 qh[4], ql[4];  // B operand of S^T = K Q^T
+    hat_q_frags(Qp, a.sQr, q0 + r, a.n_q, h, qh, ql);
     const float cs = a.scale * 1.44269504088896340736f;  // scores in log2 units: softmax = one v_exp_f32 per element
 
     f32x16 om[2], oc[2];
@@ -112,14 +81,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_f16x2_kernel(sm_attn_arg
     for (int v = 0; v < 16; ++v) { om[0][v] = 0.f; om[1][v] = 0.f; oc[0][v] = 0.f; oc[1][v] = 0.f; }
     float m_run = -INFINITY, l_run = 0.f;
 
-    // key fragment offsets inside a row (A operand of S^T): pieces 2(2t+h) [hi] and +1 [lo], permuted by the row
-    const int ksw = hat_swz(r & 15);
-    int k_hi[4], k_lo[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        k_hi[t] = ((2 * (2 * t + h)) ^ ksw) * 16;
-        k_lo[t] = ((2 * (2 * t + h) + 1) ^ ksw) * 16;
-    }
+    int k_hi[4], k_lo[4];  // A operand of S^T
+    hat_key_offsets(r, h, k_hi, k_lo);
     // transposed V reads: 16-lane group = (column block cb, key half h); lane 4q+p of a group supplies row q, columns
     // 4p..4p+3 and receives column (lane & 15).  Rows 16u + 4h + q and + 8; pieces 2(4db + 2cb + (p>>1)) [hi], +1 [lo]
     const int cb = (lane >> 4) & 1, li = lane & 15, trq = li >> 2, trp = li & 3;
@@ -128,7 +91,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_f16x2_kernel(sm_attn_arg
     const int vpiece = 4 * cb + 2 * (trp >> 1), vsub = (trp & 1) * 8;
 
     for (int c = 0; c < nch; ++c) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();  // chunk c has landed for every wave, and every wave is done with chunk c-1
         __builtin_amdgcn_sched_barrier(0);
         if (c + 1 < nch) issue(c + 1, (c + 1) & 1);
@@ -139,7 +102,9 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_f16x2_kernel(sm_attn_arg
         const char* Ks = smema + slot * HAT_SLOT;
         const unsigned vs_lds = lds0 + slot * HAT_SLOT + HAT_TENSOR;
 
-        // raw scores t = main + cross / 2048 (the softmax scale cs > 0 is applied inside the exponent's fma)
+        // raw scores t = main + cross / 2048 (the softmax scale cs > 0 is applied inside the exponent's fma).  The block below is
+        // hat_scores32<false> + hat_mask_tail of attention_split.h, kept spelled out here: called as functions they cost this kernel
+        // 0.5 % of an eager batch-1 forward (profiles/forward_pieces_ab.log, bisect), same bits either way.
         f32x16 s[2];
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
@@ -221,15 +186,13 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_f16x2_kernel(sm_attn_arg
                         f16x8 vh, vl;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) { vh[e] = h1[e]; vh[4 + e] = h2[e]; vl[e] = l1[e]; vl[4 + e] = l2[e]; }
-                        om[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, ph[kb][u], om[db], 0, 0, 0);
-                        oc[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, pl[kb][u], oc[db], 0, 0, 0);
-                        oc[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, ph[kb][u], oc[db], 0, 0, 0);
+                        f16x2_step32(vh, vl, ph[kb][u], pl[kb][u], om[db], oc[db]);
                     }
                 }
             }
         }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no DMA may outlive the workgroup's LDS allocation
+    wait_vmcnt<0>();  // no DMA may outlive the workgroup's LDS allocation
     if (!active) return;
 
     const float l = halves_sum(l_run);
@@ -243,8 +206,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_f16x2_kernel(sm_attn_arg
                 float x[4], y[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    x[e] = (om[db][4 * g + e] + oc[db][4 * g + e] * (1.0f / 2048.0f)) * inv;
-                    y[e] = (om[db][4 * g + 4 + e] + oc[db][4 * g + 4 + e] * (1.0f / 2048.0f)) * inv;
+                    x[e] = f16x2_join(om[db][4 * g + e], oc[db][4 * g + e]) * inv;
+                    y[e] = f16x2_join(om[db][4 * g + 4 + e], oc[db][4 * g + 4 + e]) * inv;
                 }
                 if (a.out_f16x2) {  // lanes l / l^32 trade halves: each writes one whole 32-B F16X2 group
                     pair_groups(x, y);
@@ -285,8 +248,6 @@ extern "C" int sm_attention_f16x2(const sm_attn_args* a, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const int nqb = (a->n_q + 31) / 32;
     const int groups = (nqb + 3) / 4;
-    const int nw = (nqb + groups - 1) / groups;
     // always four waves: those past the last query block (decoder: a single block) issue their share of the ring's DMA
-    (void)nw;
     return sm::launch_attn_h(*a, groups, st);
 }

@@ -1,7 +1,7 @@
 // P = softmax(scale * Q K^T) per (batch, head), head_dim 64, WRITTEN OUT: the post-softmax `attn` of Attention.forward
 // (vision_transformer.py:122-123), which VisionTransformer.get_last_selfattention returns (:307-314).  Q and K arrive in the
-// F16X2 split format (as the projection GEMMs write them); products are the three-MFMA split form of attention_f16x2.hip:
-// (hi*hi + (hi*lo + lo*hi) / 2048) * scale * log2(e), then exp2.
+// F16X2 split format (as the projection GEMMs write them); products are the three-MFMA split form of attention_split.h, shared
+// with attention_f16x2.hip: (hi*hi + (hi*lo + lo*hi) / 2048) * scale * log2(e), then exp2.
 //
 // Every key's NORMALISED probability is needed, not a running sum, so the keys are walked twice (a score tile held resident
 // would be 16 registers per 32 keys: 112 at 197 tokens, 400 at 785 - it does not fit the shapes the forward accepts, and one
@@ -16,23 +16,16 @@
 // the batch - so any launch that contains a row writes the same bits for it.  Keys past n_k are masked to -inf in pass 1
 // (exp2 gives exactly 0) and never stored in pass 2.  No atomics.
 //
-// Staging: as attention_f16x2.hip - 64 keys per chunk as raw 256-B head slices by LDS-DMA into a two-deep ring (2 x 16 KiB),
-// piece p of row r in slot p ^ swz(r); the ring simply runs through the 2 * chunks iterations of both passes.  Four waves
-// of 32 queries share a ring; waves past the last query block only help with the staging.
-#include "common.h"
-#include <math.h>
+// Staging: the two-deep ring of attention_split.h, K alone (2 x 16 KiB); it simply runs through the 2 * chunks iterations of
+// both passes.  Four waves of 32 queries share a ring; waves past the last query block only help with the staging.
+#include "attention_split.h"
 
 namespace sm {
 
-constexpr int AP_CH = 64;              // keys per ring slot
-constexpr int AP_SLOT = AP_CH * 256;   // bytes of K per slot
-constexpr int AP_NW = 4;               // waves (32 queries each) per workgroup
-
-// slot permutation of row r (attention_f16x2.hip): bits (r0, r1, r2, r3) -> XOR mask bits (0, 3, 1, 2)
-__device__ __forceinline__ int ap_swz(int r) { return (r & 1) | ((r & 2) << 2) | ((r & 4) >> 1) | ((r & 8) >> 1); }
+constexpr int AP_NW = 4;  // waves (32 queries each) per workgroup
 
 __global__ __launch_bounds__(AP_NW * 64, 2) void attention_probs_f16x2_kernel(sm_attn_probs_args a, int groups) {
-    __shared__ __attribute__((aligned(16))) char smem[2 * AP_SLOT];
+    __shared__ __attribute__((aligned(16))) char smem[2 * HAT_TENSOR];
     const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -49,41 +42,29 @@ __global__ __launch_bounds__(AP_NW * 64, 2) void attention_probs_f16x2_kernel(sm
     const char* Kp = reinterpret_cast<const char*>(a.K + b * a.sKb + head * SM_HEAD_DIM);
     float* Pb = a.P + b * a.sPb + ((int64_t)head * a.nq - a.q0) * a.n_k;  // row i of the image's head at Pb + i * n_k
 
-    // ring fill: 16 one-KiB pieces per chunk (a piece = 4 rows), four per wave
+    // ring fill: 16 one-KiB pieces per chunk (a piece = 4 rows), four per wave.  hat_feed<AP_NW, false> of attention_split.h spelled
+    // out: through the shared function this kernel wrote 1.5 % fewer GB/s (profiles/forward_pieces_ab.log, bisect), same bits.
     const int n_k = a.n_k;
     const int srow = lane >> 4;
     auto issue = [&](int chunk, int slot) {
 #pragma unroll
         for (int j = 0; j < 16 / AP_NW; ++j) {
             const int g = wave + AP_NW * j, row = 4 * g + srow;
-            int key = chunk * AP_CH + row;
+            int key = chunk * HAT_CH + row;
             key = key < n_k ? key : n_k - 1;  // tail rows repeat the last key (finite data; masked / not stored below)
-            const int piece = (lane & 15) ^ ap_swz(row);
-            lds_dma16(Kp + (int64_t)key * a.sKr * 4 + piece * 16, __builtin_amdgcn_readfirstlane(lds0 + slot * AP_SLOT + g * 1024));
+            const int piece = (lane & 15) ^ hat_swz(row);
+            lds_dma16(Kp + (int64_t)key * a.sKr * 4 + piece * 16, __builtin_amdgcn_readfirstlane(lds0 + slot * HAT_TENSOR + g * 1024));
         }
     };
-    const int nch = (n_k + AP_CH - 1) / AP_CH, nit = 2 * nch;
+    const int nch = (n_k + HAT_CH - 1) / HAT_CH, nit = 2 * nch;
     issue(0, 0);
 
-    // Q fragments: lane (r, h), 16-dim step t -> k-group 2t + h: hi chunk, lo chunk.  Rows past the range repeat its last row.
-    int qrow = qw + r;
-    qrow = qrow < q_end ? qrow : q_end - 1;
     f16x8 qh[4], ql[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const char* p = Qp + (int64_t)qrow * a.sQr * 4 + (2 * t + h) * 32;
-        qh[t] = *reinterpret_cast<const f16x8*>(p);
-        ql[t] = *reinterpret_cast<const f16x8*>(p + 16);
-    }
+    hat_q_frags(Qp, a.sQr, qw + r, q_end, h, qh, ql);
     const float cs = a.scale * 1.44269504088896340736f;  // scores in log2 units
 
-    const int ksw = ap_swz(r & 15);
     int k_hi[4], k_lo[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        k_hi[t] = ((2 * (2 * t + h)) ^ ksw) * 16;
-        k_lo[t] = ((2 * (2 * t + h) + 1) ^ ksw) * 16;
-    }
+    hat_key_offsets(r, h, k_hi, k_lo);
 
     float m_run = -INFINITY, l_run = 0.f;  // pass 1: this lane's query; l_run over the rows of this lane's half
     float rm[16], ri[16];                  // pass 2: -max * cs and 1 / sum of query row acc_row(v, h)
@@ -91,7 +72,7 @@ __global__ __launch_bounds__(AP_NW * 64, 2) void attention_probs_f16x2_kernel(sm
     for (int v = 0; v < 16; ++v) { rm[v] = 0.f; ri[v] = 0.f; }
 
     for (int it = 0; it < nit; ++it) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();  // the chunk of this iteration has landed for every wave; every wave is done with the previous one
         __builtin_amdgcn_sched_barrier(0);
         if (it + 1 < nit) issue(it + 1 < nch ? it + 1 : it + 1 - nch, (it + 1) & 1);
@@ -107,37 +88,16 @@ __global__ __launch_bounds__(AP_NW * 64, 2) void attention_probs_f16x2_kernel(sm
                 ri[v] = __shfl(inv, acc_row(v, h), 64);
             }
         }
-        const int ck = min(AP_CH, n_k - c * AP_CH);
-        const char* Ks = smem + (it & 1) * AP_SLOT;
+        const int ck = min(HAT_CH, n_k - c * HAT_CH);
+        const char* Ks = smem + (it & 1) * HAT_TENSOR;
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
             if (kb * 32 >= ck) break;
             const char* kr = Ks + (kb * 32 + r) * 256;
-            f16x8 kh[4], kl[4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                kh[t] = *reinterpret_cast<const f16x8*>(kr + k_hi[t]);
-                kl[t] = *reinterpret_cast<const f16x8*>(kr + k_lo[t]);
-            }
-            f32x16 mn, cr;
-#pragma unroll
-            for (int v = 0; v < 16; ++v) { mn[v] = 0.f; cr[v] = 0.f; }
             if (!second) {
-                // S^T block: register v of lane (r, h) = key kb*32 + acc_row(v, h), query qw + r
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    mn = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh[t], qh[t], mn, 0, 0, 0);
-                    cr = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh[t], ql[t], cr, 0, 0, 0);
-                    cr = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl[t], qh[t], cr, 0, 0, 0);
-                }
-                float s[16];
-#pragma unroll
-                for (int v = 0; v < 16; ++v) s[v] = fmaf(cr[v], 1.0f / 2048.0f, mn[v]);
-                if ((kb + 1) * 32 > ck) {  // only the last chunk's last block has keys past n_k (wave-uniform branch)
-#pragma unroll
-                    for (int v = 0; v < 16; ++v)
-                        if (kb * 32 + acc_row(v, h) >= ck) s[v] = -INFINITY;
-                }
+                f32x16 s;
+                hat_scores32<false>(kr, k_hi, k_lo, qh, ql, s);
+                hat_mask_tail(s, kb, ck, h);
                 float bmax = s[0];
 #pragma unroll
                 for (int v = 1; v < 16; ++v) bmax = fmaxf(bmax, s[v]);
@@ -151,26 +111,20 @@ __global__ __launch_bounds__(AP_NW * 64, 2) void attention_probs_f16x2_kernel(sm
                 l_run = l_run * alpha + psum;
                 m_run = m_new;
             } else {
-                // S block: register v of lane (r, h) = query qw + acc_row(v, h), key kb*32 + r
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    mn = __builtin_amdgcn_mfma_f32_32x32x16_f16(qh[t], kh[t], mn, 0, 0, 0);
-                    cr = __builtin_amdgcn_mfma_f32_32x32x16_f16(ql[t], kh[t], cr, 0, 0, 0);
-                    cr = __builtin_amdgcn_mfma_f32_32x32x16_f16(qh[t], kl[t], cr, 0, 0, 0);
-                }
-                const int key = c * AP_CH + kb * 32 + r;
+                f32x16 s;
+                hat_scores32<true>(kr, k_hi, k_lo, qh, ql, s);
+                const int key = c * HAT_CH + kb * 32 + r;
                 if (key < n_k) {
 #pragma unroll
                     for (int v = 0; v < 16; ++v) {
                         const int qi = qw + acc_row(v, h);
-                        const float s = fmaf(cr[v], 1.0f / 2048.0f, mn[v]);
-                        if (qi < q_end) Pb[(int64_t)qi * n_k + key] = __builtin_amdgcn_exp2f(fmaf(s, cs, rm[v])) * ri[v];
+                        if (qi < q_end) Pb[(int64_t)qi * n_k + key] = __builtin_amdgcn_exp2f(fmaf(s[v], cs, rm[v])) * ri[v];
                     }
                 }
             }
         }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no DMA may outlive the workgroup's LDS allocation
+    wait_vmcnt<0>();  // no DMA may outlive the workgroup's LDS allocation
 }
 
 }  // namespace sm

@@ -52,6 +52,12 @@ __device__ __forceinline__ void lds_dma16(const void* gsrc, unsigned lds_off) {
         : "memory");
 }
 
+// the retire point of those DMAs: at most N of this wave's vector-memory operations still in flight
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
 // The same with a wave-uniform 64-bit base (SGPR pair) + a per-lane 32-bit byte offset: half the address registers of the
 // pointer form, and a K loop advances the scalar base instead of 64 per-lane pointers
 __device__ __forceinline__ void lds_dma16_s(const void* sbase, unsigned voff, unsigned lds_off) {

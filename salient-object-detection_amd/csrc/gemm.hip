@@ -9,13 +9,13 @@
 //     (global_load_lds_dwordx4: no staging VGPRs, no ds_write), NST buffers deep, retired with a COUNTED
 //     s_waitcnt vmcnt(N) + one raw s_barrier per K-tile (never vmcnt(0) in the loop when NST > 2);
 //   * the LDS image is linear (an LDS-DMA wave-instruction writes 64 lanes x 16 B contiguously), so bank
-//     conflicts are removed by XOR-swizzling the 16-B chunk index with (row>>1)&7 on the per-lane SOURCE
+//     conflicts are removed by XOR-swizzling the 16-B chunk index with ring32_swz(row) on the per-lane SOURCE
 //     address and again on the ds_read_b128 fragment reads (conflict-free for all four 16-lane groups);
 //   * k-permutation: within each 8-wide k group lane-half h owns k = 4h..4h+3, so one ds_read_b128 per operand
 //     feeds 4 consecutive MFMA steps (A and W use the same permutation: the set of products is unchanged);
 //   * two-level summation: the MFMA chain runs over 128 k, then is folded into a second accumulator with VALU
 //     adds (a single 1536-long chain measured 5x torch-CPU's error against fp64).
-#include "common.h"
+#include "forward_pieces.h"
 #include <mutex>
 #include <type_traits>
 
@@ -25,24 +25,6 @@ constexpr int BK = 32;
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
-
-// One LDS-DMA wave-instruction: 64 lanes x 16 B from per-lane global addresses to LDS [lds_off, lds_off + 1 KiB).
-// Issued from inline asm on purpose: hipcc does not count asm VMEM ops, so it cannot insert its conservative
-// `s_waitcnt vmcnt(0)` in front of the next ds_read (it did with the builtin, serialising DMA and MFMA); the
-// retire points are the explicit counted waits below.  M0 (the LDS base) is compiler-reserved: save/restore it.
-__device__ __forceinline__ void dma16(const float* gsrc, unsigned lds_off) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_off)
-        : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 template <int EPI>
 __device__ __forceinline__ void store_out(const sm_gemm_args& g, float* C, int64_t bz, int m, int n, float val) {
@@ -76,15 +58,8 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(sm_gemm_args g) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
     const int r = lane & 31, h = lane >> 5;
-    // XCD-aware tile order (1-D grid): workgroups are dealt round-robin over the 8 XCDs (id % 8 labels the XCD, each
-    // with a private 4 MiB L2).  Give every XCD a CONTIGUOUS range of logical tiles (m-tile major, n-tile minor) so all
-    // n-tiles of an A row-panel run on one XCD and re-read it from that L2 instead of the Infinity Cache.
-    int tile_id = blockIdx.x;
+    const int tile_id = xcd_tile_order(blockIdx.x, gridDim.x);
     const int ntn = (g.N + BN - 1) / BN;
-    {
-        const int nwg = gridDim.x, q8 = nwg >> 3, r8 = nwg & 7, xcd = tile_id & 7, slot = tile_id >> 3;
-        tile_id = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
-    }
     const int n0 = (tile_id % ntn) * BN, m0 = (tile_id / ntn) * BM;
     const int M = g.M, N = g.N;
     // split-K: blockIdx.z is the K-slice (batch == 1); otherwise it is the batch index
@@ -101,7 +76,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(sm_gemm_args g) {
 #pragma unroll
     for (int i = 0; i < A_INST; ++i) {
         const int row = (wave * A_INST + i) * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ ((row >> 1) & 7);
+        const int c = (lane & 7) ^ ring32_swz(row);
         int gm = m0 + row;
         gm = gm < M ? gm : M - 1;
         a_src[i] = A + (int64_t)gm * g.lda + c * 4;
@@ -109,7 +84,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(sm_gemm_args g) {
 #pragma unroll
     for (int i = 0; i < W_INST; ++i) {
         const int row = (wave * W_INST + i) * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ ((row >> 1) & 7);
+        const int c = (lane & 7) ^ ring32_swz(row);
         int gn = n0 + row;
         gn = gn < N ? gn : N - 1;
         w_src[i] = W + (int64_t)gn * g.ldw + c * 4;
@@ -119,13 +94,13 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(sm_gemm_args g) {
         const unsigned sa = __builtin_amdgcn_readfirstlane(lds_base + (stage * STAGE + wave * A_INST * 8 * BK) * 4);
         const unsigned sw = __builtin_amdgcn_readfirstlane(lds_base + (stage * STAGE + BM * BK + wave * W_INST * 8 * BK) * 4);
 #pragma unroll
-        for (int i = 0; i < A_INST; ++i) dma16(a_src[i] + kt * BK, sa + i * 8 * BK * 4);
+        for (int i = 0; i < A_INST; ++i) lds_dma16(a_src[i] + kt * BK, sa + i * 8 * BK * 4);
 #pragma unroll
-        for (int i = 0; i < W_INST; ++i) dma16(w_src[i] + kt * BK, sw + i * 8 * BK * 4);
+        for (int i = 0; i < W_INST; ++i) lds_dma16(w_src[i] + kt * BK, sw + i * 8 * BK * 4);
     };
 
     // ---- fragment read offsets (floats): row r of a 32-row block, chunk (2kb+h) ^ ((r>>1)&7) -----------------------
-    const int swz = (r >> 1) & 7;
+    const int swz = ring32_swz(r);
     int koff[4];
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb) koff[kb] = ((2 * kb + h) ^ swz) * 4;

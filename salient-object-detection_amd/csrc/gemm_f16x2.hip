@@ -21,7 +21,7 @@
 // ds_read_b128 per MFMA), and this kernel's LDS-read + MFMA loop alone runs at that rate; what the kernel adds on top
 // - LDS-DMA issue, prologue latency, the epilogue's HBM writes - overlaps only across workgroups, so occupancy
 // (__launch_bounds__) and the tile's DMA bytes per FLOP decide the default shapes.
-#include "common.h"
+#include "forward_pieces.h"
 #include <type_traits>
 #include <mutex>
 #include <stdlib.h>
@@ -29,12 +29,6 @@
 namespace sm {
 
 constexpr int HBK = 32;  // k per pipeline stage (two 16-deep MFMA steps)
-
-__device__ __forceinline__ void dma16h(const void* gsrc, unsigned lds_off) { lds_dma16(gsrc, lds_off); }  // common.h
-template <int N>
-__device__ __forceinline__ void wait_vmcnt_h() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // NWM x NWN waves per workgroup, each owning a (BM/NWM) x (BN/NWN) block of the tile as TM x TN 32x32 accumulators.
 // The kernel is fed from L2 at a roughly fixed rate per CU (~50 GB/s measured), so what a tile shape buys is MACs per
@@ -62,15 +56,8 @@ __global__ __launch_bounds__(NWM * NWN * 64, MINB) void gemm_f16x2_kernel(sm_gem
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / NWN, wn = wave % NWN;
     const int r = lane & 31, h = lane >> 5;
-    // XCD-aware tile order (1-D grid): workgroups are dealt round-robin over the 8 XCDs (id % 8 labels the XCD, each
-    // with a private 4 MiB L2).  Give every XCD a CONTIGUOUS range of logical tiles (m-tile major, n-tile minor) so all
-    // n-tiles of an A row-panel run on one XCD and re-read it from that L2 instead of the Infinity Cache.
-    int tile_id = blockIdx.x;
+    const int tile_id = xcd_tile_order(blockIdx.x, gridDim.x);
     const int ntn = (g.N + BN - 1) / BN;
-    {
-        const int nwg = gridDim.x, q8 = nwg >> 3, r8 = nwg & 7, xcd = tile_id & 7, slot = tile_id >> 3;
-        tile_id = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
-    }
     const int n0 = (tile_id % ntn) * BN, m0 = (tile_id / ntn) * BM;
     const int M = g.M, N = g.N;
     const int split = g.split_k > 1 ? g.split_k : 1;
@@ -86,7 +73,7 @@ __global__ __launch_bounds__(NWM * NWN * 64, MINB) void gemm_f16x2_kernel(sm_gem
 #pragma unroll
     for (int i = 0; i < A_INST; ++i) {
         const int row = (wave * A_INST + i) * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ ((row >> 1) & 7);
+        const int c = (lane & 7) ^ ring32_swz(row);
         int gm = m0 + row;
         gm = gm < M ? gm : M - 1;
         a_src[i] = A + ((int64_t)gm * g.lda) * 4 + c * 16;
@@ -94,7 +81,7 @@ __global__ __launch_bounds__(NWM * NWN * 64, MINB) void gemm_f16x2_kernel(sm_gem
 #pragma unroll
     for (int i = 0; i < W_INST; ++i) {
         const int row = (wave * W_INST + i) * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ ((row >> 1) & 7);
+        const int c = (lane & 7) ^ ring32_swz(row);
         int gn = n0 + row;
         gn = gn < N ? gn : N - 1;
         w_src[i] = W + ((int64_t)gn * g.ldw) * 4 + c * 16;
@@ -103,12 +90,12 @@ __global__ __launch_bounds__(NWM * NWN * 64, MINB) void gemm_f16x2_kernel(sm_gem
     auto issue_a = [&](int kt, int slot) {
         const unsigned sa = __builtin_amdgcn_readfirstlane(lds_base + slot * A_STAGE + wave * A_INST * 1024);
 #pragma unroll
-        for (int i = 0; i < A_INST; ++i) dma16h(a_src[i] + kt * 128, sa + i * 1024);
+        for (int i = 0; i < A_INST; ++i) lds_dma16(a_src[i] + kt * 128, sa + i * 1024);
     };
     auto issue_w = [&](int kt, int slot) {
         const unsigned sw = __builtin_amdgcn_readfirstlane(lds_base + W_RING + slot * W_STAGE + wave * W_INST * 1024);
 #pragma unroll
-        for (int i = 0; i < W_INST; ++i) dma16h(w_src[i] + kt * 128, sw + i * 1024);
+        for (int i = 0; i < W_INST; ++i) lds_dma16(w_src[i] + kt * 128, sw + i * 1024);
     };
     // one pipeline step: the W tile NST-1 ahead, then the A tile NSTA-1 ahead (this order is what the counted wait below
     // relies on); tiles past the end re-fetch the last one so that every step issues the same number of pieces
@@ -119,7 +106,7 @@ __global__ __launch_bounds__(NWM * NWN * 64, MINB) void gemm_f16x2_kernel(sm_gem
     };
 
     // fragment byte offsets inside a 128-B row: k16-step s, lane half h -> k-group 2s+h -> chunks 2(2s+h) [hi], +1 [lo]
-    const int swz = (r >> 1) & 7;
+    const int swz = ring32_swz(r);
     int off_hi[2], off_lo[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -143,7 +130,7 @@ __global__ __launch_bounds__(NWM * NWN * 64, MINB) void gemm_f16x2_kernel(sm_gem
     for (int kt = 0; kt < nk; ++kt) {
         // tiles kt of both rings have landed; what may still fly was issued after the later of the two: AX = 0 the
         // NST-2 steps since; AX = 1 the A tile issued right behind W(kt) plus those steps
-        wait_vmcnt_h<(NST - 2) * NI + AX * A_INST>();
+        wait_vmcnt<(NST - 2) * NI + AX * A_INST>();
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         issue_step(kt);
@@ -172,14 +159,12 @@ __global__ __launch_bounds__(NWM * NWN * 64, MINB) void gemm_f16x2_kernel(sm_gem
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
                     // D[n][m]: weights are the MFMA A operand (rows = n), activations the B operand (cols = m)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[s][j], ah[s][i], acc[i][j], 0, 0, 0);
-                    crs[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[s][j], al[s][i], crs[i][j], 0, 0, 0);
-                    crs[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[s][j], ah[s][i], crs[i][j], 0, 0, 0);
+                    f16x2_step32(wh[s][j], wl[s][j], ah[s][i], al[s][i], acc[i][j], crs[i][j]);
                 }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
-    wait_vmcnt_h<0>();
+    wait_vmcnt<0>();
 
     float* C = g.C + (split > 1 ? (int64_t)blockIdx.z : bz) * g.strideC;
     const bool out_split = g.patch_n < 0;  // out-format flag travels in the sign of patch_n for non-PATCH epilogues
@@ -201,9 +186,9 @@ __global__ __launch_bounds__(NWM * NWN * 64, MINB) void gemm_f16x2_kernel(sm_gem
     if constexpr (BN == SM_EMBED) {
         // ---- residual + LayerNorm epilogue (SM_EPI_RESIDUAL_LN): the tile spans whole rows (N = BN = 384), so the
         // pre-norm of the NEXT block runs here instead of in its own launch.  All waves stage their fp32 blocks
-        // (A W^T + bias) row-major in the idle ring, then every 16 lanes take one row exactly as layernorm384_kernel
-        // does (three 8-element groups per lane, two-pass variance, 4-step butterflies): x = R + value goes to C
-        // (fp32 residual stream), LayerNorm(x) to C2 in F16X2 - bit-identical to the unfused pair of launches.
+        // (A W^T + bias) row-major in the idle ring, then every 16 lanes take one row through the ln384_* steps that
+        // layernorm384_kernel runs (forward_pieces.h): x = R + value goes to C (fp32 residual stream), LayerNorm(x)
+        // to C2 in F16X2 - bit-identical to the unfused pair of launches.
         if (g.epilogue == SM_EPI_RESIDUAL_LN) {
             constexpr int LNLD = BN * 4 + 16;
             static_assert(BM * LNLD <= RING_BYTES, "row staging must fit in the ring");
@@ -217,7 +202,7 @@ __global__ __launch_bounds__(NWM * NWN * 64, MINB) void gemm_f16x2_kernel(sm_gem
                     float* vp = &val.x;
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
-                        vp[e] = (acc[0][j][4 * q + e] + crs[0][j][4 * q + e] * (1.0f / 2048.0f)) + (g.bias ? g.bias[nl + e] : 0.f);
+                        vp[e] = f16x2_join(acc[0][j][4 * q + e], crs[0][j][4 * q + e]) + (g.bias ? g.bias[nl + e] : 0.f);
                     *reinterpret_cast<float4*>(smemh + (wm * WTM + r) * LNLD + nl * 4) = val;
                 }
             __syncthreads();
@@ -251,36 +236,14 @@ __global__ __launch_bounds__(NWM * NWN * 64, MINB) void gemm_f16x2_kernel(sm_gem
                         *reinterpret_cast<float4*>(cr + k + 4) = make_float4(v[i][4], v[i][5], v[i][6], v[i][7]);
                     }
                 }
-                float sum = 0.f;
-#pragma unroll
-                for (int i = 0; i < 3; ++i) sum += ((v[i][0] + v[i][1]) + (v[i][2] + v[i][3])) + ((v[i][4] + v[i][5]) + (v[i][6] + v[i][7]));
-#pragma unroll
-                for (int o = 8; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 16);
-                const float mean = sum * (1.0f / 384.0f);
-                float qv = 0.f;
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        v[i][e] -= mean;
-                        qv += v[i][e] * v[i][e];
-                    }
-#pragma unroll
-                for (int o = 8; o > 0; o >>= 1) qv += __shfl_xor(qv, o, 16);
-                const float rstd = 1.0f / sqrtf(qv * (1.0f / 384.0f) + g.ln_eps);
+                const float rstd = ln384_center(v, g.ln_eps);
                 if (live) {
                     float* yr = (g.C2 + bz * g.strideC) + (int64_t)m * g.ldc;
 #pragma unroll
                     for (int i = 0; i < 3; ++i) {
                         const int k = (l16 + 16 * i) * 8;
                         float o[8];
-#pragma unroll
-                        for (int hh = 0; hh < 2; ++hh) {
-                            const float4 gm = *reinterpret_cast<const float4*>(g.ln_gamma + k + 4 * hh);
-                            const float4 bt = *reinterpret_cast<const float4*>(g.ln_beta + k + 4 * hh);
-                            o[4 * hh + 0] = v[i][4 * hh + 0] * rstd * gm.x + bt.x; o[4 * hh + 1] = v[i][4 * hh + 1] * rstd * gm.y + bt.y;
-                            o[4 * hh + 2] = v[i][4 * hh + 2] * rstd * gm.z + bt.z; o[4 * hh + 3] = v[i][4 * hh + 3] * rstd * gm.w + bt.w;
-                        }
+                        ln384_affine(v[i], rstd, g.ln_gamma, g.ln_beta, k, o);
                         const float (&o0)[4] = *reinterpret_cast<const float (*)[4]>(&o[0]);
                         const float (&o1)[4] = *reinterpret_cast<const float (*)[4]>(&o[4]);
                         store_f16x2_8(yr, k, o0, o1);
@@ -307,8 +270,8 @@ __global__ __launch_bounds__(NWM * NWN * 64, MINB) void gemm_f16x2_kernel(sm_gem
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             const int nx = n0 + wn * WTN + j * 32 + 8 * q + 4 * h + e, ny = nx + 8;
-                            x[e] = (acc[i][j][4 * q + e] + crs[i][j][4 * q + e] * (1.0f / 2048.0f)) + ((g.bias && nx < N) ? g.bias[nx] : 0.f);
-                            y[e] = (acc[i][j][4 * q + 4 + e] + crs[i][j][4 * q + 4 + e] * (1.0f / 2048.0f)) + ((g.bias && ny < N) ? g.bias[ny] : 0.f);
+                            x[e] = f16x2_join(acc[i][j][4 * q + e], crs[i][j][4 * q + e]) + ((g.bias && nx < N) ? g.bias[nx] : 0.f);
+                            y[e] = f16x2_join(acc[i][j][4 * q + 4 + e], crs[i][j][4 * q + 4 + e]) + ((g.bias && ny < N) ? g.bias[ny] : 0.f);
                             if constexpr (EPI == SM_EPI_RELU) {
                                 x[e] = fmaxf(x[e], 0.f);
                                 y[e] = fmaxf(y[e], 0.f);
@@ -327,7 +290,7 @@ __global__ __launch_bounds__(NWM * NWN * 64, MINB) void gemm_f16x2_kernel(sm_gem
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             const float b = (g.bias && n < N) ? g.bias[n + e] : 0.f;
-                            float t = (acc[i][j][4 * q + e] + crs[i][j][4 * q + e] * (1.0f / 2048.0f)) + b;
+                            float t = f16x2_join(acc[i][j][4 * q + e], crs[i][j][4 * q + e]) + b;
                             if constexpr (EPI == SM_EPI_GELU) t = 0.5f * t * (1.0f + fast_erff(t * 0.70710678118654752440f));
                             else if constexpr (EPI == SM_EPI_RELU) t = fmaxf(t, 0.f);
                             vp[e] = t;

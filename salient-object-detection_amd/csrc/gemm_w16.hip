@@ -15,20 +15,15 @@
 // The epilogue multiplies the accumulator by 2^-s (exact) before the bias.  Half the accumulator registers buy a
 // 256 x 128 tile per workgroup: 3/4 of the staged bytes per MFMA of the 128 x 128 tile at the same occupancy.
 //
-// Everything else follows gemm_f16x2.hip: LDS-DMA ring with counted vmcnt + one raw barrier per K-tile, XOR swizzle on
+// Everything else is the structure of gemm_f16x2.hip: LDS-DMA ring with counted vmcnt + one raw barrier per K-tile, XOR swizzle on
 // the DMA source address and the fragment reads, weights as the MFMA A operand (a lane owns one output row), epilogue
-// turned through the idle ring so global accesses are contiguous row segments, XCD-aware tile order.
-#include "common.h"
+// turned through the idle ring so global accesses are contiguous row segments, XCD-aware tile order (forward_pieces.h).
+#include "forward_pieces.h"
 #include <type_traits>
 #include <mutex>
 #include <stdlib.h>
 
 namespace sm {
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt_w() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // ---- 16x16x32 MFMA kernel ---------------------------------------------------------------------------------------------------
 // The GEMM runs on v_mfma_f32_16x16x32_f16.  Why: with three batches in flight the chip sits at its power limit, and in
@@ -94,12 +89,8 @@ __global__ __launch_bounds__(NWM * NWN * 64, WPS) void gemm_w16m16_kernel(sm_gem
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / NWN, wn = wave % NWN;
     const int r16 = lane & 15, kg = lane >> 4;
-    int tile_id = blockIdx.x;
+    const int tile_id = xcd_tile_order(blockIdx.x, gridDim.x);
     const int ntn = (g.N + BN - 1) / BN;
-    {
-        const int nwg = gridDim.x, q8 = nwg >> 3, r8 = nwg & 7, xcd = tile_id & 7, slot = tile_id >> 3;
-        tile_id = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
-    }
     const int n0 = (tile_id % ntn) * BN, m0 = (tile_id / ntn) * BM;
     const int M = g.M, N = g.N;
     const int split = (!PLAIN && g.split_k > 1) ? g.split_k : 1;
@@ -158,32 +149,17 @@ __global__ __launch_bounds__(NWM * NWN * 64, WPS) void gemm_w16m16_kernel(sm_gem
     for (int v = -(NST - 1); v < 0; ++v) issue_step(v);
     // LayerNorm folded into this GEMM (g.ln_stats): A holds the RAW residual stream x (F16X2), W the weight times the norm's gain,
     // and LN(x) W^T + b = r (x W'^T - mu c) + b' with c = row sums of W', b' = b + W beta - applied in the epilogue.  Here, under
-    // the latency of the first K-tile: (mu r, r) of this tile's rows from the twelve 32-column partials (mean, M2) the producing
-    // residual GEMM left per row, merged in segment order, into LDS behind the ring (a PLAIN launch has no such tail).
+    // the latency of the first K-tile: (mu r, r) of this tile's rows (SM_LN_FOLD_ROW, forward_pieces.h) into LDS behind the ring (a PLAIN
+    // launch has no such tail).
     float2* lnrow = reinterpret_cast<float2*>(smemm + RING_BYTES);
     if (!PLAIN && g.ln_stats && tid < BM) {
         int m = m0 + tid;
         m = m < M ? m : M - 1;
-        const float4* sp = reinterpret_cast<const float4*>(g.ln_stats + (int64_t)m * 24);
-        float mean_s[12], m2 = 0.f, msum = 0.f;
-#pragma unroll
-        for (int q = 0; q < 6; ++q) {
-            const float4 v = sp[q];
-            mean_s[2 * q] = v.x; mean_s[2 * q + 1] = v.z;
-            m2 += v.y; m2 += v.w;
-            msum += v.x; msum += v.z;
-        }
-        const float mu = msum * (1.0f / 12.0f);
-        float dev = 0.f;
-#pragma unroll
-        for (int q = 0; q < 12; ++q) dev += (mean_s[q] - mu) * (mean_s[q] - mu);
-        const float rstd = 1.0f / sqrtf((m2 + 32.0f * dev) * (1.0f / 384.0f) + g.ln_eps);
-        lnrow[tid] = make_float2(mu * rstd, rstd);
+        SM_LN_FOLD_ROW(g.ln_stats + (int64_t)m * 24, g.ln_eps, lnrow[tid]);
     }
-    const f16x8 down = {(_Float16)0.00048828125f, (_Float16)0.00048828125f, (_Float16)0.00048828125f, (_Float16)0.00048828125f,
-                        (_Float16)0.00048828125f, (_Float16)0.00048828125f, (_Float16)0.00048828125f, (_Float16)0.00048828125f};
+    const f16x8 down = f16x2_lo8();
     for (int kt = 0; kt < nk; ++kt) {
-        wait_vmcnt_w<(NST - 2) * NI>();
+        wait_vmcnt<(NST - 2) * NI>();
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         if (kt == 0) GEMM_STAMP(1);
@@ -226,7 +202,7 @@ __global__ __launch_bounds__(NWM * NWN * 64, WPS) void gemm_w16m16_kernel(sm_gem
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
-    wait_vmcnt_w<0>();
+    wait_vmcnt<0>();
     GEMM_STAMP(2);
 
     float* C = g.C + (split > 1 ? (int64_t)blockIdx.z : 0) * g.strideC;

@@ -2,7 +2,7 @@
 // mean and (two-pass, biased) variance by shuffle butterflies.  HBM-bound: reads x once, writes y once.
 // Reference: nn.LayerNorm at vision_transformer.py:165,169,299 (eps 1e-6), transformer_decoder.py:280,290,295,
 // 139 (eps 1e-5).
-#include "common.h"
+#include "forward_pieces.h"
 
 namespace sm {
 
@@ -10,15 +10,7 @@ __device__ __forceinline__ int64_t map_row(int r, sm_row_map m) {
     return m.group > 0 ? (int64_t)(r / m.group) * m.stride + m.offset + r % m.group : r;
 }
 
-// 16 lanes per row (four rows per wave), each lane owning the three 8-element groups g = l16 + 16 i: every access is a
-// 16-B (fp32: 2 x 16 B) piece and an F16X2 group leaves as one contiguous 32-B store; statistics are 4-step butterflies
-// inside the 16-lane group.
-__device__ __forceinline__ float group16_sum(float v) {
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 16);
-    return v;
-}
-
+// 16 lanes per row, each lane owning three 8-element groups: the layout and arithmetic of forward_pieces.h (ln384_*)
 __global__ __launch_bounds__(256) void layernorm384_kernel(sm_ln_args a) {
     const int lane = threadIdx.x & 63, l16 = lane & 15;
     const int row = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 4 + (lane >> 4);
@@ -65,19 +57,7 @@ __global__ __launch_bounds__(256) void layernorm384_kernel(sm_ln_args a) {
             *reinterpret_cast<float4*>(rw + k + 4) = make_float4(v[i][4], v[i][5], v[i][6], v[i][7]);
         }
     }
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) s += ((v[i][0] + v[i][1]) + (v[i][2] + v[i][3])) + ((v[i][4] + v[i][5]) + (v[i][6] + v[i][7]));
-    const float mean = group16_sum(s) * (1.0f / 384.0f);
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            v[i][e] -= mean;
-            q += v[i][e] * v[i][e];
-        }
-    const float rstd = 1.0f / sqrtf(group16_sum(q) * (1.0f / 384.0f) + a.eps);
+    const float rstd = ln384_center(v, a.eps);
     if (!live) return;
     const int64_t orow = map_row(row, a.out_map);
     float* yr = a.y ? a.y + orow * a.ldy : nullptr;
@@ -89,13 +69,7 @@ __global__ __launch_bounds__(256) void layernorm384_kernel(sm_ln_args a) {
     for (int i = 0; i < 3; ++i) {
         const int k = (l16 + 16 * i) * 8;
         float o[8];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const float4 gm = *reinterpret_cast<const float4*>(a.gamma + k + 4 * h);
-            const float4 bt = *reinterpret_cast<const float4*>(a.beta + k + 4 * h);
-            o[4 * h + 0] = v[i][4 * h + 0] * rstd * gm.x + bt.x; o[4 * h + 1] = v[i][4 * h + 1] * rstd * gm.y + bt.y;
-            o[4 * h + 2] = v[i][4 * h + 2] * rstd * gm.z + bt.z; o[4 * h + 3] = v[i][4 * h + 3] * rstd * gm.w + bt.w;
-        }
+        ln384_affine(v[i], rstd, a.gamma, a.beta, k, o);
         if (chain) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[i][e] = o[e];  // the chained norm's input: y as stored
@@ -122,19 +96,7 @@ __global__ __launch_bounds__(256) void layernorm384_kernel(sm_ln_args a) {
     }
     if (!chain) return;
     // chained norm: the same arithmetic, in the same order, as a launch of its own reading y (every lane of a live row's group is live)
-    float s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) s2 += ((v[i][0] + v[i][1]) + (v[i][2] + v[i][3])) + ((v[i][4] + v[i][5]) + (v[i][6] + v[i][7]));
-    const float mean2 = group16_sum(s2) * (1.0f / 384.0f);
-    float q2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            v[i][e] -= mean2;
-            q2 += v[i][e] * v[i][e];
-        }
-    const float rstd2 = 1.0f / sqrtf(group16_sum(q2) * (1.0f / 384.0f) + a.chain_eps);
+    const float rstd2 = ln384_center(v, a.chain_eps);
     const int64_t crow = map_row(row, a.chain_map);
     float* cyr = a.chain_y ? a.chain_y + crow * a.chain_ldy : nullptr;
     float* cysr = a.chain_ys ? a.chain_ys + crow * a.chain_ldy : nullptr;
@@ -142,13 +104,7 @@ __global__ __launch_bounds__(256) void layernorm384_kernel(sm_ln_args a) {
     for (int i = 0; i < 3; ++i) {
         const int k = (l16 + 16 * i) * 8;
         float o[8];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const float4 gm = *reinterpret_cast<const float4*>(a.chain_gamma + k + 4 * h);
-            const float4 bt = *reinterpret_cast<const float4*>(a.chain_beta + k + 4 * h);
-            o[4 * h + 0] = v[i][4 * h + 0] * rstd2 * gm.x + bt.x; o[4 * h + 1] = v[i][4 * h + 1] * rstd2 * gm.y + bt.y;
-            o[4 * h + 2] = v[i][4 * h + 2] * rstd2 * gm.z + bt.z; o[4 * h + 3] = v[i][4 * h + 3] * rstd2 * gm.w + bt.w;
-        }
+        ln384_affine(v[i], rstd2, a.chain_gamma, a.chain_beta, k, o);
         const float (&o0)[4] = *reinterpret_cast<const float (*)[4]>(&o[0]);
         const float (&o1)[4] = *reinterpret_cast<const float (*)[4]>(&o[4]);
         if (cyr) {

@@ -23,7 +23,7 @@
 // the same memory becomes K (224 x 256 B) + V^T (64 x 896 B).  N <= 208 tokens: the ViT-S/16 224^2 headline shape (197);
 // larger grids take the unfused path (K and V of one head no longer fit: 785 tokens x 256 B x 2 = 392 KiB).
 // The 32x32x16 form of round 2, the all-waves-load form and the three-slot ring were measured and rejected.
-#include "common.h"
+#include "forward_pieces.h"
 #include <type_traits>
 #include <math.h>
 #include <mutex>
@@ -127,35 +127,20 @@ __global__ __launch_bounds__(QA_WAVES * 64, 2) void qkv_attention_m16_kernel(sm_
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int v = 0; v < 4; ++v) acc[d][t][v] = 0.f;
-    const f16x8 down = {(_Float16)0.00048828125f, (_Float16)0.00048828125f, (_Float16)0.00048828125f, (_Float16)0.00048828125f,
-                        (_Float16)0.00048828125f, (_Float16)0.00048828125f, (_Float16)0.00048828125f, (_Float16)0.00048828125f};  // 2^-11
+    const f16x8 down = f16x2_lo8();
     constexpr int NKT = SM_EMBED / 32;
     QKV_STAMP_DECL;
     QKV_STAMP(0);
 #pragma unroll
     for (int t = 0; t < NST - 1; ++t) issue(t, t);
     // LayerNorm folded into the projection (a.ln_stats; see gemm_w16.hip): Xn then holds the RAW residual stream, the weights carry
-    // the norm's gain, and (mu r, r) per token come from the producer's twelve partials - computed here under the first stage's
+    // the norm's gain, and (mu r, r) per token come from the producer's twelve partials (SM_LN_FOLD_ROW) - computed here under the first stage's
     // latency, kept at the top of the LDS (above the ring and above the K / V^T overlay)
     float2* lnrow = reinterpret_cast<float2*>(smm + QA_LDS - QA_TOK * 8);
     static_assert(DUMP + (PPW * LOADERS - NP) * 1024 <= QA_LDS - QA_TOK * 8 && QM_K_BYTES + QM_V_BYTES <= QA_LDS - QA_TOK * 8, "row statistics above everything");
     if (a.ln_stats && tid < QA_TOK) {
         const int tok = tid < N ? tid : N - 1;
-        const float4* sp = reinterpret_cast<const float4*>(a.ln_stats + ((int64_t)b * N + tok) * 24);
-        float mean_s[12], m2 = 0.f, msum = 0.f;
-#pragma unroll
-        for (int q = 0; q < 6; ++q) {
-            const float4 v = sp[q];
-            mean_s[2 * q] = v.x; mean_s[2 * q + 1] = v.z;
-            m2 += v.y; m2 += v.w;
-            msum += v.x; msum += v.z;
-        }
-        const float mu = msum * (1.0f / 12.0f);
-        float dev = 0.f;
-#pragma unroll
-        for (int q = 0; q < 12; ++q) dev += (mean_s[q] - mu) * (mean_s[q] - mu);
-        const float rstd = 1.0f / sqrtf((m2 + 32.0f * dev) * (1.0f / 384.0f) + a.ln_eps);
-        lnrow[tid] = make_float2(mu * rstd, rstd);
+        SM_LN_FOLD_ROW(a.ln_stats + ((int64_t)b * N + tok) * 24, a.ln_eps, lnrow[tid]);
     }
     // A wave whose second 16-token tile lies wholly beyond N (wave 6 at N = 197: rows 208..223) skips that tile's MFMAs in
     // both phases: its accumulators stay zero, so its K rows / V^T columns hold the bias (finite; those keys are masked).
@@ -163,7 +148,7 @@ __global__ __launch_bounds__(QA_WAVES * 64, 2) void qkv_attention_m16_kernel(sm_
     auto project = [&](auto nt_tag) {
         constexpr int NT = decltype(nt_tag)::value;
         for (int kt = 0; kt < NKT; ++kt) {
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NST - 2) * PPW) : "memory");
+            wait_vmcnt<(NST - 2) * PPW>();
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
             if (kt == 0) QKV_STAMP(1);
@@ -209,7 +194,7 @@ __global__ __launch_bounds__(QA_WAVES * 64, 2) void qkv_attention_m16_kernel(sm_
     if (two_tiles) project(std::integral_constant<int, 2>{});
     else project(std::integral_constant<int, 1>{});
     QKV_STAMP(2);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __syncthreads();  // the ring becomes K / V^T
     QKV_STAMP(3);
 
@@ -325,7 +310,7 @@ __global__ __launch_bounds__(QA_WAVES * 64, 2) void qkv_attention_m16_kernel(sm_
                             cr = __builtin_amdgcn_mfma_f32_16x16x32_f16(kl[s], qh[t][s], cr, 0, 0, 0);
                         }
                     }
-                    if constexpr (TERMS == 3) sc[kt][t] = cr * (1.0f / 2048.0f) + mn;
+                    if constexpr (TERMS == 3) sc[kt][t] = cr * F16X2_LO + mn;
                     else sc[kt][t] = mn;
                 }
             }
@@ -438,7 +423,7 @@ __global__ __launch_bounds__(QA_WAVES * 64, 2) void qkv_attention_m16_kernel(sm_
                 for (int dt = 0; dt < 4; ++dt) {
                     float x[4];
     #pragma unroll
-                    for (int e = 0; e < 4; ++e) x[e] = (om[dt][t][e] + oc[dt][t][e] * (1.0f / 2048.0f)) * inv;
+                    for (int e = 0; e < 4; ++e) x[e] = (om[dt][t][e] + oc[dt][t][e] * F16X2_LO) * inv;
                     const int d = head * SM_HEAD_DIM + 16 * dt + 4 * kg;  // this lane's four consecutive head-dims
                     if (a.out_f16x2 & 1) store_f16x2_4(Orow, d, x);
                     else *reinterpret_cast<float4*>(Orow + d) = make_float4(x[0], x[1], x[2], x[3]);

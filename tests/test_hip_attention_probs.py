@@ -16,8 +16,9 @@ import _ledger as ledger  # noqa: E402
 
 DEV = "cuda:0"
 HEADS = 6
-SHAPES = [(1, 1), (2, 21), (2, 197), (1, 209), (1, 337), (1, 526)]  # (B, n): single key; small grid; tail masked up to 208;
-#                                                          one past the fused limit; the 250 x 333 grid; the P8 grid
+SHAPES = [(1, 1), (2, 21), (2, 197), (1, 209), (1, 337), (1, 526),  # (B, n): single key; small grid; tail masked up to 208;
+          #                                                          one past the fused limit; the 250 x 333 grid; the P8 grid
+          (1, 32), (1, 64), (1, 65), (1, 96), (1, 128)]  # a 64-key chunk exactly full, one key over, exactly one 32-key block
 REGIMES = {"unit": 1.0, "peaky": 15.0}  # unit-variance q, k: |score| <= ~5;  q x 15: |score| reaches ~60, most of a row underflows
 GUARD = 257  # floats of NaN behind every image's block (odd: the blocks do not stay aligned), and a sentinel block in front
 

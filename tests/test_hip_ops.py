@@ -157,7 +157,10 @@ def _attn_ref(q, k, v, scale):
 
 
 @pytest.mark.parametrize("B,nq,nk", [(2, 197, 197), (1, 785, 785), (1, 577, 577), (3, 20, 20), (3, 20, 196), (2, 20, 784),
-                                      (1, 1, 1), (1, 33, 225)])
+                                      (1, 1, 1), (1, 33, 225),
+                                      # key counts at the edges of the split kernel's 64-key chunks and 32-key blocks: a chunk exactly
+                                      # full, one key over, exactly one block
+                                      (1, 5, 32), (1, 5, 64), (1, 40, 65), (2, 33, 96), (1, 64, 128)])
 @pytest.mark.parametrize("split", [False, True])
 def test_attention_shapes(B, nq, nk, split):
     qkv = _rand(B, max(nq, nk), 3, 6, 64, seed=30, scale=1.5).to(DEV)
