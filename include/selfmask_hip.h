@@ -505,6 +505,29 @@ int sm_upsample_selected_native_f64(const float* masks, int64_t mask_stride_b, c
 int sm_mask_planes_u8_to_f32(const uint8_t* src, const sm_bilateral_image* images, float* dst, int32_t B, int32_t Hmax,
                              int32_t Wmax, int32_t max_pixels, void* stream);
 
+/* ---- E-measure and weighted F-measure (sod_metrics.hip; the values are defined by selfmask_amd/sod_metrics.py) -----------
+ * Both are computed from the 8-bit plane of a prediction at the ground truth's size: trunc(255 clip(v, 0, 1)), the predictor's
+ * `soft` bytes.  `pred` and `gt` are concatenated H_b * W_b-byte planes, image b of BOTH at images[b].gt_off (gt: 0 / non-zero);
+ * sizes may differ within a batch; 1 <= H_b, W_b <= 16384 and H_b * W_b <= max_pixels <= 2^22.  `images` is the device table the
+ * kernels read, `images_host` the same table on the host: it is checked and sizes the launch grids.
+ * out[b] = {e_adp, e_mean, e_max, wfm} (fp64); hist: NULL, or int32 [B][2][256], the histograms of the plane over the foreground
+ * ([0]) and the background ([1]).  An image without foreground gets wfm = 0.  The weighted F-measure rests on an exact Euclidean
+ * feature transform in which a background pixel equally near to several foreground pixels takes the one of the lowest raster
+ * index.  Integer atomics only, fixed-order fp64 sums: an image's values depend neither on the batch nor on its place in it.
+ * Nothing is allocated or synchronised; workspace: sm_sod_metrics_workspace_bytes(B, max_pixels) bytes, 256-B aligned. */
+size_t sm_sod_metrics_workspace_bytes(int32_t B, int32_t max_pixels);
+int sm_sod_metrics_u8(const uint8_t* pred, const uint8_t* gt, const sm_eval_image* images, const sm_eval_image* images_host,
+                      int32_t B, int32_t max_pixels, double* out, int32_t* hist, void* workspace, size_t workspace_bytes,
+                      void* stream);
+/* The plane those metrics score: the query named in rows[b][sel_col] (14 = picked, 15 = upper bound, as sm_evaluate_masks_f32
+ * wrote it) up-sampled as that call scored it - scale > 0: F.interpolate(scale_factor=scale)[..., :H_b, :W_b]; scale = 0: resized
+ * to (H_b, W_b) - then trunc(255 clip(v, 0, 1)), written at out + images[b].gt_off (the device table of sm_evaluate_masks_f32, so
+ * the plane lies where sm_sod_metrics_u8 looks for it).  For the picked query these are the bytes of sm_predict_masks_f32's soft
+ * plane. */
+int sm_upsample_selected_u8(const float* masks, int64_t mask_stride_b, const float* rows, int32_t sel_col,
+                            const sm_eval_image* images, uint8_t* out, int32_t B, int32_t mh, int32_t mw, float scale,
+                            int32_t max_pixels, void* stream);
+
 /* ---- predictor finish (SaliencyPredictor): query masks -> the picked query's mask per image at the image's own size ------ */
 /* One fused step from the last decoder layer to the results: best[b] = arg-max objectness, and the picked mask up-sampled
  * to (H_b, W_b) - pixel for pixel the value sm_evaluate_masks_f32 scores and sm_upsample_selected*_f64 emit - leaves as run

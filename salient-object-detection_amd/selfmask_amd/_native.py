@@ -276,6 +276,10 @@ SYMBOLS = {
     "sm_upsample_selected_native_f64": (C.c_int, [fp, C.c_int64, fp, C.c_int32, fp, fp, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                                   C.c_int32, fp]),
     "sm_mask_planes_u8_to_f32": (C.c_int, [fp, fp, fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, fp]),
+    "sm_sod_metrics_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "sm_sod_metrics_u8": (C.c_int, [fp, fp, fp, fp, C.c_int32, C.c_int32, fp, fp, fp, C.c_size_t, fp]),
+    "sm_upsample_selected_u8": (C.c_int, [fp, C.c_int64, fp, C.c_int32, fp, fp, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
+                                          fp]),
     "sm_preprocess_normalize_u8": (C.c_int, [fp, fp, fp, fp, C.c_int32, C.c_int32, fp]),
     "sm_preprocess_normalize_pad_u8": (C.c_int, [fp, fp, fp, fp, C.c_int32, C.c_int32, C.c_int32, fp]),
     "sm_pick_mask_f32": (C.c_int, [fp, C.c_int64, fp, C.c_int64, fp, fp, C.c_int32, C.c_int32, C.c_int32, fp]),

@@ -152,6 +152,40 @@ def gather_rows(rows_local: torch.Tensor, idx_local: Sequence[int], n_total: int
     return out
 
 
+def gather_values(values_local: torch.Tensor, idx_local: Sequence[int], n_total: int, comm) -> np.ndarray:
+    """gather_rows for fp64 values of any width K: values_local (n_local, K) float64 -> (n_total, K) float64 numpy in global index
+    order on every rank (payload per rank: ceil(n/W) x (K + 1) fp64, the global index first, padded with index -1)."""
+    K = int(values_local.shape[1])
+    per = -(-n_total // comm.world_size)
+    buf = torch.full((per, K + 1), -1.0, dtype=torch.float64, device=values_local.device)
+    n = len(idx_local)
+    if n:
+        buf[:n, 0] = torch.tensor(list(idx_local), dtype=torch.float64, device=values_local.device)
+        buf[:n, 1:] = values_local
+    allb = comm.all_gather(buf).reshape(-1, K + 1).cpu().numpy()
+    out = np.full((n_total, K), np.nan, np.float64)
+    seen = np.zeros(n_total, bool)
+    for r in allb:
+        i = int(r[0])
+        if i >= 0:
+            assert not seen[i], f"image {i} evaluated twice"
+            out[i], seen[i] = r[1:], True
+    assert seen.all(), f"{int((~seen).sum())} images missing after the gather"
+    return out
+
+
+def average_values(values: np.ndarray) -> List[float]:
+    """Column means of (n, K) fp64 values, each column added in index order (as the S-measure's meter adds): the same bits on every
+    rank and for every sharding."""
+    out = []
+    for k in range(values.shape[1]):
+        s = 0.0
+        for v in values[:, k]:
+            s += float(v)
+        out.append(s / len(values))
+    return out
+
+
 def gather_bytes(payload: bytes, comm, device="cpu") -> List[bytes]:
     """One variable-length byte string per rank -> the list of all ranks' strings, in rank order, on every rank: an all-gather of the
     lengths, then one of the payloads padded to the longest (device tensors under RCCL, host tensors under gloo)."""

@@ -4,6 +4,10 @@ Appendix A, evaluator.pyc@L17-373) with the per-image work on the MI355X:
   forward (HIP) -> last decoder layer -> bilinear up-sample + crop -> upper-bound query by IoU, arg-max-objectness
   query -> 7 metrics x {pick, upper bound} (sm_evaluate_masks_f32) -> running means -> ``metrics_<dataset>.txt``.
 
+``extra_metrics`` adds the two numbers every salient-object-detection table also carries - E-measure (adaptive, mean, max) and
+weighted F-measure, on the 8-bit plane of the same up-sampled masks (sm_sod_metrics_u8; sod_metrics.py defines them) - in a file of
+their own, ``metrics_<dataset>_extra.txt``.
+
 Two operating points: the reference's own (batch 1, native resolution, up-sample factor patch_size // scale_factor,
 i.e. the hard-coded 4 of evaluator.pyc@L209-211 for ViT-S/8) and a batched mode (``img_size`` given: inputs resized
 to S x S, masks resized to each GT's native size).  Images shard across ranks (distributed.py).
@@ -20,7 +24,8 @@ from .base_structure import BaseStructure
 from .datasets import get_dataset
 from .graphs import GraphedForward
 from .streams import DEFAULT_STREAMS, StreamRing
-from .distributed import HEADER, KEYS, SingleComm, TorchDistComm, average_rows, gather_rows, shard_indices
+from .distributed import HEADER, KEYS, SingleComm, TorchDistComm, average_rows, average_values, gather_rows, gather_values, shard_indices
+from .sod_metrics import NAMES as EXTRA_NAMES
 
 
 # constants of evaluator.pyc@L164-309 (read from the bytecode as data: tests/golden/evaluator_constants.json pins them)
@@ -41,7 +46,7 @@ class Evaluator(BaseStructure):
     def __call__(self, dataset_name: str, dir_ckpt: str, img_size: Optional[int] = None, scale_factor: int = 2,
                  batch_size: int = 1, device: torch.device = torch.device("cuda:0"), cost_type: str = "iou",
                  comm=None, streams: int = DEFAULT_STREAMS, hip_graph: bool = True, input_pipeline: str = "device",
-                 workers: Optional[int] = None, refine: Optional[str] = None) -> dict:
+                 workers: Optional[int] = None, refine: Optional[str] = None, extra_metrics: bool = False) -> dict:
         """evaluator.pyc@L164-309.  Extra keyword arguments (not in the reference): ``comm`` / ``streams`` / ``hip_graph``
         (image sharding, batches in flight, graph replay) and ``input_pipeline``: "device" (default) decodes on a pool of
         ``workers`` host threads running ahead of the GPU and does resize + ToTensor + Normalize in HIP kernels
@@ -51,7 +56,10 @@ class Evaluator(BaseStructure):
         launch sequence - and the solver's binary mask is scored by the same metric kernels; the returned dict gains the seven
         ``*_refined`` values and ``metrics_<dataset>_refined.txt`` is written.  At native resolution (``img_size=None``, batch 1
         or token-grid buckets) the target is the mask the metrics scored - up-sampled by the reference factor and cropped to the
-        image - the reference image is the decoded one at its own size, and a bucket is ONE mixed-size solve."""
+        image - the reference image is the decoded one at its own size, and a bucket is ONE mixed-size solve.
+        ``extra_metrics=True``: the dict gains ``e_adp, e_mean, e_max, wfm`` of the picked mask, their ``_ub`` twins and, with
+        ``refine``, their ``_refined`` ones (fp64 means over the images in index order), written to ``metrics_<dataset>_extra.txt``;
+        ``metrics_<dataset>.txt`` and the fourteen other values are the same bytes with or without it."""
         assert cost_type == "iou", "the upper bound is chosen by IoU (evaluator.pyc@L216); other costs are unused"
         if not getattr(self.model, "use_binary_classifier", True):
             raise RuntimeError("the evaluator dereferences objectness unconditionally (evaluator.pyc@L219): "
@@ -85,6 +93,9 @@ class Evaluator(BaseStructure):
         pin_path = ("fused" if (img_size is not None and batch_size >= 16) else "unfused") if prev_path == "auto" else None
         rows_local = torch.empty((len(mine), 16), dtype=torch.float32, device=device)
         rows_refined = torch.empty((len(mine), 16), dtype=torch.float32, device=device) if refine else None
+        # per image: [pick, upper bound(, refined)] x (e_adp, e_mean, e_max, wfm)
+        n_extra = (3 if refine else 2) if extra_metrics else 0
+        extra_local = torch.empty((len(mine), n_extra, 4), dtype=torch.float64, device=device) if extra_metrics else None
         ring = StreamRing(device, streams)  # consecutive batches in flight on different HIP streams (streams.py)
         # recurring batch shapes replay one captured hipGraph per stream instead of ~150 launches (graphs.py)
         # native-resolution mode meets a new shape with almost every image: graphs would only thrash there.  In token-grid
@@ -133,7 +144,11 @@ class Evaluator(BaseStructure):
                     yield s, (shapes, lambda sh, S, dev, packed=packed, **kw: preprocess_on_device(sh, S, dev, packed=packed, **kw)), gts
                     s += len(shapes)
 
-        bucket_pos, bucket_rows, bucket_rows_refined = [], [], []
+        bucket_pos, bucket_rows, bucket_rows_refined, bucket_extra = [], [], [], []
+
+        def scored(*a, **kw):  # rows, and the (B, 2, 4) extra values when they are asked for
+            res = ops.evaluate_masks(*a, extra=extra_metrics, **kw)
+            return res if extra_metrics else (res, None)
         try:
             if pin_path is not None:  # inside the try: whatever fails below, the shared model gets its "auto" back
                 self.model.attention_path = pin_path
@@ -153,7 +168,7 @@ class Evaluator(BaseStructure):
                     if mask_pred.dim() == 5:  # evaluator.pyc@L199-205: last decoder layer
                         mask_pred, obj = mask_pred[:, -1], obj[:, -1]
                     gtb = ops.GtBatch.from_packed(gts, device) if isinstance(gts, tuple) else ops.GtBatch(gts, device)
-                    rows = ops.evaluate_masks(mask_pred, obj.squeeze(-1), gtb, scale=scale)
+                    rows, extra = scored(mask_pred, obj.squeeze(-1), gtb, scale=scale)
                     if bucketed:  # s = this bucket's positions in the rank's image list: scattered after the loop - an index
                         bucket_pos += s       # tensor built here is a pageable host-to-device copy, which waits for this
                         bucket_rows.append(rows)  # stream's work: it serialised the three streams (2.2 ms per batch)
@@ -167,7 +182,7 @@ class Evaluator(BaseStructure):
                         mb = MixedBatch(gtb.shapes, device, packed_pixel_offsets(gtb.shapes))
                         target = ops.upsample_selected_native(mask_pred, rows, mb, scale, "pick")
                         _, binary, _ = bilateral_solver_mixed_packed(u8, target, mb)
-                        refined = ops.evaluate_masks(ops.mask_planes_u8_to_f32(binary, mb), rows[:, 0:1], gtb, scale=1.0)
+                        refined, ex_ref = scored(ops.mask_planes_u8_to_f32(binary, mb), rows[:, 0:1], gtb, scale=1.0)
                         if bucketed:
                             bucket_rows_refined.append(refined)
                         else:
@@ -177,13 +192,22 @@ class Evaluator(BaseStructure):
                         target = ops.upsample_selected(mask_pred, rows, (img_size, img_size), "pick")
                         _, binary = bilateral_solver_batch_device(u8, target)
                         refined = ops.mask_u8_to_f32(binary).unsqueeze(1)  # one "query" per image; its objectness is moot
-                        rows_refined[s:s + gtb.B] = ops.evaluate_masks(refined, rows[:, 0:1], gtb, scale=0.0)
+                        rows_refined[s:s + gtb.B], ex_ref = scored(refined, rows[:, 0:1], gtb, scale=0.0)
+                    if extra_metrics:
+                        if refine:  # a refined mask is one query: its pick and upper bound are the same plane
+                            extra = torch.cat([extra, ex_ref[:, 0:1]], dim=1)
+                        if bucketed:
+                            bucket_extra.append(extra)
+                        else:
+                            extra_local[s:s + gtb.B] = extra
             ring.join()
             if bucket_rows:
                 at = torch.as_tensor(bucket_pos, device=device)
                 rows_local[at] = torch.cat(bucket_rows)
                 if bucket_rows_refined:
                     rows_refined[at] = torch.cat(bucket_rows_refined)
+                if bucket_extra:
+                    extra_local[at] = torch.cat(bucket_extra)
         finally:
             if prev_path == "auto":
                 self.model.attention_path = prev_path
@@ -211,6 +235,15 @@ class Evaluator(BaseStructure):
                 with open(os.path.join(dir_ckpt, f"metrics_{dataset_name}_refined.txt"), "w") as f:
                     f.write("iou,pixel_acc,f_score,f_max,f_mean,mae,s_measure\n")
                     f.write(",".join(str(ref[k]) for k in ("iou", "pixel_accuarcy", "f_score", "f_max", "f_mean", "mae", "s_measure")))
+        if extra_metrics:
+            ex = gather_values(extra_local.reshape(len(mine), n_extra * 4), mine, n_total, comm)  # gathered as the rows are
+            names = [k + sfx for sfx in ("", "_ub", "_refined")[:n_extra] for k in EXTRA_NAMES]
+            results.update(zip(names, average_values(ex)))
+            self.last_extra = ex.reshape(n_total, n_extra, 4)
+            if comm.rank == 0:  # a file of its own: metrics_<dataset>.txt keeps the reference's columns
+                with open(os.path.join(dir_ckpt, f"metrics_{dataset_name}_extra.txt"), "w") as f:
+                    f.write(",".join(names) + "\n")
+                    f.write(",".join(str(results[k]) for k in names))
         return results
 
 
@@ -230,6 +263,8 @@ def main(argv=None):
     ap.add_argument("--suffix", type=str, default="")
     ap.add_argument("--img_size", type=int, default=None, help="batched mode: resize inputs to S x S")
     ap.add_argument("--batch_size", type=int, default=1)
+    ap.add_argument("--extra_metrics", action="store_true",
+                    help="also E-measure (adaptive, mean, max) and weighted F-measure -> metrics_<dataset>_extra.txt")
     args = ap.parse_args(argv)
     base = yaml.safe_load(open(args.config))
     vars(args).update(base)
@@ -249,7 +284,7 @@ def main(argv=None):
     ev = Evaluator(network=model, dir_dataset=args.dir_dataset)
     ev.device = device
     res = ev(args.dataset_name, dir_ckpt=os.path.join(args.dir_ckpt, "eval" + args.suffix), img_size=args.img_size,
-             scale_factor=args.scale_factor, batch_size=args.batch_size, device=device)
+             scale_factor=args.scale_factor, batch_size=args.batch_size, device=device, extra_metrics=bool(args.extra_metrics))
     if int(os.environ.get("RANK", "0")) == 0:
         print(res)
     return res

@@ -3,6 +3,7 @@
 PyTorch is plumbing here: device memory + streams.  Every function launches hand-written gfx950 kernels from
 libselfmask_hip.so and raises if handed a CPU tensor (there is no fallback path).
 """
+import ctypes
 from typing import Optional, Tuple
 
 import torch
@@ -347,6 +348,7 @@ class GtBatch:
             flat.append(g.reshape(-1))
         self.B = B
         self.shapes = [(int(g.shape[0]), int(g.shape[1])) for g in gts]
+        self.offsets = [int(descr[b].gt_off) for b in range(B)]
         self.gt_all = (flat[0] if B == 1 else torch.cat(flat)).to(device)
         self.images = torch.frombuffer(bytearray(bytes(descr)), dtype=torch.uint8).to(device)
 
@@ -357,6 +359,10 @@ def _gtbatch_from_packed(packed, device) -> "GtBatch":
     flat, descr, shapes = packed
     gb = GtBatch.__new__(GtBatch)
     gb.B, gb.shapes = len(shapes), shapes
+    gb.offsets, off = [], 0
+    for h, w in shapes:  # pack_gts lays the planes end to end
+        gb.offsets.append(off)
+        off += h * w
     gb.gt_all = flat.to(device, non_blocking=True)
     gb.images = descr.to(device, non_blocking=True)
     _POOL.release_after((flat, descr), torch.cuda.current_stream(device))
@@ -388,6 +394,7 @@ def _gtbatch_from_device(flat: torch.Tensor, shapes, offsets) -> "GtBatch":
     host.numpy()[:n] = np.frombuffer(bytes(descr), np.uint8)
     gb = GtBatch.__new__(GtBatch)
     gb.B, gb.shapes, gb.gt_all = B, shapes, flat
+    gb.offsets = [int(o) for o in offsets]
     gb.images = host.to(flat.device, non_blocking=True)
     _POOL.release_after((host,), torch.cuda.current_stream(flat.device))
     return gb
@@ -397,13 +404,15 @@ GtBatch.from_device = staticmethod(_gtbatch_from_device)
 
 
 def evaluate_masks(mask_pred_last: torch.Tensor, objectness_last: torch.Tensor, gts, scale: float = 0.0,
-                   return_ious: bool = False):
+                   return_ious: bool = False, extra: bool = False):
     """Evaluator post-processing + 14 metrics per image on the device (sm_evaluate_masks_f32).
 
     mask_pred_last (B, nq, mh, mw) probabilities (any batch stride, e.g. ``out["mask_pred"][:, -1]``),
     objectness_last (B, nq), gts: list of B uint8 {0,1} tensors (H_b, W_b) or a prepacked GtBatch.
     scale > 0: reference mode (F.interpolate(scale_factor=scale)[..., :H, :W]); 0: resize to each GT's size.
-    Returns rows (B, 16) float32 [7 metrics of the picked mask, 7 of the upper bound, q*, ub] (+ ious (B, nq))."""
+    Returns rows (B, 16) float32 [7 metrics of the picked mask, 7 of the upper bound, q*, ub] (+ ious (B, nq)).
+    ``extra=True`` appends ``extra`` (B, 2, 4) float64 to the result: e_adp, e_mean, e_max, wfm (sod_metrics) of the picked and of
+    the upper-bound query's 8-bit plane (upsample_selected_u8), as the same call up-sampled them."""
     _dev(mask_pred_last, objectness_last)
     B, nq, mh, mw = mask_pred_last.shape
     assert mask_pred_last.stride(3) == 1 and mask_pred_last.stride(2) == mw and mask_pred_last.stride(1) == mh * mw
@@ -430,6 +439,10 @@ def evaluate_masks(mask_pred_last: torch.Tensor, objectness_last: torch.Tensor, 
     a.B, a.nq, a.mh, a.mw, a.scale = B, nq, mh, mw, float(scale)
     a.max_pixels = max_pixels
     N.check(lib.sm_evaluate_masks_f32(a, _stream()), "sm_evaluate_masks_f32")
+    if extra:
+        ex = torch.stack([sod_metrics(upsample_selected_u8(mask_pred_last, rows, gb, scale, which), gb) for which in ("pick", "ub")],
+                         dim=1)
+        return (rows, ious, ex) if return_ious else (rows, ex)
     return (rows, ious) if return_ious else rows
 
 
@@ -483,6 +496,87 @@ def mask_planes_u8_to_f32(binary: torch.Tensor, batch) -> torch.Tensor:
     N.check(N.load().sm_mask_planes_u8_to_f32(binary.data_ptr(), batch.dev.data_ptr(), out.data_ptr(), batch.B, Hm, Wm,
                                               batch.max_pixels, _stream()), "sm_mask_planes_u8_to_f32")
     return out
+
+
+def _gt_host_table(gb: "GtBatch"):
+    """The batch's sm_eval_image table on the host (sm_sod_metrics_u8 checks it and sizes its grids from it), built once."""
+    t = getattr(gb, "_host_table", None)
+    if t is None:
+        t = (N.EvalImage * gb.B)()
+        for b, ((h, w), off) in enumerate(zip(gb.shapes, gb.offsets)):
+            t[b].gt_off, t[b].H, t[b].W = off, h, w
+        gb._host_table = t
+    return t
+
+
+def _gt_extent(gb: "GtBatch") -> int:
+    return max(off + h * w for (h, w), off in zip(gb.shapes, gb.offsets))
+
+
+def upsample_selected_u8(mask_pred_last: torch.Tensor, rows: torch.Tensor, gts: "GtBatch", scale: float = 0.0,
+                         which: str = "pick") -> torch.Tensor:
+    """The 8-bit plane E-measure and weighted F are defined on (sm_upsample_selected_u8): image b's picked ("pick") or upper-bound
+    ("ub") query up-sampled as evaluate_masks(..., scale=scale) scored it, clipped to [0, 1], times 255, truncated - the
+    predictor's ``soft`` bytes.  Returns a flat uint8 buffer with image b's (H_b, W_b) plane at ``gts.offsets[b]``, where the ground
+    truth lies in ``gts.gt_all``."""
+    _dev(mask_pred_last, rows)
+    B, nq, mh, mw = mask_pred_last.shape
+    assert mask_pred_last.stride(3) == 1 and mask_pred_last.stride(2) == mw and mask_pred_last.stride(1) == mh * mw
+    assert rows.shape == (B, 16) and rows.is_contiguous() and gts.B == B and which in ("pick", "ub")
+    if scale > 0:
+        for (h, w) in gts.shapes:
+            assert h <= int(mh * scale) and w <= int(mw * scale), "GT larger than the up-sampled mask"
+    out = torch.empty(_gt_extent(gts), dtype=torch.uint8, device=mask_pred_last.device)
+    N.check(N.load().sm_upsample_selected_u8(mask_pred_last.data_ptr(), mask_pred_last.stride(0), rows.data_ptr(),
+                                             14 if which == "pick" else 15, gts.images.data_ptr(), out.data_ptr(), B, mh, mw,
+                                             float(scale), max(h * w for h, w in gts.shapes), _stream()), "sm_upsample_selected_u8")
+    return out
+
+
+def sod_metrics(pred_u8, gts, return_hist: bool = False):
+    """E-measure and weighted F-measure per image on the device (sm_sod_metrics_u8; ``sod_metrics.py`` defines the values).
+
+    ``pred_u8``: a list of B (H_b, W_b) uint8 device tensors (then ``gts`` may be a list of uint8 tensors of the same sizes or a
+    GtBatch), or one flat uint8 buffer with image b's plane at ``gts.offsets[b]`` (``gts`` a GtBatch; what upsample_selected_u8
+    returns).  Returns (B, 4) float64 on the device: e_adp, e_mean, e_max, wfm; with ``return_hist`` also the (B, 2, 256) int32
+    histograms of the planes over foreground and background."""
+    if isinstance(pred_u8, (list, tuple)):
+        if not pred_u8:
+            raise ValueError("an empty batch")
+        dev = pred_u8[0].device
+        gb = gts if isinstance(gts, GtBatch) else GtBatch(gts, dev)
+        for p in pred_u8:
+            if not p.is_cuda or p.dtype != torch.uint8 or p.dim() != 2:
+                raise RuntimeError("sod_metrics takes 2-D uint8 planes on a HIP device (no CPU fallback)")
+        if [tuple(p.shape) for p in pred_u8] != [tuple(s) for s in gb.shapes]:
+            raise ValueError("prediction and ground-truth sizes differ")
+        if all(o == sum(h * w for h, w in gb.shapes[:b]) for b, o in enumerate(gb.offsets)):
+            flat = pred_u8[0].reshape(-1) if gb.B == 1 else torch.cat([p.reshape(-1) for p in pred_u8])
+        else:
+            flat = torch.empty(_gt_extent(gb), dtype=torch.uint8, device=dev)
+            for p, o in zip(pred_u8, gb.offsets):
+                flat[o:o + p.numel()] = p.reshape(-1)
+    else:
+        if not isinstance(gts, GtBatch):
+            raise ValueError("a packed prediction buffer goes with a GtBatch")
+        flat, gb = pred_u8, gts
+        if not flat.is_cuda or flat.dtype != torch.uint8 or flat.dim() != 1 or not flat.is_contiguous():
+            raise RuntimeError("sod_metrics takes a flat uint8 buffer on a HIP device (no CPU fallback)")
+    dev = flat.device
+    if flat.numel() < _gt_extent(gb) or gb.gt_all.numel() < _gt_extent(gb) or gb.gt_all.device != dev:
+        raise ValueError("the prediction buffer (or the ground truth) is shorter than the batch's planes, or on another device")
+    B = gb.B
+    max_pixels = max(h * w for h, w in gb.shapes)
+    lib = N.load()
+    wsb = lib.sm_sod_metrics_workspace_bytes(B, max_pixels)
+    if wsb == 0:
+        raise ValueError("unsupported sod_metrics shape (1 <= H W <= 2^22 per image)")
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    out = torch.empty((B, 4), dtype=torch.float64, device=dev)
+    hist = torch.empty((B, 2, 256), dtype=torch.int32, device=dev) if return_hist else None
+    N.check(lib.sm_sod_metrics_u8(flat.data_ptr(), gb.gt_all.data_ptr(), gb.images.data_ptr(), ctypes.addressof(_gt_host_table(gb)), B, max_pixels,
+                                  out.data_ptr(), _ptr(hist), ws.data_ptr(), wsb, _stream()), "sm_sod_metrics_u8")
+    return (out, hist) if return_hist else out
 
 
 class PackedImages:
