@@ -49,6 +49,9 @@ void tap_end(int handle) {
 // Forwards this small (batch 1-2 at 224^2: serving) run the encoder's fc2 - K = 1536 on M/64 x 6 workgroups, a 48-step serial K
 // loop of ~20 us - split four ways along K; the LayerNorm launch that follows sums the slices (as the decoder's does).  Only on
 // the automatic path (sm_forward_io.attn_path = 0): the Evaluator pins a path so that rows do not depend on the batch size.
+// And only below 16 images: from there on the automatic path IS the large-batch kernel set, to the bit (the "fused" pin) - a
+// caller who pins for a ragged last batch gets what the full batches gave.  (The split would be 0.10 ms of 1.1 - 1.8 ms faster at
+// 16 - 100 images of 32^2 - 80^2 pixels, profiles/auto_vs_fused_pin_small_grids.log: given up for that equality.)
 static const int64_t SM_SPLIT_FC2_ROWS = 512;
 
 struct Shape {
@@ -344,7 +347,7 @@ int Fwd::encoder() const {
     // epilogues and the statistics cost more than 23 co-resident LayerNorm launches) - so it follows the same batch rule and the same
     // pin as the attention path (sm_forward_io.attn_path: 2 = the small-batch kernels, 1 = the large-batch ones).
     const bool lnf = c.W16 && w->ln_fold != 0 && io->attn_path != 1 && (io->attn_path == 2 || s.B * SM_HEADS < 96);
-    const bool split_fc2 = c.W16 && S && io->attn_path == 0 && s.M <= SM_SPLIT_FC2_ROWS;  // see SM_SPLIT_FC2_ROWS
+    const bool split_fc2 = c.W16 && S && io->attn_path == 0 && s.M <= SM_SPLIT_FC2_ROWS && s.B * SM_HEADS < 96;  // see SM_SPLIT_FC2_ROWS
 
     auto pre_norm = [&](const float* gamma, const float* beta) {  // X -> Xn; the LN output only feeds a GEMM: F16X2 in split mode
         sm_ln_args a = ln_args(ws.X, gamma, beta, S ? nullptr : ws.Xn, s.M, 1e-6f);

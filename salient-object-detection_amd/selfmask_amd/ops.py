@@ -258,14 +258,20 @@ def fold_layernorm(weight: torch.Tensor, bias: torch.Tensor, gamma: torch.Tensor
 
 
 def qkv_attention(xn: torch.Tensor, w_qkv: torch.Tensor, b_qkv: torch.Tensor, B: int, scale: float = 0.125,
-                  out_f16x2: bool = False, ln=None) -> torch.Tensor:
+                  out_f16x2: bool = False, ln=None, xs: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Fused qkv Linear + softmax attention of an encoder block (sm_qkv_attention_w16): xn (B*N, 384) fp32 LayerNorm output
-    (converted to F16X2 here), w_qkv (1152, 384) / b_qkv (1152) fp32 -> (B*N, 384) merged-head attention output."""
-    _dev(xn, w_qkv, b_qkv)
-    M = xn.shape[0]
-    assert M % B == 0 and xn.shape[1] == N.EMBED
-    xs = split_f16x2(xn.contiguous())
-    o = torch.empty((M, N.EMBED), device=xn.device, dtype=torch.float32)
+    (converted to F16X2 here), w_qkv (1152, 384) / b_qkv (1152) fp32 -> (B*N, 384) merged-head attention output.
+    ``xs``: the input already in F16X2 (then ``xn`` is not read and may be None) - a (B*N, 384) view whose row stride becomes
+    ldx, e.g. a column slice of a wider buffer that starts at a multiple of 8 columns.  ``out``: a (B*N, 384) view to write
+    into; its row stride becomes ldo.  The library checks strides and alignment."""
+    _dev(xn, w_qkv, b_qkv, xs, out)
+    if xs is None:
+        xs = split_f16x2(xn.contiguous())
+    M = xs.shape[0]
+    assert M % B == 0 and xs.dim() == 2 and xs.shape[1] == N.EMBED and xs.stride(1) == 1
+    o = out if out is not None else torch.empty((M, N.EMBED), device=xs.device, dtype=torch.float32)
+    assert tuple(o.shape) == (M, N.EMBED) and o.stride(1) == 1
     a = N.QkvAttnArgs()
     if ln is not None:  # (gamma, beta, eps, stats): xn is then the RAW stream whose LayerNorm is folded into the projection
         gamma, beta, eps, stats = ln
@@ -275,7 +281,7 @@ def qkv_attention(xn: torch.Tensor, w_qkv: torch.Tensor, b_qkv: torch.Tensor, B:
     else:
         w16, ws = split_w16(w_qkv)
     a.Xn, a.Wqkv, a.bias, a.O = xs.data_ptr(), w16.data_ptr(), b_qkv.data_ptr(), o.data_ptr()
-    a.ldx, a.ldo, a.B, a.N, a.w_scale, a.scale, a.out_f16x2 = N.EMBED, N.EMBED, B, M // B, ws, scale, 1 if out_f16x2 else 0
+    a.ldx, a.ldo, a.B, a.N, a.w_scale, a.scale, a.out_f16x2 = xs.stride(0), o.stride(0), B, M // B, ws, scale, 1 if out_f16x2 else 0
     N.check(N.load().sm_qkv_attention_w16(a, _stream()), "sm_qkv_attention_w16")
     return o
 

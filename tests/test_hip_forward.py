@@ -1,5 +1,6 @@
 """Whole-forward parity of the HIP path (through the C ABI) against (a) the vectors the REAL reference produced
 (tests/golden, made by oracle/gen_golden.py) and (b) the CPU oracle run on this box in fp32 and fp64."""
+import functools
 import glob
 import os
 
@@ -12,6 +13,7 @@ pytestmark = pytest.mark.gpu
 from oracle import selfmask_oracle as O  # noqa: E402  (checker only)
 from selfmask_amd import MaskFormer, synthetic_state_dict, synthetic_images  # noqa: E402
 import _ledger as ledger  # noqa: E402
+import _qkv_attention_cases as QC  # noqa: E402
 
 DEV = "cuda:0"
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -150,7 +152,7 @@ def test_forward_is_deterministic_and_batch_invariant():
     m = _model(16, 0, "soft")
     x = torch.from_numpy(synthetic_images(99, (4, 3, 224, 224))).to(DEV)
     # with the encoder path pinned (as the Evaluator pins it): the automatic choice depends on the batch size - fused QKV +
-    # attention from 16 images up, fc2 split along K below 513 token rows - and those agree to rounding, not to the bit
+    # attention from 16 images up, fc2 split along K below that and below 513 token rows - and those agree to rounding, not to the bit
     m.attention_path = "unfused"
     a = m(x, return_logits=True)
     b = m(x, return_logits=True)
@@ -347,6 +349,77 @@ def test_forward_other_shapes_and_model_sizes_vs_oracle(variant, mode, patch, B,
     if binary:
         assert (out["objectness"].cpu() - ref["objectness"]).abs().max().item() <= 2e-5
     assert (out["features"].cpu() - ref["features"]).abs().max().item() <= 5e-5
+
+
+def _small_grid_model(row):
+    patch, _, _, _, nq, L, _ = row
+    sd, x = QC.forward_inputs(row)
+    m = MaskFormer(n_queries=nq, patch_size=patch, n_decoder_layers=L, return_intermediate=True, use_binary_classifier=True,
+                   gemm_mode="w16")
+    m.load_state_dict(sd, strict=True)
+    return m.to(DEV), x
+
+
+def _oracle_gate(out, ref, pick=None):
+    """the gates of test_forward_other_shapes_and_model_sizes_vs_oracle on the images `pick` of `out` -> (|logit|max, logit error)"""
+    sel = (lambda t: t) if pick is None else (lambda t: t[pick])
+    scale = ref["mask_logits"].abs().max().item()
+    d = (sel(out["mask_logits"]).cpu() - ref["mask_logits"]).abs().max().item()
+    assert sel(out["mask_pred"]).shape == ref["mask_pred"].shape
+    assert scale <= 16.0 and d <= ABS_TOL
+    assert (sel(out["objectness"]).cpu() - ref["objectness"]).abs().max().item() <= 2e-5
+    assert (sel(out["features"]).cpu() - ref["features"]).abs().max().item() <= 5e-5
+    return scale, d
+
+
+@pytest.mark.parametrize("row", QC.FORWARD_ROWS, ids=[QC.forward_id(r) for r in QC.FORWARD_ROWS])
+def test_forward_fused_path_at_small_token_grids(row):
+    """The fused QKV + attention kernel inside the forward at token counts other than 197 - what the Evaluator and the predictor
+    run at --img_size 128 .. 208 with 16 images or more per batch: every row has B * 6 < 96, so only the "fused" pin sends it
+    there, and at most 208 tokens, so the pin does not fall back.  Strict 1e-4 against the CPU oracle (fp32), calib weights; image 1
+    alone gives the bits it has inside the batch; a second call reproduces the first."""
+    m, x = _small_grid_model(row)
+    assert QC.tokens_of(row) <= QC.MAX_TOKENS and row[1] * 6 < 96
+    m.attention_path = "fused"
+    out = m(x.to(DEV), return_logits=True)
+    again = m(x.to(DEV), return_logits=True)
+    assert torch.equal(out["mask_logits"], again["mask_logits"]) and torch.equal(out["objectness"], again["objectness"])
+    one = m(x[1:2].to(DEV), return_logits=True)
+    assert torch.equal(one["mask_logits"][0], out["mask_logits"][1]) and torch.equal(one["objectness"][0], out["objectness"][1])
+    ref = QC.oracle_row(row)
+    d = (out["mask_logits"].cpu() - ref["mask_logits"]).abs().max().item()
+    scale = ref["mask_logits"].abs().max().item()
+    print(f"\n fused pin {QC.forward_id(row)}: N={QC.tokens_of(row)} |logit|max={scale:.2f} hip-oracle32={d:.2e}")
+    ledger.record("forward_fused_small_grids", QC.forward_id(row), {"tokens": QC.tokens_of(row), "logit_absmax": scale, "hip_minus_ref32": d,
+                                                                     "rule": "hip-ref32 <= 1e-4", "err_over_bound": d / ABS_TOL})
+    _oracle_gate(out, ref)
+
+
+@functools.lru_cache(maxsize=None)
+def _auto_and_pinned_at_16_images():
+    """B = 16 at 32 x 32 (96 (image, head) pairs: the batch from which "auto" takes the fused kernel) under "auto" and under "fused" """
+    m, x = _small_grid_model(QC.AUTO_ROW)
+    auto = {k: v.clone() for k, v in m(x.to(DEV), return_logits=True).items()}
+    m.attention_path = "fused"
+    return auto, {k: v.clone() for k, v in m(x.to(DEV), return_logits=True).items()}
+
+
+def test_forward_auto_path_at_16_images_vs_oracle():
+    """the automatic path at the batch where it switches to the fused kernel: images 0 and 15 against the CPU oracle"""
+    row, pick = QC.AUTO_ROW, [0, 15]
+    auto, _ = _auto_and_pinned_at_16_images()
+    scale, d = _oracle_gate(auto, QC.oracle_row(row, tuple(pick)), pick)
+    ledger.record("forward_fused_small_grids", QC.forward_id(row) + "|auto", {"tokens": QC.tokens_of(row), "logit_absmax": scale, "hip_minus_ref32": d,
+                                                                               "rule": "hip-ref32 <= 1e-4", "images": pick, "err_over_bound": d / ABS_TOL})
+
+
+def test_forward_auto_path_at_16_images_has_the_bits_of_the_fused_pin():
+    """From 16 images up "auto" is the large-batch kernel set to the bit, also where the forward has at most 512 token rows (here
+    16 x 5 = 80): the K-split fc2 of the automatic path belongs to the small-batch set only.  (It once followed the row count
+    alone, and "auto" was 9.3e-6 away from the pin at this shape.)"""
+    auto, pinned = _auto_and_pinned_at_16_images()
+    print(f"\n auto vs fused pin, B=16 32x32: max|diff| = {(auto['mask_logits'] - pinned['mask_logits']).abs().max().item():.2e}")
+    assert torch.equal(auto["mask_logits"], pinned["mask_logits"])
 
 
 def test_encoder_only_and_3d_path():
