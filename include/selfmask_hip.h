@@ -442,6 +442,9 @@ int sm_spectral_cluster_dim_f32(const sm_spectral_args* args, int32_t D, void* s
  * method: 0 = as the clusterer chooses, 1 = Gram matrix (whole to 8192 points, above in slabs of 2048 rows, each selected from before
  * the next is formed), 2 = streaming (no n x n array).  n <= 32768.  16 <= n, n % 4 == 0, n_neighbors 2..33.  workspace: sm_knn_workspace_bytes of the same arguments
  * (0 = unsupported), 256-B aligned. */
+#define SM_KNN_AUTO 0   /* `method`: as the clusterer chooses */
+#define SM_KNN_GRAM 1   /* Gram matrix                        */
+#define SM_KNN_STREAM 2 /* streaming                          */
 size_t sm_knn_workspace_bytes(int32_t B, int32_t n, int32_t D, int32_t n_neighbors, int32_t method);
 int sm_knn_f32(const float* features, int32_t B, int32_t n, int32_t D, int32_t n_neighbors, int32_t method, int32_t* idx, void* workspace,
                size_t workspace_bytes, void* stream);
@@ -575,6 +578,8 @@ typedef struct sm_object {
 } sm_object;
 #define SM_OBJ_SUMMARY_INTS 10 /* per image: components before filtering, objects written, segments, overflow flag, the whole mask's
                                 * box x0 y0 x1 y1 (x1 = -1: empty mask), its flags as sm_object.flags, its area */
+#define SM_OBJ_MAX_OBJECTS 64  /* sm_objects_args.max_objects at most */
+#define SM_OBJ_MAX_WIDTH 16384 /* sm_objects_args.max_width at most   */
 typedef struct sm_objects_args {
     const int32_t* starts; const int32_t* info; int32_t cap; /* in: (B, cap) and (B, 2), as sm_predict_args                       */
     const sm_bilateral_image* images;             /* DEVICE table: H and W are read                                               */
@@ -587,8 +592,8 @@ typedef struct sm_objects_args {
                                                   /* written, the rows after them are left untouched                              */
     void* workspace; size_t workspace_bytes;      /* sm_mask_objects_workspace_bytes, 256-B aligned                               */
     int32_t B, mh, mw;
-    int32_t max_width;                            /* >= every W_b, <= 16384                                                       */
-    int32_t connectivity, min_area, max_objects;  /* 4 or 8; >= 0; 1 .. 64                                                        */
+    int32_t max_width;                            /* >= every W_b, <= SM_OBJ_MAX_WIDTH                                            */
+    int32_t connectivity, min_area, max_objects;  /* 4 or 8; >= 0; 1 .. SM_OBJ_MAX_OBJECTS                                        */
     float scale;                                  /* as sm_predict_args                                                           */
 } sm_objects_args;
 int32_t sm_mask_objects_seg_cap(int32_t cap, int32_t max_width); /* rows per image of `segments`; 0: an argument out of range */
@@ -609,7 +614,9 @@ int sm_mask_objects(const sm_objects_args* args, const sm_bilateral_image* image
  * computed nor stored (rgb and lut_rgba are needed with heat_out only).  mask_out is 4-byte, heat_out 16-byte aligned.
  * Nothing is allocated, copied or synchronised; the grids are sized from images_host (the same table on the host), the kernels read
  * images_dev; images of different sizes go in one call and every image's bytes are those of its own single call.  Limits: B <= 65535,
- * 1 <= mh, mw <= 512, H_b * W_b <= 2^24, 0 <= blend_alpha <= 1. */
+ * 1 <= mh, mw <= SM_PRESENT_MAX_MASK, H_b * W_b <= SM_PRESENT_MAX_PIXELS, 0 <= blend_alpha <= 1. */
+#define SM_PRESENT_MAX_MASK 512
+#define SM_PRESENT_MAX_PIXELS (1 << 24)
 typedef struct sm_present_image {
     int64_t img_off;   /* bytes: this image's (H, W, 3) uint8 RGB inside `rgb` (sm_pre_image.off fits as it is)                    */
     int64_t px_off;    /* elements: this image's H*W block inside mask_out; heat_out uses 4*px_off bytes                           */

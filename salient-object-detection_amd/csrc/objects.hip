@@ -27,8 +27,8 @@ namespace sm {
 constexpr int OB_THREADS = 256;
 constexpr int OB_WAVES = OB_THREADS / 64;
 constexpr int OB_LDS_SEGS = 3072;       // five int tables of this length: 60 KiB of the 64 KiB a workgroup gets without opt-in
-constexpr int OB_MAX_OBJECTS = 64;
-constexpr int OB_MAX_WIDTH = 16384;
+constexpr int OB_MAX_OBJECTS = SM_OBJ_MAX_OBJECTS;
+constexpr int OB_MAX_WIDTH = SM_OBJ_MAX_WIDTH;
 constexpr int OB_MAX_PIXELS = 1 << 22;  // as the run kernels
 constexpr int OB_NONE = 0x7fffffff;
 constexpr int OB_MASS_BLOCKS = 256;     // workgroups per image of the mass launch, at most

@@ -23,8 +23,8 @@
 namespace sm {
 
 constexpr int PR_THREADS = 256;
-constexpr int PR_MAX_MASK = 512;
-constexpr int PR_MAX_PIXELS = 1 << 24;
+constexpr int PR_MAX_MASK = SM_PRESENT_MAX_MASK;
+constexpr int PR_MAX_PIXELS = SM_PRESENT_MAX_PIXELS;
 
 __host__ __device__ __forceinline__ int pr_pitch(int max_w) { return (max_w + 3) & ~3; }
 

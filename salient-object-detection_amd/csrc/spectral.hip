@@ -1725,11 +1725,11 @@ static int sp_knn_lists(const float* features, int B, int n, int D, int m, int p
     return SM_OK;
 }
 
-// method 0 / 1 / 2 -> the path, -1 = no such method
+// method SM_KNN_* -> the path, -1 = no such method
 static int knn_path(int n, int D, int method) {
-    if (method == 0) return sp_auto_path(n, D);
-    if (method == 1) return n <= SP_MAXN ? KNN_GRAM : KNN_SLABS;
-    return method == 2 ? KNN_STREAM : -1;
+    if (method == SM_KNN_AUTO) return sp_auto_path(n, D);
+    if (method == SM_KNN_GRAM) return n <= SP_MAXN ? KNN_GRAM : KNN_SLABS;
+    return method == SM_KNN_STREAM ? KNN_STREAM : -1;
 }
 
 }  // namespace sm

@@ -12,7 +12,8 @@ LIB_PATH = os.environ.get("SM_HIP_LIB") or os.path.normpath(os.path.join(_HERE, 
 
 EMBED, HEADS, HEAD_DIM, MLP, ENC_DEPTH, MAX_DEC_LAYERS = 384, 6, 64, 1536, 12, 8
 RESNET_EMBED = 2048                       # features per point of a ResNet type (the clusterers' other width)
-KNN_METHODS = {"auto": 0, "gram": 1, "stream": 2}  # sm_knn_f32's `method`
+KNN_AUTO, KNN_GRAM, KNN_STREAM = range(3)  # sm_knn_f32's `method`
+KNN_METHODS = {"auto": 0, "gram": 1, "stream": 2}
 EPI_BIAS, EPI_GELU, EPI_RELU, EPI_RESIDUAL, EPI_SIGMOID2, EPI_PATCH, EPI_RESIDUAL_LN = range(7)
 
 fp = C.c_void_p  # device pointers travel as integers (tensor.data_ptr())
@@ -233,6 +234,19 @@ class ResnetBlock(C.Structure):
 class Resnet50Weights(C.Structure):
     _fields_ = [("stem", ConvWeight), ("block", ResnetBlock * RESNET50_BLOCKS)]
 
+
+# every struct include/selfmask_hip.h defines: typedef name -> its mirror (constants pair by name: macro SM_X <-> X here)
+STRUCTS = {
+    "sm_gemm_args": GemmArgs, "sm_row_map": RowMap, "sm_ln_args": LnArgs, "sm_attn_args": AttnArgs,
+    "sm_attn_probs_args": AttnProbsArgs, "sm_qkv_attn_args": QkvAttnArgs, "sm_pre_image": PreImage, "sm_eval_image": EvalImage,
+    "sm_eval_args": EvalArgs, "sm_spectral_args": SpectralArgs, "sm_bilateral_args": BilateralArgs,
+    "sm_bilateral_image": BilateralImage, "sm_predict_args": PredictArgs, "sm_object": Object, "sm_objects_args": ObjectsArgs,
+    "sm_present_image": PresentImage, "sm_jpeg_info": JpegInfo, "sm_jpeg_image": JpegImage, "sm_jpeg_segment": JpegSegment,
+    "sm_jpeg_scan": JpegScan, "sm_png_image": PngImage, "sm_png_info": PngInfo, "sm_png_stream": PngStream,
+    "sm_enc_layer": EncLayer, "sm_dec_layer": DecLayer, "sm_weights": Weights, "sm_forward_io": ForwardIO,
+    "sm_conv_weight": ConvWeight, "sm_resnet_block": ResnetBlock, "sm_resnet50_weights": Resnet50Weights,
+    "sm_kernel_time": KernelTime,
+}
 
 # every symbol include/selfmask_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {

@@ -1,5 +1,6 @@
-"""CPU-only checks of the drop-in boundary: the C-ABI library loads and exports every symbol include/*.h declares,
-the ctypes structs match the header layout, and the host mirror keeps the reference's state_dict contract."""
+"""CPU-only checks of the drop-in boundary: the C-ABI library loads and exports every symbol include/*.h declares, the
+whole ctypes mirror - every struct, field, prototype and constant of selfmask_amd/_native.py - is what a compiler sees in
+the header (tests/_abi_probe.py), and the host mirror keeps the reference's state_dict contract."""
 import ctypes
 import os
 import re
@@ -7,6 +8,7 @@ import re
 import pytest
 import torch
 
+import _abi_probe as P
 from selfmask_amd import _native as N
 from selfmask_amd import MaskFormer, get_model, BaseStructure, state_shapes, synthetic_state_dict
 
@@ -24,37 +26,54 @@ def test_library_exports_every_declared_symbol():
     assert lib.sm_version() >= 100
 
 
-def test_struct_sizes_match_header_layout(tmp_path):
-    """sizeof()/offsetof() as the C compiler sees the header vs the ctypes mirrors (gcc is part of the image)."""
-    import shutil
-    import subprocess
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if cc is None:
-        pytest.skip("no C compiler")
-    pairs = {"sm_gemm_args": N.GemmArgs, "sm_ln_args": N.LnArgs, "sm_attn_args": N.AttnArgs, "sm_weights": N.Weights,
-             "sm_forward_io": N.ForwardIO, "sm_eval_args": N.EvalArgs, "sm_eval_image": N.EvalImage,
-             "sm_bilateral_args": N.BilateralArgs, "sm_enc_layer": N.EncLayer, "sm_dec_layer": N.DecLayer,
-             "sm_row_map": N.RowMap, "sm_kernel_time": N.KernelTime, "sm_qkv_attn_args": N.QkvAttnArgs, "sm_pre_image": N.PreImage,
-             "sm_spectral_args": N.SpectralArgs}
-    last = {"sm_gemm_args": "mfma_terms", "sm_ln_args": "chain_eps", "sm_attn_args": "scale", "sm_weights": "no_objectness",
-            "sm_forward_io": "last_layer_only", "sm_eval_args": "scale", "sm_bilateral_args": "W", "sm_qkv_attn_args": "mfma_terms", "sm_pre_image": "ksy",
-            "sm_spectral_args": "kmeans_max_iter"}
-    src = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{os.path.join(REPO, "include", "selfmask_hip.h")}"',
-           'int main(void){']
-    for cname in pairs:
-        src.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
-    for cname, field in last.items():
-        src.append(f'printf("{cname}.{field} %zu\\n", offsetof({cname}, {field}));')
-    src.append('return 0;}')
-    c = tmp_path / "sz.c"
-    c.write_text("\n".join(src))
-    exe = tmp_path / "sz"
-    subprocess.run([cc, "-o", str(exe), str(c)], check=True)
-    out = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    for cname, ct in pairs.items():
-        assert int(out[cname]) == ctypes.sizeof(ct), (cname, out[cname], ctypes.sizeof(ct))
-    for cname, field in last.items():
-        assert int(out[f"{cname}.{field}"]) == getattr(pairs[cname], field).offset, (cname, field)
+def test_every_header_struct_has_one_mirror():
+    assert set(P.header_structs()) == set(N.STRUCTS), set(P.header_structs()) ^ set(N.STRUCTS)
+    defined = {c for c in vars(N).values() if isinstance(c, type) and issubclass(c, ctypes.Structure) and c.__module__ == N.__name__}
+    assert defined == set(N.STRUCTS.values()), defined ^ set(N.STRUCTS.values())
+
+
+def test_mirror_equals_what_the_compiler_sees():
+    """struct: sizeof and alignof; field: offset, kind and element count; proto: the kinds of the return value and of every parameter
+    (ctypes converts a Python number to whatever argtypes says, so a c_int32 where the header has int64_t never raises)"""
+    for what in ("struct", "field", "proto"):
+        c, py = P.header()[what], P.mirror()[what]
+        assert c.keys() == py.keys(), what
+        wrong = {k: {"header": c[k], "mirror": py[k]} for k in c if c[k] != py[k]}
+        assert not wrong, (what, wrong)
+
+
+def test_field_names_in_header_order():
+    """a trailing field that tail padding hides, or two same-typed neighbours swapped, move no offset the layout test looks at"""
+    hdr = P.header_structs()
+    for cname, ct in N.STRUCTS.items():
+        assert hdr[cname] == [f for f, _ in ct._fields_], cname
+
+
+# macros the binding has no use for; every other SM_X of the header is the module's X
+UNMIRRORED = {"SM_OK", "SM_EINVAL", "SM_ELAUNCH", "SM_ENOSPACE", "SM_JPEG_MAX_SCAN_BYTES", "SM_JPEG_SUBSEQ_BITS_MAX", "SM_PNG_MAX_DATA_BYTES"}
+
+
+def test_every_header_macro_is_mirrored_or_listed():
+    c, py = P.header()["macro"], P.mirror()["macro"]
+    assert set(c) - set(py) == UNMIRRORED, (set(c) - set(py)) ^ UNMIRRORED
+    wrong = {m: {"header": c[m], "mirror": py[m]} for m in py if c[m] != py[m]}
+    assert not wrong, wrong
+    assert N.KNN_METHODS == {"auto": N.KNN_AUTO, "gram": N.KNN_GRAM, "stream": N.KNN_STREAM}
+
+
+def test_pinned_values_on_both_sides():
+    """the literal numbers the features' own tests used to pin: a change made on both sides at once still fails here"""
+    c = P.header()
+    for cname, size in {"sm_present_image": 40, "sm_png_image": 48, "sm_object": 56, "sm_jpeg_segment": 16, "sm_jpeg_scan": 160,
+                        "sm_jpeg_image": 64}.items():
+        assert c["struct"][cname][0] == ctypes.sizeof(N.STRUCTS[cname]) == size, cname
+    for macro, value in {"SM_PNG_STREAM_MAGIC": 0x474e5073, "SM_PNG_MAX_PIXELS": 1 << 24, "SM_OBJ_SUMMARY_INTS": 10,
+                         "SM_RESNET50_BLOCKS": 16}.items():
+        assert c["macro"][macro] == getattr(N, macro[3:]) == value, macro
+    # the attention-map fields were appended at the END: nothing in front of them moved
+    last3 = ["last_attn", "last_attn_cls", "attn_only"]
+    assert P.header_structs()["sm_forward_io"][-3:] == [f for f, _ in N.ForwardIO._fields_][-3:] == last3
+    assert N.PNG_UNSUPPORTED != N.JPEG_UNSUPPORTED  # the two decoders' "hand it to Pillow" verdicts stay apart
 
 
 def test_argument_validation_without_gpu():

@@ -1,10 +1,6 @@
 """CPU-only checks of the attention-map surface: the fp64 restatement (tests/_attention_ref.py) against the reference's own fp64
-vectors, the new ABI fields and their validation, and the state_dict contract after the encoder gained its method."""
-import ctypes
-import os
-import shutil
-import subprocess
-
+vectors, the validation of the new ABI fields (their layout: tests/test_abi_cpu.py), and the state_dict contract after the encoder
+gained its method."""
 import numpy as np
 import pytest
 import torch
@@ -12,8 +8,6 @@ import torch
 import _attention_ref as R
 from selfmask_amd import _native as N
 from selfmask_amd import MaskFormer, state_shapes
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize("name", R.FIXTURES)
@@ -31,29 +25,6 @@ def test_fp64_restatement_matches_reference_fp64(name):
         d32 = max(d32, np.abs(fx.rows_f32.astype(np.float64) - fx.rows_f64).max())
     assert d32 <= fx.bar
     assert np.abs(a.sum(-1) - 1).max() <= 1e-12
-
-
-def test_new_structs_match_header_layout(tmp_path):
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if cc is None:
-        pytest.skip("no C compiler")
-    fields = {"sm_forward_io": (N.ForwardIO, ["last_layer_only", "last_attn", "last_attn_cls", "attn_only"]),
-              "sm_attn_probs_args": (N.AttnProbsArgs, [f[0] for f in N.AttnProbsArgs._fields_])}
-    src = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{os.path.join(REPO, "include", "selfmask_hip.h")}"', 'int main(void){']
-    for cname, (_ct, names) in fields.items():
-        src.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
-        src += [f'printf("{cname}.{f} %zu\\n", offsetof({cname}, {f}));' for f in names]
-    src.append('return 0;}')
-    (tmp_path / "sz.c").write_text("\n".join(src))
-    subprocess.run([cc, "-o", str(tmp_path / "sz"), str(tmp_path / "sz.c")], check=True)
-    out = dict(line.split() for line in subprocess.run([str(tmp_path / "sz")], check=True, capture_output=True, text=True).stdout.splitlines())
-    for cname, (ct, names) in fields.items():
-        assert int(out[cname]) == ctypes.sizeof(ct), cname
-        for f in names:
-            assert int(out[f"{cname}.{f}"]) == getattr(ct, f).offset, (cname, f)
-    # appended at the END: nothing in front of them moved
-    assert N.ForwardIO.last_attn.offset > N.ForwardIO.last_layer_only.offset
-    assert [f[0] for f in N.ForwardIO._fields_][-3:] == ["last_attn", "last_attn_cls", "attn_only"]
 
 
 def _weights():

@@ -191,10 +191,8 @@ def test_size_against_a_zlib_model_of_the_scheme(name, a):
 
 # ---- the C ABI's host half (no GPU: every check below returns before a launch) -------------------------------------------------------------
 def test_abi_bound_workspace_and_range_checks():
-    import ctypes
     from selfmask_amd import _native as N
     lib = N.load()
-    assert ctypes.sizeof(N.PngImage) == 48
     for H, W, C in ((1, 1, 1), (17, 23, 3), (300, 400, 4), (4096, 4096, 4), (1, 1 << 24, 1)):
         assert lib.sm_png_bound(H, W, C) == png.bound(H, W, C) > 0
     assert lib.sm_png_bound(5, 6, 2) == 0 and lib.sm_png_bound(0, 6, 3) == 0 and lib.sm_png_bound(4097, 4096, 1) == 0

@@ -2,9 +2,6 @@
 C ABI of the fused finish, its host-side validation, the planner's refusals and the multi-rank branch.  The device half runs in
 tests/test_hip_predict.py and tests/test_hip_predictor.py."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,8 +12,6 @@ from selfmask_amd import MaskFormer, _native as N
 from selfmask_amd.distributed import shard_indices
 from selfmask_amd.mask_generator import rle_decode, rle_encode
 from selfmask_amd.predictor import SaliencyPredictor, build_parser
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # ---- the restatement's known answers ------------------------------------------------------------------------------------------
@@ -50,24 +45,7 @@ def test_rle_round_trip_mixed_sizes(seed):
         assert np.array_equal(rle_decode(rle_encode(m)), m)
 
 
-# ---- C ABI ----------------------------------------------------------------------------------------------------------------------
-def test_predict_args_layout_matches_header(tmp_path):
-    gcc = shutil.which("gcc") or shutil.which("cc")
-    assert gcc, "a C compiler is part of the image"
-    fields = [f for f, _ in N.PredictArgs._fields_]
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "selfmask_hip.h"\nint main(void) {\n'
-                   '  printf("sizeof %zu\\n", sizeof(sm_predict_args));\n' +
-                   "".join(f'  printf("{f} %zu\\n", offsetof(sm_predict_args, {f}));\n' for f in fields) + "  return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.run([gcc, "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)], check=True)
-    out = dict(ln.split() for ln in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(out["sizeof"]) == C.sizeof(N.PredictArgs)
-    assert int(out["scale"]) == N.PredictArgs.scale.offset
-    for f in fields:
-        assert int(out[f]) == getattr(N.PredictArgs, f).offset, f
-
-
+# ---- C ABI (its layout: tests/test_abi_cpu.py) ----------------------------------------------------------------------------------
 def _err(lib):
     return (lib.sm_last_error() or b"").decode()
 

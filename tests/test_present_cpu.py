@@ -1,9 +1,7 @@
 """CPU-only checks of the response's images (selfmask_amd/present.py, csrc/present.hip): the integer restatement equals Pillow and
-matplotlib bit for bit, the colour table is pinned, and the new C ABI is exported, laid out as its ctypes mirror and validated on the
-host before any launch."""
-import ctypes
+matplotlib bit for bit, the colour table is pinned, and the C ABI's arguments are validated on the host before any launch (its
+layout and exports: tests/test_abi_cpu.py)."""
 import hashlib
-import os
 
 import numpy as np
 import pytest
@@ -12,7 +10,6 @@ from selfmask_amd import _native as N
 from selfmask_amd import present as P
 from _present_cases import KINDS, SHAPES, make_case, pil_heat, pil_mask
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = [(i, k) for i in range(len(SHAPES)) for k in KINDS]
 
 
@@ -88,33 +85,10 @@ def test_pinned_table_digest():
 
 def test_library_exports_the_present_symbols():
     lib = N.load()
-    for name in ("sm_present_masks_u8", "sm_present_workspace_bytes"):
-        assert hasattr(lib, name) and name in N.SYMBOLS
     assert lib.sm_present_workspace_bytes(1, 28, 400) >= 28 * 400
     assert lib.sm_present_workspace_bytes(3, 56, 1920) >= 3 * 56 * 1920
     for bad in ((0, 28, 400), (1, 0, 400), (1, 513, 400), (1, 28, 0), (65536, 28, 400)):
         assert lib.sm_present_workspace_bytes(*bad) == 0
-
-
-def test_present_image_layout_matches_header(tmp_path):
-    import shutil
-    import subprocess
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if cc is None:
-        pytest.skip("no C compiler")
-    fields = [f for f, _ in N.PresentImage._fields_]
-    src = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{os.path.join(REPO, "include", "selfmask_hip.h")}"', 'int main(void){',
-           'printf("sizeof %zu\\n", sizeof(sm_present_image));']
-    src += [f'printf("{f} %zu\\n", offsetof(sm_present_image, {f}));' for f in fields]
-    src.append('return 0;}')
-    c = tmp_path / "present_layout.c"
-    c.write_text("\n".join(src))
-    exe = tmp_path / "present_layout"
-    subprocess.run([cc, "-o", str(exe), str(c)], check=True)
-    out = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(out["sizeof"]) == ctypes.sizeof(N.PresentImage) == 40
-    for f in fields:
-        assert int(out[f]) == getattr(N.PresentImage, f).offset, f
 
 
 def _valid_call():

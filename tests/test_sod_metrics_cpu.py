@@ -1,8 +1,6 @@
 """E-measure and weighted F-measure: the numpy definition (selfmask_amd/sod_metrics.py) against brute-force per-pixel
 restatements and against the SciPy chain the toolkits use, and the C ABI of sm_sod_metrics_u8 as far as it goes without a GPU."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
@@ -11,7 +9,6 @@ import _sod_metrics_ref as R
 from selfmask_amd import _native as N
 from selfmask_amd import sod_metrics as S
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL = R.small_cases()
 
 
@@ -120,22 +117,7 @@ def test_sod_metrics_row_and_argument_checks():
     assert abs(perfect[3] - 1.0) < 1e-12 and abs(perfect[2] - 600.0 / 599.0) < 1e-12
 
 
-# ---- ABI ----
-NEW = ("sm_sod_metrics_workspace_bytes", "sm_sod_metrics_u8", "sm_upsample_selected_u8")
-
-
-def test_symbols_match_the_header():
-    hdr = open(os.path.join(REPO, "include", "selfmask_hip.h")).read()
-    declared = set(re.findall(r"\b(sm_[a-z0-9_]+)\s*\(", hdr))
-    lib = N.load()
-    for name in NEW:
-        assert name in declared and name in N.SYMBOLS and hasattr(lib, name), name
-    # the prototypes' argument counts are the bound ones
-    for name in NEW:
-        proto = re.search(r"^(?:int|size_t) " + name + r"\(([^;]*)\);", hdr, re.M).group(1)
-        assert len(proto.split(",")) == len(N.SYMBOLS[name][1]), name
-
-
+# ---- ABI (its prototypes and exports: tests/test_abi_cpu.py) ----
 def test_workspace_grows_with_batch_and_pixels():
     lib = N.load()
     f = lib.sm_sod_metrics_workspace_bytes
