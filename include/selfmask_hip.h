@@ -912,6 +912,40 @@ size_t sm_forward_workspace_bytes(const sm_weights* w, int32_t B, int32_t H, int
 int sm_maskformer_forward(const sm_weights* w, const sm_forward_io* io, void* workspace, size_t workspace_bytes,
                           void* stream);
 
+/* ---- encoder taps: tokens and attention of every DINO block ------------------------------------------------------------------
+ * What VisionTransformer.forward's dict layer1 .. layer12 (vision_transformer.py:293-304) and the feature-extraction family around it
+ * (get_tokens :316-357, forward_features :359-375, forward_selfattention :403-446, forward_return_n_last_blocks :448-471,
+ * return_patch_emb_from_n_last_blocks :473-497) select.  All of it is defined on prepare_tokens' tokens (:269-281: zero-padded to the
+ * patch size, position table interpolated to the token grid); N = 1 + gh*gw tokens per image, n = gh*gw patch rows.
+ * The residual stream lies in the workspace after every block: a tap is a launch that only reads it.  With any set of taps (and
+ * stop == 0) every output of sm_forward_io keeps its bits, and a forward afterwards finds the workspace in no other state. */
+#define SM_TAP_ALL 0   /* `select`: all N tokens, R = N */
+#define SM_TAP_CLS 1   /*           the CLS row only, R = 1 */
+#define SM_TAP_PATCH 2 /*           the n patch rows only, R = n */
+typedef struct sm_encoder_taps {
+    uint32_t layer_mask; /* bit i: the output of block i + 1 (i = 0 .. 11), stacked in ascending block order */
+    int32_t select;      /* SM_TAP_*: the rows of every token output below */
+    int32_t norm;        /* 1: encoder.norm applied (the dict, get_tokens(norm=True)), the bits sm_layernorm_rows_f32 gives the row;
+                            0: the raw residual stream */
+    float* tokens;       /* (B, n_taps, R, 384), n_taps = bits set in layer_mask; NULL when layer_mask == 0 */
+    float* post_pe;      /* (B, R, 384) the stream after the position embedding (get_tokens(post_pe=True)), or NULL */
+    float* input_tokens; /* (B, R, 384) cat(cls_token, patch_embed(x)) before the position embedding, or NULL */
+    float* patch_mean;   /* (B, 384) mean over the patch rows of norm(x) of block 12 (return_patch_avgpool), or NULL: one fixed
+                            summation order, an image's values do not depend on the batch it is in */
+    uint32_t attn_mask;  /* bit i: the post-softmax attention of block i + 1 (as sm_forward_io.last_attn for block 12) */
+    float* attn;         /* (n_attn, B, 6, N, N), n_attn = bits set in attn_mask, ascending block order, or NULL */
+    float* attn_cls;     /* (n_attn, B, 6, N): row 0 of each, or NULL */
+    int32_t stop;        /* 1: return right after the last requested block's taps (patch_mean counts as block 12) - the rest of the
+                            encoder and the decoder are not launched, every output pointer of sm_forward_io may be NULL and its
+                            last_attn / last_attn_cls / attn_only must be unset */
+} sm_encoder_taps;
+
+/* sm_maskformer_forward with taps; taps == NULL is sm_maskformer_forward itself (same launches, same bits).  gemm_mode 0, 1, 2
+ * (3 -> SM_EINVAL).  SM_EINVAL as well for: nothing requested, a bit >= 12 in a mask, a non-empty mask without a destination (or a
+ * destination without its mask), select / norm / stop out of range, sm_forward_io.attn_only together with taps. */
+int sm_maskformer_forward_taps(const sm_weights* w, const sm_forward_io* io, const sm_encoder_taps* taps, void* workspace,
+                               size_t workspace_bytes, void* stream);
+
 /* ---- dilated ResNet-50 backbone: the MoCo-v2 / SwAV feature branch of the pseudo-mask generator -------------------------------
  * (mask_generator.pyc@L136-200 feature_types "mocov2" / "swav"; utils/misc.py:220-223 -> networks/resnet.py:8-56 ->
  * resnet_backbone.py:42-105 "resnet50_dilated8" -> resnet_models.py:57-154).  Activations are NHWC, one row per pixel, fp32 or F16X2;

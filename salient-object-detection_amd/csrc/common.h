@@ -280,6 +280,20 @@ struct TapGuard {
     ~TapGuard() { tap_end(h); }
 };
 
+// encoder taps (encoder_taps.hip), queued by forward.hip.  Rows [row0, row0 + R) of every image of src (B, N, 384) go, normed by
+// gamma / beta (NULL: as they lie) to dst + b * dst_image + j * 384
+struct EncoderTapRows {
+    const float* src;
+    float* dst;
+    const float *gamma, *beta;
+    int64_t dst_image;  // floats between the images' slots of dst
+    int B, N, row0, R;
+    float eps;
+};
+int encoder_tap_rows(const EncoderTapRows& a, hipStream_t st);
+int encoder_patch_mean(const float* tok, float* mean, int B, int n, hipStream_t st);  // (B, n, 384) -> (B, 384), fixed order
+int encoder_tap_zero(float* dst, int64_t nfloat, hipStream_t st);
+
 }  // namespace sm
 
 const char* sm_qkv_attention_kernel_name(int mfma_terms);  // qkv_attention.hip: rocprofv3 name of the fused kernel that is launched

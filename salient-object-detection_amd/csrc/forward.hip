@@ -249,6 +249,7 @@ struct Fwd {
     static constexpr int D = SM_EMBED;
     const sm_weights* w;
     const sm_forward_io* io;
+    const sm_encoder_taps* tp;  // encoder taps, or NULL: then every launch below is the plain forward's
     Shape s;
     Ws ws;
     Ctx c;
@@ -258,8 +259,11 @@ struct Fwd {
     const float* qd_a;   // ... and their GEMM-operand view
 
     int tokens() const;
-    int encoder() const;  // returns inside block 12 when io->attn_only
-    int last_attention(const sm_gemm_args& qkv) const;
+    int encoder() const;  // returns inside block 12 when io->attn_only, after the last requested tap when tp->stop
+    int block_attention(int i, const sm_gemm_args& qkv) const;
+    // encoder taps (sm_encoder_taps): launches that only read
+    int tap_rows(const float* src, float* dst, int slot, int slots, bool norm) const;
+    int tap_input_tokens() const;
     int decoder() const;
     int heads() const;
     // the steps of a decoder layer (transformer_decoder.py:260-327); `tgt` is the fp32 residual stream
@@ -287,13 +291,43 @@ int Fwd::tokens() const {
     const int K = 3 * s.P * s.P;
     sm_gemm_args g = linear_args(cols, K, w->patch_w, w->patch_s, w->patch_b, ws.X, D, s.Mp, D, K, SM_EPI_PATCH, pos, D);
     g.patch_n = s.n;
-    return gemm(c, g);
+    TRY(gemm(c, g));
+    if (tp && tp->post_pe) TRY(tap_rows(ws.X, tp->post_pe, 0, 1, false));
+    if (tp && tp->input_tokens) TRY(tap_input_tokens());
+    return SM_OK;
 }
 
-// The last block's attention matrix (sm_forward_io.last_attn / last_attn_cls; vision_transformer.py:307-314): Q|K of block 12 -
-// rows [0, 768) of its qkv weight, a prefix of the same tensor in every weight format, with the same fold arguments - into
-// ws.QKV as (M, 768), then the probabilities kernel once per requested output.  `qkv` is the block's own qkv projection.
-int Fwd::last_attention(const sm_gemm_args& qkv) const {
+// Rows `select` picks of src (B, N, 384) - the stream where it lies - into slot `slot` of a (B, slots, R, 384) stack, through the
+// final norm or as they are
+int Fwd::tap_rows(const float* src, float* dst, int slot, int slots, bool norm) const {
+    EncoderTapRows a = {};
+    a.row0 = tp->select == SM_TAP_PATCH ? 1 : 0;
+    a.R = tp->select == SM_TAP_ALL ? s.N : tp->select == SM_TAP_CLS ? 1 : s.n;
+    a.src = src; a.dst = dst + (int64_t)slot * a.R * D; a.dst_image = (int64_t)slots * a.R * D;
+    a.B = s.B; a.N = s.N; a.eps = 1e-6f;
+    if (norm) { a.gamma = w->enc_norm_w; a.beta = w->enc_norm_b; }
+    return encoder_tap_rows(a, c.st);
+}
+
+// cat(cls_token, patch_embed(x)) before the position embedding (get_tokens(input_tokens=True), vision_transformer.py:329-336): the
+// patch epilogue once more over the im2col columns still in ws.HID, with a zeroed position table (the head of ws.QKV) and ws.Xn
+// as the destination - both free until block 1's norm1 - so ws.X is not disturbed; then the selected rows to the caller
+int Fwd::tap_input_tokens() const {
+    float *zero = ws.QKV, *T = ws.Xn;
+    TRY(encoder_tap_zero(zero, (int64_t)s.N * D, c.st));
+    TRY(sm_cls_rows_f32(w->cls_token, zero, T, s.B, s.N, c.st));
+    const int K = 3 * s.P * s.P;
+    sm_gemm_args g = linear_args(ws.HID, K, w->patch_w, w->patch_s, w->patch_b, T, D, s.Mp, D, K, SM_EPI_PATCH, zero, D);
+    g.patch_n = s.n;
+    TRY(gemm(c, g));
+    return tap_rows(T, tp->input_tokens, 0, 1, false);
+}
+
+// Block i + 1's attention matrix (sm_forward_io.last_attn / last_attn_cls for block 12, vision_transformer.py:307-314;
+// sm_encoder_taps.attn / attn_cls for any block, :433-439): Q|K of the block - rows [0, 768) of its qkv weight, a prefix of the same
+// tensor in every weight format, with the same fold arguments - into ws.QKV as (M, 768), then the probabilities kernel once per
+// requested output.  `qkv` is the block's own qkv projection.
+int Fwd::block_attention(int i, const sm_gemm_args& qkv) const {
     float* QK = ws.QKV;
     sm_gemm_args g = qkv;
     g.N = g.ldc = 2 * D;
@@ -309,10 +343,16 @@ int Fwd::last_attention(const sm_gemm_args& qkv) const {
     a.Q = QK; a.K = QK + D;
     a.sQb = a.sKb = (int64_t)s.N * 2 * D; a.sQr = a.sKr = 2 * D;
     a.batch = s.B; a.heads = SM_HEADS; a.n_q = s.N; a.n_k = s.N; a.scale = 0.125f;
-    for (int pass = 0; pass < 2; ++pass) {
-        a.P = pass ? io->last_attn_cls : io->last_attn;
+    const bool last = i + 1 == SM_ENC_DEPTH, tapped = tp && (tp->attn_mask >> i & 1u);
+    const int64_t slot = tapped ? __builtin_popcount(tp->attn_mask & ((1u << i) - 1u)) : 0;  // blocks stack in ascending order
+    const int64_t per_block = (int64_t)s.B * SM_HEADS * s.N;  // rows of one block's slot
+    float* const dst[4] = {last ? io->last_attn : nullptr, last ? io->last_attn_cls : nullptr,
+                           tapped && tp->attn ? tp->attn + slot * per_block * s.N : nullptr,
+                           tapped && tp->attn_cls ? tp->attn_cls + slot * per_block : nullptr};
+    for (int pass = 0; pass < 4; ++pass) {
+        a.P = dst[pass];
         if (!a.P) continue;
-        a.q0 = 0; a.nq = pass ? 1 : s.N;
+        a.q0 = 0; a.nq = pass & 1 ? 1 : s.N;
         // both walks over the keys count: 2 x (2 nq n_k 64) per head; bytes: Q, K once + P
         TapGuard tap(c.st, "attention_probs_f16x2_kernel", 4.0 * s.B * SM_HEADS * a.nq * (double)s.N * SM_HEAD_DIM,
                      4.0 * s.B * SM_HEADS * (SM_HEAD_DIM * ((double)a.nq + s.N) + (double)a.nq * s.N));
@@ -354,6 +394,17 @@ int Fwd::encoder() const {
         a.ys = S ? ws.Xn : nullptr;
         return ln(c, a);
     };
+    // taps: which blocks' outputs / attention are asked for, and with tp->stop the block the forward returns in - after its token
+    // tap (stop_tok; patch_mean needs block 12's) or, when the last thing asked for is an attention, right after that (stop_attn)
+    const uint32_t lmask = tp ? tp->layer_mask : 0u, amask = tp ? tp->attn_mask : 0u;
+    const int n_layers = __builtin_popcount(lmask);
+    int stop_tok = -1, stop_attn = -1;
+    if (tp && tp->stop) {
+        const int hi_tok = tp->patch_mean ? SM_ENC_DEPTH - 1 : lmask ? 31 - __builtin_clz(lmask) : -1;
+        const int hi_attn = amask ? 31 - __builtin_clz(amask) : -1;
+        if (hi_tok < 0 && hi_attn < 0) return SM_OK;  // only post_pe / input_tokens: written by tokens()
+        if (hi_attn > hi_tok) stop_attn = hi_attn; else stop_tok = hi_tok;
+    }
     for (int i = 0; i < SM_ENC_DEPTH; ++i) {
         const sm_enc_layer& e = w->enc[i];
         const bool last = i + 1 == SM_ENC_DEPTH;
@@ -363,10 +414,11 @@ int Fwd::encoder() const {
         sm_gemm_args qkv = linear_args(ws.Xn, D, f1 ? e.qkv_fw : e.qkv_w, f1 ? e.qkv_fs : e.qkv_s, f1 ? e.qkv_fb : e.qkv_b, ws.QKV,
                                        3 * D, s.M, 3 * D, D, SM_EPI_BIAS);
         if (f1) { qkv.ln_stats = ws.ST; qkv.ln_c = e.qkv_c; qkv.ln_eps = 1e-6f; }
-        if (last && (io->last_attn || io->last_attn_cls)) {
-            // ws.HID is free here (block 11's fc2 has consumed it), ws.QKV is rewritten by this block's own projection below
-            TRY(last_attention(qkv));
-            if (io->attn_only) return SM_OK;
+        if ((last && (io->last_attn || io->last_attn_cls)) || (amask >> i & 1u)) {
+            // ws.HID is free here (the previous block's fc2 - for block 1 the patch GEMM - has consumed it), ws.QKV is rewritten by
+            // this block's own projection below
+            TRY(block_attention(i, qkv));
+            if ((last && io->attn_only) || i == stop_attn) return SM_OK;
         }
         if (fused_qkv) {
             sm_qkv_attn_args q = {};
@@ -401,13 +453,20 @@ int Fwd::encoder() const {
             if (lnf && !last) { fc2.C2 = ws.Xn; fc2.ln_stats_out = ws.ST; }
             TRY(gemm(c, fc2));
         }
+        // ws.X is block i + 1's output from here until the next block's proj
+        if (lmask >> i & 1u) TRY(tap_rows(ws.X, tp->tokens, __builtin_popcount(lmask & ((1u << i) - 1u)), n_layers, tp->norm != 0));
+        if (i == stop_tok && !tp->patch_mean) return SM_OK;  // (patch_mean stops behind the final norm below)
     }
     // final norm on the last layer only (the other 11 per-layer norms of :299 are dead work when
-    // lateral_connection=False), dropping the cls row on the way (maskformer.py:107-108,177)
+    // lateral_connection=False: a caller who wants them asks through sm_encoder_taps), dropping the cls row on the way
+    // (maskformer.py:107-108,177)
     sm_ln_args a = ln_args(ws.X, w->enc_norm_w, w->enc_norm_b, tok, s.Mp, 1e-6f);
     a.in_map = {s.n, s.N, 1};
     a.ys = S ? ws.TOKs : nullptr;
-    return ln(c, a);
+    TRY(ln(c, a));
+    // return_patch_avgpool (vision_transformer.py:466-470): the mean of exactly these rows
+    if (tp && tp->patch_mean) TRY(encoder_patch_mean(tok, tp->patch_mean, s.B, s.n, c.st));
+    return SM_OK;
 }
 
 // ---- decoder layers (transformer_decoder.py:260-327) -----------------------------------------------------------------
@@ -564,21 +623,21 @@ int Fwd::heads() const {
 
 }  // namespace
 
-static int forward(const sm_weights* w, const sm_forward_io* io, float* wsbase, hipStream_t st) {
+static int forward(const sm_weights* w, const sm_forward_io* io, const sm_encoder_taps* tp, float* wsbase, hipStream_t st) {
     const Shape s = make_shape(w, io->B, io->H, io->W);
     const Ws ws = carve(s, wsbase);
     const Ctx c = {w->gemm_mode >= 1, w->gemm_mode >= 2, st, w->gemm_mode == 3 ? 1 : 3};
     float* tok = io->patch_tokens ? io->patch_tokens : ws.TOK;
     float* QD = io->queries ? io->queries : ws.QD;
-    const Fwd f = {w, io, s, ws, c, tok, c.S ? ws.TOKs : tok, QD, c.S ? ws.QDs : QD};
+    const Fwd f = {w, io, tp, s, ws, c, tok, c.S ? ws.TOKs : tok, QD, c.S ? ws.QDs : QD};
     TRY(f.tokens());
     TRY(f.encoder());
-    if (io->attn_only || io->encoder_only) return SM_OK;  // attn_only: the encoder returned inside block 12
+    if (io->attn_only || io->encoder_only || (tp && tp->stop)) return SM_OK;  // attn_only / stop: the encoder returned early
     TRY(f.decoder());
     return f.heads();
 }
 
-static int validate(const sm_weights* w, const sm_forward_io* io) {
+static int validate(const sm_weights* w, const sm_forward_io* io, const sm_encoder_taps* tp) {
     SM_REQUIRE(w && io, "sm_maskformer_forward: null arguments");
     SM_REQUIRE(w->patch == 8 || w->patch == 16, "sm_maskformer_forward: patch=%d (8 or 16)", w->patch);
     SM_REQUIRE(w->gemm_mode >= 0 && w->gemm_mode <= 3, "sm_maskformer_forward: gemm_mode=%d (0..3)", w->gemm_mode);
@@ -618,8 +677,8 @@ static int validate(const sm_weights* w, const sm_forward_io* io) {
     SM_REQUIRE(!io->attn_only || want_attn, "sm_maskformer_forward: attn_only needs last_attn or last_attn_cls");
     SM_REQUIRE(!want_attn || w->gemm_mode != 3,
                "sm_maskformer_forward: last_attn / last_attn_cls are not available in gemm_mode 3 (the one-MFMA diagnostic)");
-    if (io->attn_only)
-        ;  // the forward stops inside block 12: no other output is written
+    if (io->attn_only || (tp && tp->stop))
+        ;  // the forward stops inside the encoder: no other output is written
     else if (!io->encoder_only)
         SM_REQUIRE(io->mask_pred && (io->objectness || w->mask_head_ffn || w->no_objectness) && io->features,
                    "sm_maskformer_forward: null output");
@@ -627,6 +686,26 @@ static int validate(const sm_weights* w, const sm_forward_io* io) {
         SM_REQUIRE(io->patch_tokens, "sm_maskformer_forward: encoder_only needs patch_tokens");
     SM_REQUIRE(io->attn_path >= 0 && io->attn_path <= 2, "sm_maskformer_forward: attn_path=%d (0 auto, 1 fused, 2 two launches)", io->attn_path);
     SM_REQUIRE(!(io->last_layer_only && w->mask_head_ffn), "sm_maskformer_forward: last_layer_only is the 3-D path (no ffn mask head)");
+    if (!tp) return SM_OK;
+    const uint32_t depth_bits = (1u << SM_ENC_DEPTH) - 1u;
+    SM_REQUIRE(w->gemm_mode != 3, "sm_maskformer_forward_taps: encoder taps are not available in gemm_mode 3 (the one-MFMA diagnostic)");
+    SM_REQUIRE(!(tp->layer_mask & ~depth_bits) && !(tp->attn_mask & ~depth_bits),
+               "sm_maskformer_forward_taps: layer_mask=0x%x attn_mask=0x%x (bits 0..%d: blocks 1..%d)", tp->layer_mask, tp->attn_mask,
+               SM_ENC_DEPTH - 1, SM_ENC_DEPTH);
+    SM_REQUIRE(tp->layer_mask || tp->attn_mask || tp->post_pe || tp->input_tokens || tp->patch_mean,
+               "sm_maskformer_forward_taps: nothing requested (empty masks, no post_pe / input_tokens / patch_mean)");
+    SM_REQUIRE((tp->layer_mask != 0) == (tp->tokens != nullptr), "sm_maskformer_forward_taps: layer_mask and tokens go together (mask 0x%x, tokens %s)",
+               tp->layer_mask, tp->tokens ? "set" : "NULL");
+    SM_REQUIRE((tp->attn_mask != 0) == (tp->attn || tp->attn_cls), "sm_maskformer_forward_taps: attn_mask and attn / attn_cls go together (mask 0x%x)",
+               tp->attn_mask);
+    SM_REQUIRE(tp->select >= SM_TAP_ALL && tp->select <= SM_TAP_PATCH, "sm_maskformer_forward_taps: select=%d (SM_TAP_ALL, _CLS, _PATCH)", tp->select);
+    SM_REQUIRE((tp->norm == 0 || tp->norm == 1) && (tp->stop == 0 || tp->stop == 1), "sm_maskformer_forward_taps: norm=%d stop=%d (0 or 1)",
+               tp->norm, tp->stop);
+    SM_REQUIRE(((uintptr_t)tp->tokens | (uintptr_t)tp->post_pe | (uintptr_t)tp->input_tokens | (uintptr_t)tp->patch_mean) % 16 == 0,
+               "sm_maskformer_forward_taps: token outputs must be 16-B aligned");
+    SM_REQUIRE(!io->attn_only, "sm_maskformer_forward_taps: attn_only with taps (set stop and ask for block 12 through attn_mask)");
+    SM_REQUIRE(!tp->stop || !(want_attn || io->encoder_only),
+               "sm_maskformer_forward_taps: stop with last_attn / last_attn_cls / encoder_only (ask for block 12 through attn_mask)");
     return SM_OK;
 }
 
@@ -637,16 +716,21 @@ extern "C" size_t sm_forward_workspace_bytes(const sm_weights* w, int32_t B, int
     return sm::carve(sm::make_shape(w, B, H, W), nullptr).total;
 }
 
-extern "C" int sm_maskformer_forward(const sm_weights* w, const sm_forward_io* io, void* workspace, size_t workspace_bytes,
-                                     void* stream) {
-    int rc = sm::validate(w, io);
+extern "C" int sm_maskformer_forward_taps(const sm_weights* w, const sm_forward_io* io, const sm_encoder_taps* taps, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+    int rc = sm::validate(w, io, taps);
     if (rc) return rc;
     const size_t need = sm_forward_workspace_bytes(w, io->B, io->H, io->W);
     if (!workspace || workspace_bytes < need || ((uintptr_t)workspace % 256) != 0) {
         sm::set_error("sm_maskformer_forward: workspace %zu B < %zu B needed (or not 256-B aligned)", workspace_bytes, need);
         return SM_ENOSPACE;
     }
-    return sm::forward(w, io, (float*)workspace, (hipStream_t)stream);
+    return sm::forward(w, io, taps, (float*)workspace, (hipStream_t)stream);
+}
+
+extern "C" int sm_maskformer_forward(const sm_weights* w, const sm_forward_io* io, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+    return sm_maskformer_forward_taps(w, io, nullptr, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sm_forward_timing(int enable) {

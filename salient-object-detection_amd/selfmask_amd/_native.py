@@ -99,6 +99,15 @@ class ForwardIO(C.Structure):
                 ("last_attn", fp), ("last_attn_cls", fp), ("attn_only", C.c_int32)]
 
 
+TAP_ALL, TAP_CLS, TAP_PATCH = range(3)  # sm_encoder_taps.select
+
+
+class EncoderTaps(C.Structure):
+    _fields_ = [("layer_mask", C.c_uint32), ("select", C.c_int32), ("norm", C.c_int32), ("tokens", fp), ("post_pe", fp),
+                ("input_tokens", fp), ("patch_mean", fp), ("attn_mask", C.c_uint32), ("attn", fp), ("attn_cls", fp),
+                ("stop", C.c_int32)]
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 64), ("launches", C.c_int32), ("total_us", C.c_double), ("overhead_us", C.c_double), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -244,6 +253,7 @@ STRUCTS = {
     "sm_present_image": PresentImage, "sm_jpeg_info": JpegInfo, "sm_jpeg_image": JpegImage, "sm_jpeg_segment": JpegSegment,
     "sm_jpeg_scan": JpegScan, "sm_png_image": PngImage, "sm_png_info": PngInfo, "sm_png_stream": PngStream,
     "sm_enc_layer": EncLayer, "sm_dec_layer": DecLayer, "sm_weights": Weights, "sm_forward_io": ForwardIO,
+    "sm_encoder_taps": EncoderTaps,
     "sm_conv_weight": ConvWeight, "sm_resnet_block": ResnetBlock, "sm_resnet50_weights": Resnet50Weights,
     "sm_kernel_time": KernelTime,
 }
@@ -354,6 +364,7 @@ SYMBOLS = {
                                       C.c_size_t, fp]),
     "sm_forward_workspace_bytes": (C.c_size_t, [C.POINTER(Weights), C.c_int32, C.c_int32, C.c_int32]),
     "sm_maskformer_forward": (C.c_int, [C.POINTER(Weights), C.POINTER(ForwardIO), fp, C.c_size_t, fp]),
+    "sm_maskformer_forward_taps": (C.c_int, [C.POINTER(Weights), C.POINTER(ForwardIO), C.POINTER(EncoderTaps), fp, C.c_size_t, fp]),
     "sm_forward_timing": (C.c_int, [C.c_int]),
     "sm_forward_timing_read": (C.c_int, [C.POINTER(KernelTime), C.c_int]),
 }

@@ -2,8 +2,9 @@
 
 Same constructor arguments, same 267-tensor ``state_dict`` (so ``selfmask_nq20.pt`` loads unchanged), same
 ``forward(x, encoder_only=False, skip_decoder=False) -> dict``; the arithmetic runs in libselfmask_hip.so.
-The sub-modules below are parameter containers only (they give the parameters the reference's names); their own
-``forward`` methods are never called on the product path.
+The sub-modules below are parameter containers only (they give the parameters the reference's names); they hold no
+arithmetic of their own.  ``model.encoder`` carries the reference's call surface (the per-layer dict, get_tokens, ...) and
+delegates every call to the MaskFormer that owns it.
 """
 from math import ceil
 from typing import Dict, Optional
@@ -63,13 +64,86 @@ class VisionTransformerParams(nn.Module):
         self.n_heads = num_heads
         self.patch_size = patch_size
 
+    def _need_owner(self, what: str):
+        owner = self.__dict__.get("_owner")
+        if owner is None:
+            raise RuntimeError(f"this encoder is a parameter container: {what} needs the MaskFormer that owns it")
+        return owner
+
     def get_last_selfattention(self, x: torch.Tensor) -> torch.Tensor:
         """vision_transformer.py:307-314: the post-softmax attention of the last block, (B, heads, N, N) with N = 1 + gh*gw.
         The arithmetic lives in the owning MaskFormer's forward (``MaskFormer.get_last_selfattention``)."""
-        owner = self.__dict__.get("_owner")
-        if owner is None:
-            raise RuntimeError("this encoder is a parameter container: get_last_selfattention needs the MaskFormer that owns it")
-        return owner.get_last_selfattention(x)
+        return self._need_owner("get_last_selfattention").get_last_selfattention(x)
+
+    # ---- the DINO feature-extraction family (vision_transformer.py:293-497).  Every method is a selection of what the device taps
+    # give (MaskFormer.encoder_taps); all of them are defined on prepare_tokens' tokens (:269-281): the input zero-padded to the patch
+    # size, the position table interpolated to the token grid.  get_tokens, forward_features, forward_return_n_last_blocks and
+    # return_patch_emb_from_n_last_blocks call interpolate_pos_encoding without its `size` argument in the reference and raise there:
+    # what is built is their evident intent, selections of the dict forward() returns.
+    def forward(self, x: torch.Tensor, layer: Optional[str] = None):
+        """vision_transformer.py:293-304: the dict ``layer1 .. layer12`` of (B, N, 384) final-normed block outputs (views of one
+        (B, 12, N, 384) stack), or the one tensor for ``layer="layer7"`` (the encoder then stops after that block)."""
+        owner = self._need_owner("forward")
+        names = [f"layer{i + 1}" for i in range(self.depth)]
+        if layer is not None:
+            if layer not in names:
+                raise KeyError(layer)
+            return owner.encoder_layers(x, [names.index(layer)])[:, 0]
+        stack = owner.encoder_layers(x)
+        return {name: stack[:, i] for i, name in enumerate(names)}
+
+    def get_tokens(self, x: torch.Tensor, layers, patch_tokens: bool = False, norm: bool = True, input_tokens: bool = False,
+                   post_pe: bool = False) -> torch.Tensor:
+        """vision_transformer.py:316-357.  ``layers``: 0-based block indices (None: all twelve), taken in ascending order as the
+        reference's ``i in layers`` does.  Stacked along dim 1 in the reference's order: the input tokens (before the position
+        embedding), the post-PE tokens, then the blocks.  ``patch_tokens=False`` returns the CLS rows (B, k, 384), True ALL tokens
+        (B, k, N, 384) - the reference's naming."""
+        owner = self._need_owner("get_tokens")
+        if layers is not None and len(list(layers)) == 0 and (input_tokens or post_pe):
+            idx = []  # only the tokens in front of the blocks
+        else:
+            idx = sorted(set(owner._check_layers(layers)))  # refuses an empty list: the reference's torch.stack of nothing raises too
+        t = owner.encoder_taps(x, layers=idx, tokens="all" if patch_tokens else "cls", norm=norm, input_tokens=input_tokens,
+                               post_pe=post_pe)
+        parts = [t[k].unsqueeze(1) for k in ("input_tokens", "post_pe") if k in t] + ([t["tokens"]] if idx else [])
+        out = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+        return out if patch_tokens else out[:, :, 0, :]
+
+    def forward_features(self, x: torch.Tensor) -> torch.Tensor:
+        """vision_transformer.py:359-375: the final-normed CLS token, (B, 384)."""
+        return self._need_owner("forward_features").encoder_layers(x, [self.depth - 1], tokens="cls")[:, 0, 0]
+
+    def forward_return_n_last_blocks(self, x: torch.Tensor, n: int = 1, return_patch_avgpool: bool = False) -> torch.Tensor:
+        """vision_transformer.py:448-471: the normed CLS tokens of the ``n`` last blocks side by side, (B, 384 n), with
+        ``return_patch_avgpool`` followed by the mean of block 12's normed patch tokens, (B, 384 n + 384)."""
+        owner = self._need_owner("forward_return_n_last_blocks")
+        if not 1 <= n <= self.depth:
+            raise ValueError(f"n={n}: 1..{self.depth} last blocks")
+        t = owner.encoder_taps(x, layers=range(self.depth - n, self.depth), tokens="cls", patch_mean=return_patch_avgpool)
+        out = t["tokens"].reshape(x.shape[0], n * self.embed_dim)
+        return torch.cat((out, t["patch_mean"]), dim=-1) if return_patch_avgpool else out
+
+    def return_patch_emb_from_n_last_blocks(self, x: torch.Tensor, n: int = 1, return_patch_avgpool: bool = False) -> torch.Tensor:
+        """vision_transformer.py:473-497: the normed patch tokens of the ``n`` last blocks, (B, n_patches, 384, n)."""
+        owner = self._need_owner("return_patch_emb_from_n_last_blocks")
+        if return_patch_avgpool:
+            raise ValueError("return_patch_avgpool=True: the reference appends a (B, 384) mean to (B, n_patches, 384) tensors and its "
+                             "torch.stack cannot succeed; take the mean from forward_return_n_last_blocks")
+        if not 1 <= n <= self.depth:
+            raise ValueError(f"n={n}: 1..{self.depth} last blocks")
+        return owner.encoder_layers(x, range(self.depth - n, self.depth), tokens="patch").permute(0, 2, 3, 1)
+
+    def forward_selfattention(self, x: torch.Tensor, return_interm_attn: bool = False, cls_only: bool = False) -> torch.Tensor:
+        """vision_transformer.py:403-446.  False: the last block's attention (``get_last_selfattention``); True: every block's,
+        (12 B, 6, N, N), blocks concatenated along dim 0 as the reference does (``cls_only``: row 0 only, (.., 6, N)).
+        Defined on prepare_tokens' tokens like every other method here.  Off 224 x 224 the reference's own method differs: it
+        interpolates the position table with ``scale_factor=`` instead of ``size=`` (other sampling positions) and does not pad
+        the input to the patch size."""
+        owner = self._need_owner("forward_selfattention")
+        if not return_interm_attn:
+            return owner.get_last_selfattention(x, cls_only=cls_only)
+        t = owner.encoder_taps(x, attn_layers=range(self.depth), attn="cls" if cls_only else "full")
+        return t["attn"].flatten(0, 1)
 
     def make_input_divisible(self, x: torch.Tensor) -> torch.Tensor:
         """vision_transformer.py:260-267 (shape helper for callers; the HIP im2col pads implicitly)."""
@@ -370,17 +444,128 @@ class MaskFormer(nn.Module):
                 "sm_maskformer_forward")
         return out
 
+    # ---- encoder taps (sm_encoder_taps) ---------------------------------------------------------------------
+    _TAP_SELECT = {"all": N.TAP_ALL, "cls": N.TAP_CLS, "patch": N.TAP_PATCH}
+
+    def _check_layers(self, layers, what: str = "layers"):
+        """0-based block indices as a list; None = all twelve.  Empty, 12 and -1 are refused."""
+        idx = list(range(N.ENC_DEPTH)) if layers is None else [int(i) for i in layers]
+        if not idx:
+            raise ValueError(f"{what} is empty: name at least one block (0..{N.ENC_DEPTH - 1})")
+        bad = [i for i in idx if not 0 <= i < N.ENC_DEPTH]
+        if bad:
+            raise ValueError(f"{what}={bad}: 0-based block indices 0..{N.ENC_DEPTH - 1}")
+        return idx
+
+    def _check_tap_args(self, tokens: str = "all", attn: str = "full"):
+        if self.gemm_mode == "f16":
+            raise RuntimeError("encoder taps are not available in the 'f16' throughput-mode diagnostic")
+        if tokens not in self._TAP_SELECT:
+            raise ValueError(f"tokens={tokens!r}: 'all', 'cls' or 'patch'")
+        if attn not in ("full", "cls"):
+            raise ValueError(f"attn={attn!r}: 'full' or 'cls'")
+
+    def _new_taps(self, B: int, n_tok: int, dev, layers=(), tokens: str = "all", norm: bool = True, post_pe: bool = False,
+                  input_tokens: bool = False, patch_mean: bool = False, attn_layers=(), attn: str = "full", stop: bool = True):
+        """(sm_encoder_taps, {name: output tensor}) for one call.  Blocks are stacked in ASCENDING order whatever the order of
+        ``layers`` / ``attn_layers`` (duplicates count once)."""
+        self._check_tap_args(tokens, attn)
+        t, out = N.EncoderTaps(), {}
+        t.select, t.norm, t.stop = self._TAP_SELECT[tokens], 1 if norm else 0, 1 if stop else 0
+        R = {"all": n_tok, "cls": 1, "patch": n_tok - 1}[tokens]
+        new = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)  # noqa: E731
+        lay = sorted(set(layers))
+        if lay:
+            t.layer_mask = sum(1 << i for i in lay)
+            out["tokens"] = new(B, len(lay), R, N.EMBED)
+            t.tokens = out["tokens"].data_ptr()
+        for name, want, shape in (("post_pe", post_pe, (B, R, N.EMBED)), ("input_tokens", input_tokens, (B, R, N.EMBED)),
+                                  ("patch_mean", patch_mean, (B, N.EMBED))):
+            if want:
+                out[name] = new(*shape)
+                setattr(t, name, out[name].data_ptr())
+        alay = sorted(set(attn_layers))
+        if alay:
+            t.attn_mask = sum(1 << i for i in alay)
+            if attn == "cls":
+                out["attn"] = new(len(alay), B, N.HEADS, n_tok)
+                t.attn_cls = out["attn"].data_ptr()
+            else:
+                out["attn"] = new(len(alay), B, N.HEADS, n_tok, n_tok)
+                t.attn = out["attn"].data_ptr()
+        return t, out
+
+    @torch.no_grad()
+    def encoder_taps(self, x: torch.Tensor, layers=(), tokens: str = "all", norm: bool = True, post_pe: bool = False,
+                     input_tokens: bool = False, patch_mean: bool = False, attn_layers=(), attn: str = "full", attn_path=0,
+                     workspace: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """Tokens and attention of any encoder blocks in one stopped forward (sm_maskformer_forward_taps with ``stop``): the encoder
+        runs up to the last block asked for, the decoder not at all.  Returns the entries asked for:
+        "tokens" (B, k, R, 384) - the outputs of the blocks ``layers`` (0-based, ascending), final-normed (``norm``) or the raw
+        residual stream, R = N / 1 / n rows for ``tokens`` = "all" / "cls" / "patch"; "post_pe" and "input_tokens" (B, R, 384) - the
+        stream after / before the position embedding; "patch_mean" (B, 384) - the mean of block 12's normed patch rows; "attn" -
+        the post-softmax attention of the blocks ``attn_layers``, (k, B, 6, N, N) or with ``attn="cls"`` row 0 only, (k, B, 6, N).
+        Everything is defined on prepare_tokens' tokens (input zero-padded to the patch size, position table interpolated to the
+        grid).  ``attn_path`` as in ``get_last_selfattention``."""
+        self._check_tap_args(tokens, attn)
+        lay = [] if layers is not None and len(list(layers)) == 0 else self._check_layers(layers)  # () = none, None = all twelve
+        alay = [] if attn_layers is not None and len(list(attn_layers)) == 0 else self._check_layers(attn_layers, "attn_layers")
+        if not (lay or alay or post_pe or input_tokens or patch_mean):
+            raise ValueError("encoder_taps: nothing requested")
+        if not x.is_cuda:
+            raise RuntimeError("MaskFormer (MI355X) needs its input on a HIP device; there is no CPU fallback")
+        lib = N.load()
+        x = x.contiguous().float()
+        B, c, H, W = x.shape
+        assert c == 3, "expected an RGB image batch (B,3,H,W)"
+        p = self.encoder.patch_size
+        n_tok = ceil(H / p) * ceil(W / p) + 1
+        taps, out = self._new_taps(B, n_tok, x.device, lay, tokens, norm, post_pe, input_tokens, patch_mean, alay, attn, stop=True)
+        w = self._weights()
+        ws = workspace if workspace is not None else self._get_workspace(w, x)
+        io = N.ForwardIO()
+        io.x, io.B, io.H, io.W = x.data_ptr(), B, H, W
+        path = self._ATTN_PATHS.get(attn_path, attn_path)
+        if path not in (0, 1, 2):
+            raise ValueError(f"attn_path={attn_path!r}: 0 / 'auto', 1 / 'fused' or 2 / 'unfused'")
+        io.attn_path = path if path else self._ATTN_PATHS[self.attention_path]
+        N.check(lib.sm_maskformer_forward_taps(w, io, taps, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream),
+                "sm_maskformer_forward_taps")
+        return out
+
+    def encoder_layers(self, x: torch.Tensor, layers=None, tokens: str = "all", norm: bool = True, attn_path=0,
+                       workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """(B, len(layers), R, 384): the outputs of the encoder blocks ``layers`` (0-based indices as get_tokens uses them,
+        vision_transformer.py:346-349; None = all twelve) in the order asked, through the final norm as VisionTransformer.forward's
+        dict holds them (:299) or, ``norm=False``, the raw residual stream.  ``tokens``: "all" (R = N), "cls" (R = 1) or "patch"
+        (R = n).  The encoder stops after the last block asked for."""
+        idx = self._check_layers(layers)
+        stack = self.encoder_taps(x, layers=idx, tokens=tokens, norm=norm, attn_path=attn_path, workspace=workspace)["tokens"]
+        asc = sorted(set(idx))
+        return stack if idx == asc else stack[:, [asc.index(i) for i in idx]]
+
+    def forward_encoder(self, x: torch.Tensor) -> torch.Tensor:
+        """maskformer.py:99-113: the patch tokens of all twelve layers, (B, depth, 384, hw)."""
+        return self.encoder_layers(x, tokens="patch").permute(0, 1, 3, 2)
+
     @torch.no_grad()
     def forward(self, x: torch.Tensor, encoder_only: bool = False, skip_decoder: bool = False,
                 return_logits: bool = False, workspace: Optional[torch.Tensor] = None,
-                return_attention=False) -> Dict[str, torch.Tensor]:
+                return_attention=False, return_layers=None) -> Dict[str, torch.Tensor]:
         """x: (B,3,H,W) normalised image on a HIP device.  Output dict as maskformer.py:240-251:
         5-D path -> {"objectness" (B,L,nq,1), "mask_pred" (B,L,nq,s gh,s gw) in [0,1] (s = scale_factor), "features" (B,384)};
         3-D path (return_intermediate=False, use_binary_classifier=False) -> {"mask_pred" logits (B,nq,s gh,s gw),
         "features"}.  ``return_logits`` additionally returns the pre-sigmoid einsum as "mask_logits" and the decoder
         queries / encoder patch tokens (parity taps).  ``return_attention``: True adds "last_selfattention" (B,6,N,N), the last
         encoder block's post-softmax attention (vision_transformer.py:307-314), "cls" adds "cls_attention" (B,6,gh,gw), its CLS
-        row without the CLS column on the token grid; every other entry keeps the bits it has without it."""
+        row without the CLS column on the token grid; every other entry keeps the bits it has without it.  ``return_layers``: 0-based
+        encoder block indices (as ``encoder_layers``): adds "encoder_layers" (B, len, N, 384), their final-normed outputs in the order
+        asked, as a tap - every other entry keeps its bits."""
+        if return_layers is not None:
+            if encoder_only:
+                raise ValueError("return_layers with encoder_only: call encoder_layers(x, layers) for the tokens alone")
+            return_layers = self._check_layers(return_layers, "return_layers")
+            self._check_tap_args()
         if return_attention not in (False, True, "cls"):
             raise ValueError(f"return_attention={return_attention!r}: False, True or 'cls'")
         if return_attention and encoder_only:
@@ -443,8 +628,15 @@ class MaskFormer(nn.Module):
         elif return_attention:
             attn["last_selfattention"] = torch.empty((B, N.HEADS, gh * gw + 1, gh * gw + 1), device=dev, dtype=torch.float32)
             io.last_attn = attn["last_selfattention"].data_ptr()
-        N.check(lib.sm_maskformer_forward(w, io, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream),
-                "sm_maskformer_forward")
+        stream = torch.cuda.current_stream().cuda_stream
+        if return_layers is not None:
+            taps, tapped = self._new_taps(B, gh * gw + 1, dev, return_layers, stop=False)
+            N.check(lib.sm_maskformer_forward_taps(w, io, taps, ws.data_ptr(), ws.numel(), stream), "sm_maskformer_forward_taps")
+            asc = sorted(set(return_layers))
+            stack = tapped["tokens"]
+            attn["encoder_layers"] = stack if return_layers == asc else stack[:, [asc.index(i) for i in return_layers]]
+        else:
+            N.check(lib.sm_maskformer_forward(w, io, ws.data_ptr(), ws.numel(), stream), "sm_maskformer_forward")
         if not self.return_intermediate:  # 3-D path: last layer, un-sigmoided (maskformer.py:219-220)
             out = {"mask_pred": extras["mask_logits"][:, -1], "features": features}
         elif not self.use_binary_classifier:  # 5-D path with the ffn mask head: no objectness (maskformer.py:225,246-249)
