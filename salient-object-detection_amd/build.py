@@ -18,7 +18,7 @@ OBJ_DIR = os.path.join(HERE, "build")
 LIB = os.path.join(LIB_DIR, "libselfmask_hip.so")
 LIB_TUNING = os.path.join(LIB_DIR, "libselfmask_hip_tuning.so")
 SOURCES = ["gemm.hip", "gemm_f16x2.hip", "gemm_w16.hip", "layernorm.hip", "attention.hip", "attention_f16x2.hip", "attention_probs.hip",
-           "qkv_attention.hip", "misc.hip", "preprocess.hip", "eval.hip", "sod_metrics.hip", "voting.hip", "cluster.hip", "spectral.hip", "bilateral.hip", "predict.hip", "objects.hip", "present.hip", "png.hip", "png_decode.hip", "jpeg.hip", "jpeg_entropy.hip", "conv.hip", "encoder_taps.hip", "forward.hip"]
+           "qkv_attention.hip", "misc.hip", "preprocess.hip", "eval.hip", "selected.hip", "sod_metrics.hip", "voting.hip", "cluster.hip", "spectral.hip", "bilateral.hip", "predict.hip", "objects.hip", "present.hip", "png.hip", "png_decode.hip", "jpeg.hip", "jpeg_entropy.hip", "conv.hip", "encoder_taps.hip", "forward.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "forward_pieces.h"), os.path.join(CSRC, "attention_split.h"), os.path.join(CSRC, "upsample.h"), os.path.join(CSRC, "resample.h"),os.path.join(CSRC, "host_common.h"), os.path.join(CSRC, "jpeg_host.h"), os.path.join(CSRC, "png_host.h"), os.path.join(CSRC, "png_inflate.h"), os.path.join(HERE, "..", "include", "selfmask_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 

@@ -34,10 +34,19 @@ inline int check_launch(const char* what) {
     } while (0)
 
 // 64-lane butterfly reduction (wavefront shuffles; every lane ends with the total)
-__device__ __forceinline__ float wave_sum(float v) {
+template <typename T>
+__device__ __forceinline__ T wave_total(T v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
+}
+__device__ __forceinline__ float wave_sum(float v) { return wave_total(v); }
+
+// idx = quo * n + rem without an integer division: float reciprocal (inv_n = 1.0f / n) + one correction step (idx < 2^24)
+__device__ __forceinline__ void split_index(int idx, int n, float inv_n, int& quo, int& rem) {
+    quo = (int)((float)idx * inv_n);
+    rem = idx - quo * n;
+    if (rem < 0) { --quo; rem += n; } else if (rem >= n) { ++quo; rem -= n; }
 }
 
 // One wave-wide LDS-DMA: every lane fetches 16 B from its own global address, the 64 pieces land contiguously at LDS

@@ -30,12 +30,6 @@
 
 namespace sm {
 
-template <typename T>
-__device__ __forceinline__ T wave_total(T v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 constexpr int EV_THREADS = 256;
 constexpr int EV_PPT = 8;                       // pixels per thread
 constexpr int EV_CHUNK = EV_THREADS * EV_PPT;   // pixels per workgroup
@@ -72,13 +66,6 @@ __device__ __forceinline__ void sum_slots(int n, Add&& add) {
 struct Centroid { int X, Y; };
 __device__ __forceinline__ Centroid centroid(const GtStats& g) {
     return {(int)rintf(SM_DIV((float)g.sum_gx, (float)g.sum_g)), (int)rintf(SM_DIV((float)g.sum_gy, (float)g.sum_g))};
-}
-
-// pixel index -> (y, x) without an integer division: float reciprocal + one correction step (idx < 2^24)
-__device__ __forceinline__ void split_idx(int idx, int W, float inv_w, int& y, int& x) {
-    y = (int)((float)idx * inv_w);
-    x = idx - y * W;
-    if (x < 0) { --y; x += W; } else if (x >= W) { ++y; x -= W; }
 }
 
 constexpr int EV_QS = 32;  // query stride of the transposed mask copy (floats): one 128-B line per low-res pixel
@@ -119,11 +106,6 @@ __device__ __forceinline__ int slots_of(const sm_eval_image& im, int mh, int wal
     const int upw = walk_upw(walk);
     const int s = (band_units(im, mh) + EV_NW * upw - 1) / (EV_NW * upw);
     return s < nslot ? s : nslot;
-}
-
-// source coordinate per destination pixel: F.interpolate's 1 / scale_factor, or in / out when the mask is resized to the GT
-__device__ __forceinline__ float source_scale(float scale, int in_size, int out_size) {
-    return scale > 0.f ? 1.0f / scale : (float)in_size / (float)out_size;
 }
 
 // What every kernel needs to know about image b, built once at its top; the reducers read `slots` and `npx` alone.  A walk adds
@@ -417,7 +399,7 @@ __global__ __launch_bounds__(EV_THREADS) void eval_query_kernel(sm_eval_args a, 
             const int idx = base + k * EV_THREADS + threadIdx.x;
             if (idx >= ic.npx) break;
             int y, x;
-            split_idx(idx, ic.im.W, inv_w, y, x);
+            split_index(idx, ic.im.W, inv_w, y, x);
             const UpIdx uy = up_index(y, ic.sy, a.mh), ux = up_index(x, ic.sx, a.mw);
             const unsigned g = ic.gt[idx] != 0;
             if (g) { sg += 1; sgx += (unsigned)x; sgy += (unsigned)y; }
@@ -597,7 +579,7 @@ __global__ __launch_bounds__(EV_THREADS) void eval_sum_kernel(sm_eval_args a, co
         const int idx = c * EV_CHUNK + k * EV_THREADS + threadIdx.x;
         if (idx >= ic.npx) break;
         int y, x;
-        split_idx(idx, ic.im.W, inv_w, y, x);
+        split_index(idx, ic.im.W, inv_w, y, x);
         sp += (double)up_sample(m, a.mw, up_index(y, ic.sy, a.mh), up_index(x, ic.sx, a.mw));
     }
     sp = wave_total(sp);
@@ -773,7 +755,7 @@ __global__ __launch_bounds__(EV_THREADS) void eval_metrics_kernel(sm_eval_args a
         float p = 0.f;
         unsigned g = 0;
         if (valid) {
-            split_idx(idx, ic.im.W, inv_w, y, x);
+            split_index(idx, ic.im.W, inv_w, y, x);
             p = up_sample(m, a.mw, up_index(y, ic.sy, a.mh), up_index(x, ic.sx, a.mw));
             g = ic.gt[idx] != 0;
         }
@@ -906,62 +888,6 @@ __global__ __launch_bounds__(256) void eval_finalize_kernel(sm_eval_args a, cons
     a.rows[(int64_t)b * 16 + 14 + which] = (float)q;
 }
 
-// ---- refinement glue (BASELINE.json configs[2]): the picked query's mask up-sampled to the solver's resolution as the fp64
-// target bilateral_solver_output expects (bilateral_solver.py:181: target cast to np.double), and the solver's binary
-// result back as an fp32 one-query "mask_pred" for the metric kernels ----------------------------------------------------
-__global__ __launch_bounds__(256) void eval_upsample_selected_kernel(const float* __restrict__ masks, int64_t stride_b,
-                                                                    const float* __restrict__ rows, int sel_col,
-                                                                    double* __restrict__ out, int mh, int mw, int OH, int OW) {
-    const int b = blockIdx.y;
-    const int q = (int)rows[(int64_t)b * 16 + sel_col];  // query index written by eval_finalize_kernel (column 14 / 15)
-    const float* m = masks + (int64_t)b * stride_b + (int64_t)q * mh * mw;
-    const float sy = (float)mh / (float)OH, sx = (float)mw / (float)OW;  // F.interpolate(size=(OH, OW)): in / out
-    for (int p = blockIdx.x * 256 + threadIdx.x; p < OH * OW; p += gridDim.x * 256) {
-        const int y = p / OW, x = p - y * OW;
-        out[(int64_t)b * OH * OW + p] = (double)up_sample(m, mw, up_index(y, sy, mh), up_index(x, sx, mw));
-    }
-}
-
-__global__ __launch_bounds__(256) void eval_u8_to_f32_kernel(const unsigned char* __restrict__ src, float* __restrict__ dst, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) dst[i] = (float)src[i];
-}
-
-// native resolution: every image has its own (H, W) and its own packed plane at px_off[b]
-__global__ __launch_bounds__(256) void eval_upsample_selected_native_kernel(const float* __restrict__ masks, int64_t stride_b,
-                                                                           const float* __restrict__ rows, int sel_col,
-                                                                           const sm_bilateral_image* __restrict__ images,
-                                                                           double* __restrict__ out, int mh, int mw, float scale) {
-    const int b = blockIdx.y;
-    const sm_bilateral_image im = images[b];
-    const int npx = im.H * im.W;
-    if ((int)blockIdx.x * 256 >= npx) return;
-    const int q = (int)rows[(int64_t)b * 16 + sel_col];
-    const float* m = masks + (int64_t)b * stride_b + (int64_t)q * mh * mw;
-    const float sy = 1.0f / scale, sx = 1.0f / scale;  // F.interpolate(scale_factor=scale): as sm_evaluate_masks_f32 with scale > 0
-    double* o = out + im.px_off;
-    for (int p = blockIdx.x * 256 + threadIdx.x; p < npx; p += gridDim.x * 256) {
-        const int y = p / im.W, x = p - y * im.W;
-        const UpIdx uy = up_index(y, sy, mh), ux = up_index(x, sx, mw);
-        // a pixel outside the up-sampled plane (H_b > scale * mh: not a size the crop can produce) reads nothing
-        o[p] = uy.i0 < mh && ux.i0 < mw ? (double)up_sample(m, mw, uy, ux) : 0.0;
-    }
-}
-
-__global__ __launch_bounds__(256) void eval_planes_u8_to_f32_kernel(const unsigned char* __restrict__ src,
-                                                                   const sm_bilateral_image* __restrict__ images,
-                                                                   float* __restrict__ dst, int Hmax, int Wmax) {
-    const int b = blockIdx.y;
-    const sm_bilateral_image im = images[b];
-    const int npx = im.H * im.W;
-    if ((int)blockIdx.x * 256 >= npx || im.H > Hmax || im.W > Wmax) return;
-    const unsigned char* s = src + im.px_off;
-    float* d = dst + (int64_t)b * Hmax * Wmax;
-    for (int p = blockIdx.x * 256 + threadIdx.x; p < npx; p += gridDim.x * 256) {
-        const int y = p / im.W, x = p - y * im.W;
-        d[(int64_t)y * Wmax + x] = (float)s[p];
-    }
-}
-
 struct EvalWs { QueryStats *qs, *qpart; GtStats *gs, *gpart; MetricCounts* cnt; double* part; float* maskT; int *sel, *ytab; float* thr_adapt; size_t total; };
 
 static EvalWs carve_eval(int B, int nq, int nchunk, int mh, int plane, char* base) {
@@ -998,44 +924,6 @@ static const int SM_EVAL_MAX_QUERIES = 960;  // one thread per query in the redu
 extern "C" size_t sm_evaluate_workspace_bytes(int32_t B, int32_t nq, int32_t mh, int32_t mw, int32_t max_pixels) {
     if (B <= 0 || nq <= 0 || nq > SM_EVAL_MAX_QUERIES || mh <= 0 || mw <= 0 || max_pixels <= 0 || max_pixels > SM_EVAL_MAX_PIXELS) return 0;
     return sm::carve_eval(B, nq, sm::eval_slots(max_pixels, mh), mh, mh * mw, nullptr).total;
-}
-
-extern "C" int sm_upsample_selected_f64(const float* masks, int64_t mask_stride_b, const float* rows, int32_t sel_col, double* out,
-                                        int32_t B, int32_t mh, int32_t mw, int32_t OH, int32_t OW, void* stream) {
-    SM_REQUIRE(masks && rows && out && B > 0 && mh > 0 && mw > 0 && OH > 0 && OW > 0 && (sel_col == 14 || sel_col == 15),
-               "sm_upsample_selected_f64: bad arguments (sel_col 14 = picked query, 15 = upper bound)");
-    const int gx = (OH * OW + 255) / 256 < 256 ? (OH * OW + 255) / 256 : 256;
-    hipLaunchKernelGGL(sm::eval_upsample_selected_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, masks, mask_stride_b, rows,
-                       sel_col, out, mh, mw, OH, OW);
-    return sm::check_launch("sm_upsample_selected_f64");
-}
-
-extern "C" int sm_mask_u8_to_f32(const uint8_t* src, float* dst, int64_t n, void* stream) {
-    SM_REQUIRE(src && dst && n > 0, "sm_mask_u8_to_f32: bad arguments");
-    const int64_t g = (n + 255) / 256;
-    hipLaunchKernelGGL(sm::eval_u8_to_f32_kernel, dim3((int)(g < 2048 ? g : 2048)), dim3(256), 0, (hipStream_t)stream, src, dst, n);
-    return sm::check_launch("sm_mask_u8_to_f32");
-}
-
-extern "C" int sm_upsample_selected_native_f64(const float* masks, int64_t mask_stride_b, const float* rows, int32_t sel_col,
-                                               const sm_bilateral_image* images, double* out, int32_t B, int32_t mh,
-                                               int32_t mw, float scale, int32_t max_pixels, void* stream) {
-    SM_REQUIRE(masks && rows && images && out && B > 0 && B <= 65535 && mh > 0 && mw > 0 && scale > 0.f && max_pixels > 0 &&
-                   (sel_col == 14 || sel_col == 15),
-               "sm_upsample_selected_native_f64: bad arguments (sel_col 14 = picked query, 15 = upper bound; scale > 0)");
-    const int gx = (max_pixels + 255) / 256 < 256 ? (max_pixels + 255) / 256 : 256;
-    hipLaunchKernelGGL(sm::eval_upsample_selected_native_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, masks, mask_stride_b,
-                       rows, sel_col, images, out, mh, mw, scale);
-    return sm::check_launch("sm_upsample_selected_native_f64");
-}
-
-extern "C" int sm_mask_planes_u8_to_f32(const uint8_t* src, const sm_bilateral_image* images, float* dst, int32_t B,
-                                        int32_t Hmax, int32_t Wmax, int32_t max_pixels, void* stream) {
-    SM_REQUIRE(src && images && dst && B > 0 && B <= 65535 && Hmax > 0 && Wmax > 0 && max_pixels > 0,
-               "sm_mask_planes_u8_to_f32: bad arguments");
-    const int gx = (max_pixels + 255) / 256 < 256 ? (max_pixels + 255) / 256 : 256;
-    hipLaunchKernelGGL(sm::eval_planes_u8_to_f32_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, src, images, dst, Hmax, Wmax);
-    return sm::check_launch("sm_mask_planes_u8_to_f32");
 }
 
 extern "C" int sm_evaluate_masks_f32(const sm_eval_args* a, void* stream) {

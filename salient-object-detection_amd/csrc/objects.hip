@@ -62,11 +62,6 @@ __device__ __forceinline__ void ob_union(int* parent, int a, int b) {
     }
 }
 
-__device__ __forceinline__ int ob_wave_total(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __device__ __forceinline__ int ob_wave_incl_scan(int v, int lane) {
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
@@ -197,7 +192,7 @@ __device__ __forceinline__ int ob_components(const sm_objects_args& a, ObShared&
         sh.mask_area = 0;
     }
     ob_sync();
-    roots = ob_wave_total(roots);
+    roots = wave_total(roots);
     if (lane == 0 && roots) atomicAdd(&sh.ncomp, roots);
     // rounds of "largest key below the previous one": key = area << 32 | ~first, unique per component
     unsigned long long prev = ~0ull;
@@ -361,10 +356,7 @@ __global__ __launch_bounds__(OB_THREADS) void objects_mass_kernel(sm_objects_arg
     const int* ws = (const int*)a.workspace + (int64_t)b * 5 * seg_cap;
     const int* __restrict__ Q = ws, *__restrict__ L = ws + seg_cap, *__restrict__ R = ws + 4 * (int64_t)seg_cap;
     const float* __restrict__ m = a.masks + (int64_t)b * a.mask_stride_b + (int64_t)a.best[b] * a.mh * a.mw;
-    // the scales of predict.hip's selected_mask
-    const float sy = a.scale > 0.f ? 1.0f / a.scale : (float)a.mh / (float)H;
-    const float sx = a.scale > 0.f ? 1.0f / a.scale : (float)a.mw / (float)W;
-    const MaskSrc<const float* __restrict__> src{m, a.mh, a.mw, sy, sx};
+    const auto src = mask_src<const float* __restrict__>(m, a.mh, a.mw, a.scale, H, W);  // the pixels the predictor's finish wrote
     if (tid < OB_MAX_OBJECTS) acc[tid] = 0;
     __syncthreads();
     for (int i = blockIdx.x * OB_WAVES + (tid >> 6); i < nseg; i += gridDim.x * OB_WAVES) {
@@ -373,7 +365,7 @@ __global__ __launch_bounds__(OB_THREADS) void objects_mass_kernel(sm_objects_arg
         const int q = Q[i], len = L[i], x = q / H, y0 = q - x * H;
         int sum = 0;  // at most 255 * 2^22
         for (int t = lane; t < len; t += 64) sum += (int)up_soft_u8(src.value(y0 + t, x));
-        sum = ob_wave_total(sum);
+        sum = wave_total(sum);
         if (lane == 0 && sum) atomicAdd(&acc[k], (unsigned long long)sum);
     }
     __syncthreads();

@@ -28,23 +28,10 @@ constexpr int PR_WAVES = PR_THREADS / 64;
 constexpr int PR_WAVE_POS = 4096;                    // positions per wave: 64 steps of 64
 constexpr int PR_CHUNK = PR_WAVES * PR_WAVE_POS;     // positions per workgroup
 constexpr int PR_LDS_FLOATS = 12288;                 // staging limit: 48 KiB, under the 64-KiB default of a workgroup
-constexpr int PR_MAX_PIXELS = 1 << 22;               // as sm_evaluate_masks_f32; split_pos needs positions < 2^24
+constexpr int PR_MAX_PIXELS = 1 << 22;               // as sm_evaluate_masks_f32; split_index needs positions < 2^24
 constexpr int PR_MAX_QUERIES = 960;
 
 __host__ __device__ inline int pr_units(int npx) { return (npx + PR_WAVE_POS - 1) / PR_WAVE_POS; }
-
-__device__ __forceinline__ int wave_total_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// position q = x * H + y -> (x, y) without an integer division: float reciprocal + one correction step (q < 2^24)
-__device__ __forceinline__ void split_pos(int q, int H, float inv_h, int& x, int& y) {
-    x = (int)((float)q * inv_h);
-    y = q - x * H;
-    if (y < 0) { --x; y += H; } else if (y >= H) { ++x; y -= H; }
-}
 
 // ---- pixel sources: value of pixel (y, x) as 0 / 1 -------------------------------------------------------------------------
 // (MaskSrc, the selected query's mask up-sampled, comes from upsample.h)
@@ -70,24 +57,24 @@ __device__ __forceinline__ void runs_chunk(const Src& src, int H, int npx, int c
     if (EMIT) {
         int s = 0;
         for (int u = lane; u < unit; u += 64) s += counts[u];
-        at = wave_total_i(s);
+        at = wave_total(s);
         if (unit == 0) {  // the image's first wave also reports the total
             const int nu = pr_units(npx);
             int t = 0;
             for (int u = lane; u < nu; u += 64) t += counts[u];
-            t = wave_total_i(t);
+            t = wave_total(t);
             if (lane == 0) { info[0] = t; info[1] = src(0, 0) ? 1 : 0; }
         }
     }
-    // the pixel before the range (pixel 0 itself for the first range: no change there)
+    // the pixel before the range (pixel 0 itself for the first range: no change there); a position is q = x * H + y
     int x, y;
-    split_pos(q0 > 0 ? q0 - 1 : 0, H, inv_h, x, y);
+    split_index(q0 > 0 ? q0 - 1 : 0, H, inv_h, x, y);
     unsigned long long carry = src(y, x) ? 1ull : 0ull;
     int n = 0;
     for (int qb = q0; qb < q1; qb += 64) {
         const int q = qb + lane;
         const bool in = q < q1;
-        split_pos(in ? q : q1 - 1, H, inv_h, x, y);
+        split_index(in ? q : q1 - 1, H, inv_h, x, y);
         const bool v = src(y, x);
         const unsigned long long m = __ballot(v), valid = __ballot(in);
         const unsigned long long c = (m ^ ((m << 1) | carry)) & valid;  // bit l: position qb + l differs from the one before
@@ -143,14 +130,13 @@ extern __shared__ float pr_tile[];
 template <bool STAGED>
 __device__ __forceinline__ auto selected_mask(const sm_predict_args& a, int b, const sm_bilateral_image& im) {
     const float* __restrict__ m = a.masks + (int64_t)b * a.mask_stride_b + (int64_t)a.best[b] * a.mh * a.mw;
-    const float sy = a.scale > 0.f ? 1.0f / a.scale : (float)a.mh / (float)im.H;
-    const float sx = a.scale > 0.f ? 1.0f / a.scale : (float)a.mw / (float)im.W;
     if constexpr (STAGED) {
+        const auto src = mask_src<const float*>(pr_tile, a.mh, a.mw, a.scale, im.H, im.W);
         for (int t = threadIdx.x; t < a.mh * a.mw; t += PR_THREADS) pr_tile[t] = m[t];
         __syncthreads();
-        return MaskSrc<const float*>{pr_tile, a.mh, a.mw, sy, sx};
+        return src;
     } else {
-        return MaskSrc<const float* __restrict__>{m, a.mh, a.mw, sy, sx};
+        return mask_src<const float* __restrict__>(m, a.mh, a.mw, a.scale, im.H, im.W);
     }
 }
 

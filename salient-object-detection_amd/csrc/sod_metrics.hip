@@ -1,5 +1,5 @@
 // E-measure and weighted F-measure of 8-bit saliency maps against binary ground truths (selfmask_amd/sod_metrics.py is the
-// definition), and the 8-bit plane of the evaluator's selected query that they are computed from.
+// definition).  The 8-bit plane of the evaluator's selected query that they are computed from: sm_upsample_selected_u8, selected.hip.
 //
 // Per call, for B images of any mix of sizes (image b's bytes at images[b].gt_off in both `pred` and `gt`):
 //   S1  histograms   a chunk of raster pixels per workgroup, two 256-bin histograms of p8 (foreground / background) in LDS by
@@ -21,7 +21,6 @@
 #include "common.h"
 
 #pragma clang fp contract(off)
-#include "upsample.h"
 
 #include <math.h>
 
@@ -326,27 +325,6 @@ __global__ __launch_bounds__(SD_THREADS) void sod_finish_kernel(const sm_eval_im
     o[3] = wfm;
 }
 
-// ---- the 8-bit plane of the selected query ----
-__global__ __launch_bounds__(256) void sod_upsample_u8_kernel(const float* __restrict__ masks, int64_t stride_b, const float* __restrict__ rows,
-                                                              int sel_col, const sm_eval_image* __restrict__ images,
-                                                              unsigned char* __restrict__ out, int mh, int mw, float scale) {
-    const int b = blockIdx.y;
-    const sm_eval_image im = images[b];
-    const int npx = im.H * im.W;
-    if ((int)blockIdx.x * 256 >= npx) return;
-    const int q = (int)rows[(int64_t)b * 16 + sel_col];
-    const float* __restrict__ m = masks + (int64_t)b * stride_b + (int64_t)q * mh * mw;
-    // the scales of sm_evaluate_masks_f32: scale_factor with crop, or a resize to (H, W)
-    const float sy = scale > 0.f ? 1.0f / scale : (float)mh / (float)im.H;
-    const float sx = scale > 0.f ? 1.0f / scale : (float)mw / (float)im.W;
-    const MaskSrc<const float* __restrict__> src{m, mh, mw, sy, sx};
-    unsigned char* __restrict__ o = out + im.gt_off;
-    for (int p = blockIdx.x * 256 + threadIdx.x; p < npx; p += gridDim.x * 256) {
-        const int y = p / im.W, x = p - y * im.W;
-        o[p] = (unsigned char)up_soft_u8(src.value(y, x));
-    }
-}
-
 static SdTaps sod_taps() {
     SdTaps t;
     double h[49], mx = 0.0, sum = 0.0;
@@ -419,17 +397,4 @@ extern "C" int sm_sod_metrics_u8(const uint8_t* pred, const uint8_t* gt, const s
         hipLaunchKernelGGL(sm::sod_finish_kernel, dim3(B), dim3(sm::SD_THREADS), 0, st, images, h, w.part, nchunk, out);
     }
     return sm::check_launch("sm_sod_metrics_u8");
-}
-
-extern "C" int sm_upsample_selected_u8(const float* masks, int64_t mask_stride_b, const float* rows, int32_t sel_col,
-                                       const sm_eval_image* images, uint8_t* out, int32_t B, int32_t mh, int32_t mw, float scale,
-                                       int32_t max_pixels, void* stream) {
-    SM_REQUIRE(masks && rows && images && out && B > 0 && B <= 65535 && mh > 0 && mw > 0 && scale >= 0.f && max_pixels > 0 &&
-                   max_pixels <= sm::SD_MAX_PIXELS && (sel_col == 14 || sel_col == 15),
-               "sm_upsample_selected_u8: bad arguments (sel_col 14 = picked query, 15 = upper bound; scale >= 0; max_pixels <= %d)",
-               sm::SD_MAX_PIXELS);
-    const int gx = (max_pixels + 255) / 256 < 256 ? (max_pixels + 255) / 256 : 256;
-    hipLaunchKernelGGL(sm::sod_upsample_u8_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, masks, mask_stride_b, rows, sel_col,
-                       images, out, mh, mw, scale);
-    return sm::check_launch("sm_upsample_selected_u8");
 }

@@ -1,6 +1,7 @@
 // The bilinear up-samples that more than one file needs.  align_corners=False on one query mask, shared by the evaluator's metric
-// kernels (eval.hip) and the predictor's finish (predict.hip): both must give a pixel the same bits, so both evaluate it with these
-// functions.  align_corners=True on channels-last features (upsample_aligned_kernel): one kernel for cluster.hip and conv.hip.
+// kernels (eval.hip), the predictor's finish (predict.hip), the object finder (objects.hip) and the selected-mask planes
+// (selected.hip): all must give a pixel the same bits, so all evaluate it with these functions.  align_corners=True
+// on channels-last features (upsample_aligned_kernel): one kernel for cluster.hip and conv.hip.
 #pragma once
 #include "common.h"
 
@@ -42,13 +43,26 @@ struct MaskSrc {
     Ptr m;
     int mh, mw;
     float sy, sx;
+    // of a pixel that is known to lie inside the up-sampled plane
+    __device__ __forceinline__ float inside(int y, int x) const { return up_sample(m, mw, up_index(y, sy, mh), up_index(x, sx, mw)); }
     __device__ __forceinline__ float value(int y, int x) const {
         const UpIdx uy = up_index(y, sy, mh), ux = up_index(x, sx, mw);
-        // a pixel outside the up-sampled plane (H_b > scale * mh) is 0, as in eval_upsample_selected_native_kernel
+        // a pixel outside the up-sampled plane (H_b > scale * mh: not a size the crop can produce) is 0
         return uy.i0 < mh && ux.i0 < mw ? up_sample(m, mw, uy, ux) : 0.f;
     }
     __device__ __forceinline__ bool operator()(int y, int x) const { return value(y, x) > 0.5f; }
 };
+
+// source coordinate per destination pixel: F.interpolate's 1 / scale_factor, or in / out when the mask is resized to the image
+__device__ __forceinline__ float source_scale(float scale, int in_size, int out_size) {
+    return scale > 0.f ? 1.0f / scale : (float)in_size / (float)out_size;
+}
+
+// mask m (mh x mw) as image (H, W) sees it: scale > 0: F.interpolate(scale_factor=scale)[..., :H, :W]; 0: F.interpolate(size=(H, W))
+template <typename Ptr>
+__device__ __forceinline__ MaskSrc<Ptr> mask_src(Ptr m, int mh, int mw, float scale, int H, int W) {
+    return {m, mh, mw, source_scale(scale, mh, H), source_scale(scale, mw, W)};
+}
 
 // F.interpolate(mode="bilinear", align_corners=True) by an integer factor on channels-last data, C % 4 == 0: image b's (gh, gw, C)
 // rows start at in + b * strideb, up is dense (B, sf gh, sf gw, C).  Source coordinate o * (in - 1) / (out - 1) (ATen

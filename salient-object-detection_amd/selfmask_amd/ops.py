@@ -343,70 +343,75 @@ class GtBatch:
     array.  Build it once per batch (the evaluator's data loader side), reuse it across calls."""
 
     def __init__(self, gts, device):
-        B = len(gts)
-        descr = (N.EvalImage * B)()
-        off, flat = 0, []
-        for b, g in enumerate(gts):
+        for g in gts:
             if g.dtype != torch.uint8 or g.dim() != 2:
                 raise RuntimeError("ground-truth masks must be 2-D uint8 tensors")
-            descr[b].gt_off, descr[b].H, descr[b].W = off, g.shape[0], g.shape[1]
-            off += g.numel()
-            flat.append(g.reshape(-1))
-        self.B = B
-        self.shapes = [(int(g.shape[0]), int(g.shape[1])) for g in gts]
-        self.offsets = [int(descr[b].gt_off) for b in range(B)]
-        self.gt_all = (flat[0] if B == 1 else torch.cat(flat)).to(device)
-        self.images = torch.frombuffer(bytearray(bytes(descr)), dtype=torch.uint8).to(device)
+        flat = [g.reshape(-1) for g in gts]
+        self._build([tuple(g.shape) for g in gts], None, (flat[0] if len(gts) == 1 else torch.cat(flat)).to(device),
+                    lambda table: torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(device))
+
+    def _build(self, shapes, offsets, gt_all, images) -> "GtBatch":
+        """The one builder: image b's (H, W) bytes at ``gt_all[offsets[b]:]`` (``offsets`` None: the planes lie end to end).  Fills the
+        host sm_eval_image table (sm_sod_metrics_u8 checks it and sizes its grids from it), ``max_pixels`` and ``extent`` once;
+        ``images`` is that table on the device, or the caller's way to bring the host table there."""
+        self.shapes = [(int(h), int(w)) for h, w in shapes]
+        self.B = len(self.shapes)
+        if offsets is None:
+            offsets = [sum(h * w for h, w in self.shapes[:b]) for b in range(self.B)]
+        self.offsets = [int(o) for o in offsets]
+        self.host = (N.EvalImage * self.B)()
+        for e, (h, w), off in zip(self.host, self.shapes, self.offsets):
+            e.gt_off, e.H, e.W = off, h, w
+        self.max_pixels = max(h * w for h, w in self.shapes)
+        self.extent = max(off + h * w for (h, w), off in zip(self.shapes, self.offsets))
+        self.gt_all = gt_all
+        self.images = images(self.host) if callable(images) else images
+        return self
+
+    @classmethod
+    def from_packed(cls, packed, device) -> "GtBatch":
+        """GtBatch from pipeline.pack_gts' page-locked buffers: two asynchronous H2D copies on the current stream."""
+        from .pipeline import _POOL
+        flat, descr, shapes = packed
+        gb = cls.__new__(cls)._build(shapes, None, flat.to(device, non_blocking=True), descr.to(device, non_blocking=True))
+        _POOL.release_after((flat, descr), torch.cuda.current_stream(device))
+        return gb
+
+    @classmethod
+    def from_device(cls, flat: torch.Tensor, shapes, offsets) -> "GtBatch":
+        """GtBatch over ground truth that is on the device already (``png_decode.decode_png_batch(mode="gt")``): image b's (H, W) bytes
+        at ``flat[offsets[b]:]``; only the descriptors travel, through a page-locked buffer on the current stream."""
+        from .pipeline import upload_tables
+        if flat.dtype != torch.uint8 or flat.dim() != 1 or flat.device.type != "cuda":
+            raise RuntimeError("GtBatch.from_device: a 1-D uint8 tensor on a HIP device")
+        if len(shapes) == 0 or len(offsets) != len(shapes):
+            raise ValueError("GtBatch.from_device: one offset per image, at least one image")
+        for b, ((h, w), off) in enumerate(zip(shapes, offsets)):
+            if off < 0 or off + h * w > flat.numel():
+                raise ValueError(f"GtBatch.from_device: image {b} ({h} x {w} at {off}) lies outside the buffer of {flat.numel()} bytes")
+        return cls.__new__(cls)._build(shapes, offsets, flat, lambda table: upload_tables([table], flat.device)[0][0])
 
 
-def _gtbatch_from_packed(packed, device) -> "GtBatch":
-    """GtBatch from pipeline.pack_gts' page-locked buffers: two asynchronous H2D copies on the current stream."""
-    from .pipeline import _POOL
-    flat, descr, shapes = packed
-    gb = GtBatch.__new__(GtBatch)
-    gb.B, gb.shapes = len(shapes), shapes
-    gb.offsets, off = [], 0
-    for h, w in shapes:  # pack_gts lays the planes end to end
-        gb.offsets.append(off)
-        off += h * w
-    gb.gt_all = flat.to(device, non_blocking=True)
-    gb.images = descr.to(device, non_blocking=True)
-    _POOL.release_after((flat, descr), torch.cuda.current_stream(device))
-    return gb
+def _last_layer(mask_pred_last: torch.Tensor):
+    """-> B, nq, mh, mw of the last layer's masks as the kernels read them: dense per image, any batch stride
+    (``out["mask_pred"][:, -1]``)"""
+    B, nq, mh, mw = mask_pred_last.shape
+    assert mask_pred_last.stride(3) == 1 and mask_pred_last.stride(2) == mw and mask_pred_last.stride(1) == mh * mw
+    return B, nq, mh, mw
 
 
-GtBatch.from_packed = staticmethod(_gtbatch_from_packed)
+def _sel_col(which: str) -> int:
+    """the column of evaluate_masks' rows that holds the picked ("pick") or the upper-bound ("ub") query's index"""
+    if which not in ("pick", "ub"):
+        raise ValueError(f'which={which!r}: "pick" or "ub"')
+    return 14 if which == "pick" else 15
 
 
-def _gtbatch_from_device(flat: torch.Tensor, shapes, offsets) -> "GtBatch":
-    """GtBatch over ground truth that is on the device already (``png_decode.decode_png_batch(mode="gt")``): image b's (H, W) bytes
-    at ``flat[offsets[b]:]``; only the descriptors travel, through a page-locked buffer on the current stream."""
-    import ctypes
-    import numpy as np
-    from .pipeline import _POOL
-    if flat.dtype != torch.uint8 or flat.dim() != 1 or flat.device.type != "cuda":
-        raise RuntimeError("GtBatch.from_device: a 1-D uint8 tensor on a HIP device")
-    shapes = [(int(h), int(w)) for h, w in shapes]
-    B = len(shapes)
-    if B == 0 or len(offsets) != B:
-        raise ValueError("GtBatch.from_device: one offset per image, at least one image")
-    descr = (N.EvalImage * B)()
-    for b, ((h, w), off) in enumerate(zip(shapes, offsets)):
-        if off < 0 or off + h * w > flat.numel():
-            raise ValueError(f"GtBatch.from_device: image {b} ({h} x {w} at {off}) lies outside the buffer of {flat.numel()} bytes")
-        descr[b].gt_off, descr[b].H, descr[b].W = int(off), h, w
-    n = B * ctypes.sizeof(N.EvalImage)
-    host = _POOL.get(n, torch.uint8)
-    host.numpy()[:n] = np.frombuffer(bytes(descr), np.uint8)
-    gb = GtBatch.__new__(GtBatch)
-    gb.B, gb.shapes, gb.gt_all = B, shapes, flat
-    gb.offsets = [int(o) for o in offsets]
-    gb.images = host.to(flat.device, non_blocking=True)
-    _POOL.release_after((host,), torch.cuda.current_stream(flat.device))
-    return gb
-
-
-GtBatch.from_device = staticmethod(_gtbatch_from_device)
+def _fits_upsampled(shapes, mh: int, mw: int, scale: float, what: str) -> None:
+    """scale-factor mode crops the up-sampled mask to (H_b, W_b): no image may be larger than it"""
+    if scale > 0:
+        for (h, w) in shapes:
+            assert h <= int(mh * scale) and w <= int(mw * scale), f"{what} larger than the up-sampled mask"
 
 
 def evaluate_masks(mask_pred_last: torch.Tensor, objectness_last: torch.Tensor, gts, scale: float = 0.0,
@@ -420,20 +425,16 @@ def evaluate_masks(mask_pred_last: torch.Tensor, objectness_last: torch.Tensor, 
     ``extra=True`` appends ``extra`` (B, 2, 4) float64 to the result: e_adp, e_mean, e_max, wfm (sod_metrics) of the picked and of
     the upper-bound query's 8-bit plane (upsample_selected_u8), as the same call up-sampled them."""
     _dev(mask_pred_last, objectness_last)
-    B, nq, mh, mw = mask_pred_last.shape
-    assert mask_pred_last.stride(3) == 1 and mask_pred_last.stride(2) == mw and mask_pred_last.stride(1) == mh * mw
+    B, nq, mh, mw = _last_layer(mask_pred_last)
     assert objectness_last.stride(1) == 1
     dev = mask_pred_last.device
     gb = gts if isinstance(gts, GtBatch) else GtBatch(gts, dev)
     assert gb.B == B
-    if scale > 0:
-        for (h, w) in gb.shapes:
-            assert h <= int(mh * scale) and w <= int(mw * scale), "GT larger than the up-sampled mask"
+    _fits_upsampled(gb.shapes, mh, mw, scale, "GT")
     rows = torch.empty((B, 16), device=dev, dtype=torch.float32)
     ious = torch.empty((B, nq), device=dev, dtype=torch.float32) if return_ious else None
     lib = N.load()
-    max_pixels = max(h * w for (h, w) in gb.shapes)
-    wsb = lib.sm_evaluate_workspace_bytes(B, nq, mh, mw, max_pixels)
+    wsb = lib.sm_evaluate_workspace_bytes(B, nq, mh, mw, gb.max_pixels)
     if wsb == 0:
         raise ValueError("unsupported evaluate_masks shape")
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
@@ -443,7 +444,7 @@ def evaluate_masks(mask_pred_last: torch.Tensor, objectness_last: torch.Tensor, 
     a.gt, a.images, a.thresholds = gb.gt_all.data_ptr(), gb.images.data_ptr(), f_max_thresholds(dev).data_ptr()
     a.rows, a.ious, a.workspace, a.workspace_bytes = rows.data_ptr(), _ptr(ious), ws.data_ptr(), wsb
     a.B, a.nq, a.mh, a.mw, a.scale = B, nq, mh, mw, float(scale)
-    a.max_pixels = max_pixels
+    a.max_pixels = gb.max_pixels
     N.check(lib.sm_evaluate_masks_f32(a, _stream()), "sm_evaluate_masks_f32")
     if extra:
         ex = torch.stack([sod_metrics(upsample_selected_u8(mask_pred_last, rows, gb, scale, which), gb) for which in ("pick", "ub")],
@@ -456,13 +457,11 @@ def upsample_selected(mask_pred_last: torch.Tensor, rows: torch.Tensor, size, wh
     """(B, nq, mh, mw) probabilities + the (B, 16) rows of evaluate_masks -> (B, OH, OW) float64: the picked ("pick") or
     upper-bound ("ub") query's mask up-sampled bilinearly to ``size`` - the bilateral solver's target."""
     _dev(mask_pred_last, rows)
-    B, nq, mh, mw = mask_pred_last.shape
-    assert mask_pred_last.stride(3) == 1 and mask_pred_last.stride(2) == mw and mask_pred_last.stride(1) == mh * mw
+    B, nq, mh, mw = _last_layer(mask_pred_last)
     assert rows.shape == (B, 16) and rows.is_contiguous()
     out = torch.empty((B, size[0], size[1]), dtype=torch.float64, device=mask_pred_last.device)
-    N.check(N.load().sm_upsample_selected_f64(mask_pred_last.data_ptr(), mask_pred_last.stride(0), rows.data_ptr(),
-                                              14 if which == "pick" else 15, out.data_ptr(), B, mh, mw, size[0], size[1],
-                                              _stream()), "sm_upsample_selected_f64")
+    N.check(N.load().sm_upsample_selected_f64(mask_pred_last.data_ptr(), mask_pred_last.stride(0), rows.data_ptr(), _sel_col(which),
+                                              out.data_ptr(), B, mh, mw, size[0], size[1], _stream()), "sm_upsample_selected_f64")
     return out
 
 
@@ -480,15 +479,13 @@ def upsample_selected_native(mask_pred_last: torch.Tensor, rows: torch.Tensor, b
     F.interpolate(scale_factor=scale)[..., :H_b, :W_b], as float64 packed at ``batch.px_off`` (a bilateral_solver.MixedBatch) -
     the value evaluate_masks(..., scale=scale) scored for that image, and the target of the mixed-size bilateral solve."""
     _dev(mask_pred_last, rows)
-    B, nq, mh, mw = mask_pred_last.shape
-    assert mask_pred_last.stride(3) == 1 and mask_pred_last.stride(2) == mw and mask_pred_last.stride(1) == mh * mw
+    B, nq, mh, mw = _last_layer(mask_pred_last)
     assert rows.shape == (B, 16) and rows.is_contiguous() and batch.B == B and scale > 0
-    for (h, w) in batch.shapes:
-        assert h <= int(mh * scale) and w <= int(mw * scale), "image larger than the up-sampled mask"
+    _fits_upsampled(batch.shapes, mh, mw, scale, "image")
     out = torch.empty(batch.n_pixels, dtype=torch.float64, device=mask_pred_last.device)
-    N.check(N.load().sm_upsample_selected_native_f64(mask_pred_last.data_ptr(), mask_pred_last.stride(0), rows.data_ptr(),
-                                                     14 if which == "pick" else 15, batch.dev.data_ptr(), out.data_ptr(), B, mh, mw,
-                                                     float(scale), batch.max_pixels, _stream()), "sm_upsample_selected_native_f64")
+    N.check(N.load().sm_upsample_selected_native_f64(mask_pred_last.data_ptr(), mask_pred_last.stride(0), rows.data_ptr(), _sel_col(which),
+                                                     batch.dev.data_ptr(), out.data_ptr(), B, mh, mw, float(scale), batch.max_pixels,
+                                                     _stream()), "sm_upsample_selected_native_f64")
     return out
 
 
@@ -504,21 +501,6 @@ def mask_planes_u8_to_f32(binary: torch.Tensor, batch) -> torch.Tensor:
     return out
 
 
-def _gt_host_table(gb: "GtBatch"):
-    """The batch's sm_eval_image table on the host (sm_sod_metrics_u8 checks it and sizes its grids from it), built once."""
-    t = getattr(gb, "_host_table", None)
-    if t is None:
-        t = (N.EvalImage * gb.B)()
-        for b, ((h, w), off) in enumerate(zip(gb.shapes, gb.offsets)):
-            t[b].gt_off, t[b].H, t[b].W = off, h, w
-        gb._host_table = t
-    return t
-
-
-def _gt_extent(gb: "GtBatch") -> int:
-    return max(off + h * w for (h, w), off in zip(gb.shapes, gb.offsets))
-
-
 def upsample_selected_u8(mask_pred_last: torch.Tensor, rows: torch.Tensor, gts: "GtBatch", scale: float = 0.0,
                          which: str = "pick") -> torch.Tensor:
     """The 8-bit plane E-measure and weighted F are defined on (sm_upsample_selected_u8): image b's picked ("pick") or upper-bound
@@ -526,16 +508,13 @@ def upsample_selected_u8(mask_pred_last: torch.Tensor, rows: torch.Tensor, gts: 
     predictor's ``soft`` bytes.  Returns a flat uint8 buffer with image b's (H_b, W_b) plane at ``gts.offsets[b]``, where the ground
     truth lies in ``gts.gt_all``."""
     _dev(mask_pred_last, rows)
-    B, nq, mh, mw = mask_pred_last.shape
-    assert mask_pred_last.stride(3) == 1 and mask_pred_last.stride(2) == mw and mask_pred_last.stride(1) == mh * mw
-    assert rows.shape == (B, 16) and rows.is_contiguous() and gts.B == B and which in ("pick", "ub")
-    if scale > 0:
-        for (h, w) in gts.shapes:
-            assert h <= int(mh * scale) and w <= int(mw * scale), "GT larger than the up-sampled mask"
-    out = torch.empty(_gt_extent(gts), dtype=torch.uint8, device=mask_pred_last.device)
-    N.check(N.load().sm_upsample_selected_u8(mask_pred_last.data_ptr(), mask_pred_last.stride(0), rows.data_ptr(),
-                                             14 if which == "pick" else 15, gts.images.data_ptr(), out.data_ptr(), B, mh, mw,
-                                             float(scale), max(h * w for h, w in gts.shapes), _stream()), "sm_upsample_selected_u8")
+    B, nq, mh, mw = _last_layer(mask_pred_last)
+    assert rows.shape == (B, 16) and rows.is_contiguous() and gts.B == B
+    _fits_upsampled(gts.shapes, mh, mw, scale, "GT")
+    out = torch.empty(gts.extent, dtype=torch.uint8, device=mask_pred_last.device)
+    N.check(N.load().sm_upsample_selected_u8(mask_pred_last.data_ptr(), mask_pred_last.stride(0), rows.data_ptr(), _sel_col(which),
+                                             gts.images.data_ptr(), out.data_ptr(), B, mh, mw, float(scale), gts.max_pixels, _stream()),
+            "sm_upsample_selected_u8")
     return out
 
 
@@ -559,7 +538,7 @@ def sod_metrics(pred_u8, gts, return_hist: bool = False):
         if all(o == sum(h * w for h, w in gb.shapes[:b]) for b, o in enumerate(gb.offsets)):
             flat = pred_u8[0].reshape(-1) if gb.B == 1 else torch.cat([p.reshape(-1) for p in pred_u8])
         else:
-            flat = torch.empty(_gt_extent(gb), dtype=torch.uint8, device=dev)
+            flat = torch.empty(gb.extent, dtype=torch.uint8, device=dev)
             for p, o in zip(pred_u8, gb.offsets):
                 flat[o:o + p.numel()] = p.reshape(-1)
     else:
@@ -569,10 +548,9 @@ def sod_metrics(pred_u8, gts, return_hist: bool = False):
         if not flat.is_cuda or flat.dtype != torch.uint8 or flat.dim() != 1 or not flat.is_contiguous():
             raise RuntimeError("sod_metrics takes a flat uint8 buffer on a HIP device (no CPU fallback)")
     dev = flat.device
-    if flat.numel() < _gt_extent(gb) or gb.gt_all.numel() < _gt_extent(gb) or gb.gt_all.device != dev:
+    if flat.numel() < gb.extent or gb.gt_all.numel() < gb.extent or gb.gt_all.device != dev:
         raise ValueError("the prediction buffer (or the ground truth) is shorter than the batch's planes, or on another device")
-    B = gb.B
-    max_pixels = max(h * w for h, w in gb.shapes)
+    B, max_pixels = gb.B, gb.max_pixels
     lib = N.load()
     wsb = lib.sm_sod_metrics_workspace_bytes(B, max_pixels)
     if wsb == 0:
@@ -580,7 +558,7 @@ def sod_metrics(pred_u8, gts, return_hist: bool = False):
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
     out = torch.empty((B, 4), dtype=torch.float64, device=dev)
     hist = torch.empty((B, 2, 256), dtype=torch.int32, device=dev) if return_hist else None
-    N.check(lib.sm_sod_metrics_u8(flat.data_ptr(), gb.gt_all.data_ptr(), gb.images.data_ptr(), ctypes.addressof(_gt_host_table(gb)), B, max_pixels,
+    N.check(lib.sm_sod_metrics_u8(flat.data_ptr(), gb.gt_all.data_ptr(), gb.images.data_ptr(), ctypes.addressof(gb.host), B, max_pixels,
                                   out.data_ptr(), _ptr(hist), ws.data_ptr(), wsb, _stream()), "sm_sod_metrics_u8")
     return (out, hist) if return_hist else out
 
@@ -693,8 +671,7 @@ def predict_masks(mask_pred_last: torch.Tensor, objectness_last: torch.Tensor, t
     pixel and, on request, an RLE each; ``None``: nothing more is launched.  ``soft_png``: the soft planes are encoded as 8-bit grey
     PNG files on the device (``png_encode_async`` on the packed planes) and ``result()`` gains "soft_png": one ``bytes`` per image."""
     _dev(mask_pred_last, objectness_last)
-    B, nq, mh, mw = mask_pred_last.shape
-    assert mask_pred_last.stride(3) == 1 and mask_pred_last.stride(2) == mw and mask_pred_last.stride(1) == mh * mw
+    B, nq, mh, mw = _last_layer(mask_pred_last)
     assert objectness_last.shape == (B, nq) and objectness_last.stride(1) == 1 and table.B == B
     return PendingPredictions(mask_pred_last, objectness_last, table, scale, rle, binary, soft, max(1, min(int(cap), table.max_pixels)),
                               ObjectOptions.of(objects), soft_png)
